@@ -50,8 +50,19 @@ def test_baseline_players_and_argument_errors():
     assert sum(stats["player1_starts"].values()) == 60 and sum(stats["player2_starts"].values()) == 60
 
 
+@pytest.fixture
+def one_thread():
+    """torch on one CPU thread for this test only: the thread count is process-wide, and a later test in the same process that compares
+    its own CPU training with that of freshly started ranks needs the default back"""
+    import torch
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    yield
+    torch.set_num_threads(n)
+
+
 @pytest.mark.parametrize("tag", ["tictactoe", "connect4", "othello6", "othello8"])
-def test_optimize_network_matches_reference_losses(tag):
+def test_optimize_network_matches_reference_losses(tag, one_thread):
     """SURVEY 8f rank 3 / golden G6: AlphaZeroTrainer.optimize_network of the reference (trainer.py:320-381: loss
     -sum(pi log p)/B + sum((v - z)^2)/B, SGD momentum 0.9, weight decay 1e-4, ExponentialLR 0.9, train-mode BatchNorm) run by
     tools/gen_golden.py on the G4 memory with closed-form initial weights, dropout 0 and a pinned batch shuffle -> the
@@ -61,7 +72,6 @@ def test_optimize_network_matches_reference_losses(tag):
     from tools import closed_form as cf
     from alphazero_amd.games.registers import CONFIGS_REGISTER
     from alphazero_amd.trainer import AlphaZeroTrainer
-    torch.set_num_threads(1)
     game, gid, H, W, A, n = TAGS[tag]
     fx, mem_fx, net_fx = golden(f"sgd_{tag}.npz"), golden(f"selfplay_{tag}.npz"), golden(f"net_{tag}.npz")
     extra = {"board_size": n} if game == "othello" else {}

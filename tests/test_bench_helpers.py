@@ -134,3 +134,55 @@ def test_dry_run_prints_one_strict_line_last():
     assert len(lines[-1]) < 8192
     d = _strict(lines[-1])
     assert d["dryrun"] is True and d["n_gpus"] == 1
+
+
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+def _fake_samples(order, S=300, A=65):
+    """a step's samples as SelfPlayEngine.samples hands them over (CPU tensors here), rows in the given order"""
+    import numpy as np
+    import torch
+    rng = np.random.RandomState(5)
+    meta = np.stack([np.arange(S) // 3 + 100, np.arange(S) % 3, np.ones(S), np.arange(S) % A], axis=1).astype(np.int32)
+    full = {"state": torch.from_numpy(rng.randint(-1, 2, (S, 8, 8)).astype(np.int8)), "pi": torch.from_numpy(rng.rand(S, A).astype(np.float32)),
+            "z": torch.from_numpy(rng.randint(-1, 2, S).astype(np.int8)), "meta": torch.from_numpy(meta),
+            "visits": torch.from_numpy(rng.randint(0, 9, (S, A)).astype(np.int32))}
+    return {k: v[torch.from_numpy(order)] for k, v in full.items()}
+
+
+def _load_dump(d):
+    import os
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f), allow_pickle=False) for f in sorted(os.listdir(d))}
+
+
+def test_dump_outputs_orders_the_rows_and_keeps_float_arrays(tmp_path):
+    """the rows of a step come out in (game id, move index) order whatever order the engine appended them in; integer arrays as
+    float64 (exact), pi as float32"""
+    import numpy as np
+    bench._imports()
+    S = 300
+    bench.dump_outputs(str(tmp_path / "a"), _fake_samples(np.arange(S)))
+    bench.dump_outputs(str(tmp_path / "b"), _fake_samples(np.random.RandomState(2).permutation(S)))
+    a, b = _load_dump(tmp_path / "a"), _load_dump(tmp_path / "b")
+    assert sorted(a) == ["meta", "n_samples", "pi", "state", "visits", "z"]
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+        assert a[k].dtype == (np.float32 if k == "pi" else np.float64), k
+    ref = _fake_samples(np.arange(S))
+    assert a["n_samples"].tolist() == [S] and np.array_equal(a["meta"], ref["meta"].numpy()) and np.array_equal(a["state"], ref["state"].numpy())
+
+
+def test_dump_outputs_samples_a_large_step_the_same_way(tmp_path, monkeypatch):
+    """a step with more rows than DUMP_ROWS: a fixed, seeded subset of the ordered rows, the same for every row order"""
+    import numpy as np
+    bench._imports()
+    monkeypatch.setattr(bench, "DUMP_ROWS", 40)
+    S = 300
+    bench.dump_outputs(str(tmp_path / "a"), _fake_samples(np.arange(S)))
+    bench.dump_outputs(str(tmp_path / "b"), _fake_samples(np.random.RandomState(3).permutation(S)))
+    a, b = _load_dump(tmp_path / "a"), _load_dump(tmp_path / "b")
+    assert a["n_samples"].tolist() == [S] and a["meta"].shape == (40, 4) and a["pi"].shape == (40, 65)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    key = a["meta"][:, 0] * 3 + a["meta"][:, 1]
+    assert np.all(np.diff(key) > 0)  # still in (game id, move index) order

@@ -77,7 +77,7 @@ def test_config5_train_loop_on_othello8_equals_oracle(tmp_path):
 
 
 def _rehearse(n, *extra, timeout=1500, torchrun=False):
-    """`python bench.py --gpus n` started plainly (it launches its own ranks) or, torchrun=True, the way the driver starts it (`python -m
+    """`python bench.py --gpus n --full` started plainly (it launches its own ranks) or, torchrun=True, the way the driver starts it (`python -m
     torch.distributed.run --nnodes=1 --nproc-per-node n --master-addr 127.0.0.1 --master-port P bench.py --gpus n ...`), in rehearsal
     mode: gloo instead of RCCL, every rank on this box's one GPU, tiny sizes -> the parsed JSON line"""
     env = dict(os.environ, AZ_BENCH_BACKEND="gloo", AZ_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -90,7 +90,7 @@ def _rehearse(n, *extra, timeout=1500, torchrun=False):
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         launcher += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--sims", "8", *extra]
+    cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--sims", "8", "--full", *extra]
     import tempfile
     with tempfile.TemporaryDirectory() as ddir:
         env["AZ_BENCH_DETAIL_DIR"] = ddir
@@ -159,6 +159,41 @@ def test_bench_rehearsal_with_five_ranks_and_an_idle_rank():
     for a, b in zip(multi, one):
         assert a["samples_with_twins"] == b["samples_with_twins"] and a["eval_results"] == json.loads(json.dumps(b["eval_results"]))
         assert a["last_losses"] == b["last_losses"]
+
+
+def test_plain_bench_times_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: set-up, warm-up, K timed steps, the dump, the line --
+    no profiled step, CPU baseline or other legs.  Two runs with the same arguments dump the same arrays: the last timed step's samples
+    in (game id, move index) order"""
+    steps, warmup, games = 2, 1, 64
+    dumps = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+               "--games", str(games), "--sims", "8", "--dump-outputs", str(tmp_path / run)]
+        env = dict(os.environ, AZ_BENCH_DETAIL_DIR=str(tmp_path / f"detail_{run}"))
+        for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+            env.pop(k, None)
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0 and line["unit"] == "games/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["value"] > 0
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+        detail = json.load(open(tmp_path / f"detail_{run}" / line["detail"]))
+        assert not {"saturated", "config1", "config3", "config4", "config5", "latency", "tree_hbm"} & set(detail)
+        assert set(detail["bench_seconds"]) == {"imports", "headline_build_warmup_timed", "until_line_of_record"}
+        dumps.append({f[:-4]: np.load(tmp_path / run / f, allow_pickle=False) for f in os.listdir(tmp_path / run)})
+    a, b = dumps
+    assert sorted(a) == ["meta", "n_samples", "pi", "state", "visits", "z"] and sorted(b) == sorted(a)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    n = int(a["n_samples"][0])
+    assert a["z"].shape[0] == n <= 128 * games and a["state"].shape == (n, 8, 8) and a["pi"].shape == (n, 65)
+    g, mv = a["meta"][:, 0], a["meta"][:, 1]
+    last = warmup + steps - 1  # the games of the last timed step
+    assert g.min() == last * games and g.max() == (last + 1) * games - 1
+    assert np.all(np.diff(g * 1000 + mv) > 0)
+    assert np.all(np.isfinite(a["pi"])) and set(np.unique(a["z"])) <= {-1.0, 0.0, 1.0}
 
 
 def test_bench_fails_when_a_rank_fails():

@@ -2,7 +2,7 @@
 # rate against the number of concurrent games per GPU (the headline workload at other slot counts): one bench line per size, condensed
 # usage (on the MI355X box): bash tools/sweep_games.sh > gpurun_out/rXX_sweep.txt
 for G in 256 512 1024 2048 4096 8192 16384 32768 65536; do
-  python3 bench.py --games $G --steps 2 --warmup 1 --no-cpu-baseline --no-literal-configs 2>/dev/null | python3 -c "
+  python3 bench.py --full --games $G --steps 2 --warmup 1 --no-cpu-baseline --no-literal-configs 2>/dev/null | python3 -c "
 import json, sys
 for l in sys.stdin:
     if l.startswith('{'):
