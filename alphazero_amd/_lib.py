@@ -6,15 +6,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libaz_amd.so")
 _LIB = None
 
-AZ_OK, AZ_EINVAL, AZ_EHIP, AZ_ESTATE, AZ_ECAPACITY, AZ_EILLEGAL = 0, -1, -2, -3, -4, -5
+AZ_OK, AZ_EINVAL, AZ_EHIP, AZ_ESTATE, AZ_ECAPACITY, AZ_EILLEGAL, AZ_EEVAL = 0, -1, -2, -3, -4, -5, -6
 GAME_IDS = {"othello": 0, "connect4": 1, "tictactoe": 2}
 TIE_LOWEST, TIE_RANDOM = 0, 1
 NOISE_OFF, NOISE_PHILOX, NOISE_HASH = 0, 1, 2
-EVAL_NET, EVAL_FAKE, EVAL_ROLLOUT = 0, 1, 2
+EVAL_NET, EVAL_FAKE, EVAL_ROLLOUT, EVAL_EXTERNAL = 0, 1, 2, 3
 
 
 class AzError(RuntimeError):
     pass
+
+
+class EvalError(AzError):
+    """AZ_EEVAL: the external evaluator (az_engine_set_evaluator) reported a failure"""
 
 
 class EngineCfg(C.Structure):
@@ -31,6 +35,17 @@ class EngineStats(C.Structure):
                 ("error_flags", C.c_int32), ("graph_replays", C.c_int64), ("max_path_len", C.c_int32), ("reserved", C.c_int32)]
 
 
+class EvalBatch(C.Structure):
+    """az_eval_batch: the pending rows an AZ_EVAL_EXTERNAL engine hands its evaluator (d_ = device pointers)"""
+    _fields_ = [("cap", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("A", C.c_int32), ("d_count", C.c_void_p),
+                ("d_input", C.c_void_p), ("d_grids", C.c_void_p), ("d_players", C.c_void_p), ("d_slots", C.c_void_p),
+                ("d_probs", C.c_void_p), ("d_value", C.c_void_p)]
+
+
+# az_eval_fn: int (*)(void *user, const az_eval_batch *batch, void *stream)
+EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(EvalBatch), C.c_void_p)
+
+
 # every symbol include/az_amd.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "az_last_error", "az_version", "az_board_legal_batch", "az_board_play_batch", "az_board_status_batch",
@@ -39,7 +54,7 @@ SYMBOLS = [
     "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
     "az_engine_get_stats", "az_engine_samples", "az_engine_set_roots", "az_engine_search", "az_engine_search_begin", "az_engine_search_end", "az_engine_pair", "az_engine_advance",
     "az_engine_root_children", "az_engine_nodes_used", "az_engine_grow_pools", "az_engine_play", "az_augment_count", "az_augment",
-    "az_engine_set_sides", "az_engine_best_moves", "az_engine_baseline_moves", "az_engine_root_status",
+    "az_engine_set_sides", "az_engine_best_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
     "az_trainer_steps", "az_trainer_check", "az_trainer_debug",
 ]
@@ -93,6 +108,7 @@ def lib():
     L.az_engine_best_moves.argtypes = [vp, vp]
     L.az_engine_baseline_moves.argtypes = [vp, i32, C.c_uint32, vp]
     L.az_engine_root_status.argtypes = [vp, vp, vp, vp, vp]
+    L.az_engine_set_evaluator.argtypes = [vp, EVAL_FN, vp]
     L.az_augment_count.argtypes = [C.c_int, vp, i64, C.POINTER(i64), vp]
     L.az_augment.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.az_engine_root_children.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
@@ -142,4 +158,6 @@ def check(rc):
     msg = lib().az_last_error().decode(errors="replace")
     if rc in (AZ_EINVAL, AZ_EILLEGAL):
         raise ValueError(msg)
+    if rc == AZ_EEVAL:
+        raise EvalError(f"[{rc}] {msg}")
     raise AzError(f"[{rc}] {msg}")

@@ -87,15 +87,25 @@ class BatchedArena:
         self.tie_mode = None  # None: fair_max draws among equals (utils.py:28-34); tests pin it to engine.TIE_LOWEST (golden G7)
 
     def _engine(self, net, G, n_sim, seed):
-        from .engine import EVAL_NET, EVAL_ROLLOUT, NOISE_OFF, TIE_RANDOM, SelfPlayEngine
+        from .engine import EVAL_EXTERNAL, EVAL_NET, EVAL_ROLLOUT, NOISE_OFF, TIE_RANDOM, SelfPlayEngine
+        from .evaluators import check_normalizer, make_evaluator, route
         plies = 4 * self.H * self.W + 16
         from .engine import EVAL_FAKE
         rollout, fake = net == "mcts", net == "fake"  # "fake": the closed-form test network of tools/closed_form.py (golden G3 / G7)
         if isinstance(net, str) and not (rollout or fake):
             raise ValueError(f"player '{net}' has no search tree")
-        return SelfPlayEngine(self.gid, self.H, self.W, n_slots=G, n_sim=n_sim, net=None if isinstance(net, str) else net.to_hip(max_batch=G),
-                              evaluator=EVAL_ROLLOUT if rollout else (EVAL_FAKE if fake else EVAL_NET), dirichlet_alpha=None, dirichlet_epsilon=None, temp_max_step=-1, temp_min_step=0,
-                              tie_mode=TIE_RANDOM if self.tie_mode is None else self.tie_mode, noise_mode=NOISE_OFF, seed=seed, max_plies=plies, sample_capacity=16)
+        # a network the HIP net does not serve evaluates the leaves itself (external evaluator, evaluators.route)
+        external = not isinstance(net, str) and route(net) != "hip"
+        if external:
+            check_normalizer(net)
+        hipnet = None if isinstance(net, str) or external else net.to_hip(max_batch=G)
+        kind = EVAL_ROLLOUT if rollout else (EVAL_FAKE if fake else (EVAL_EXTERNAL if external else EVAL_NET))
+        eng = SelfPlayEngine(self.gid, self.H, self.W, n_slots=G, n_sim=n_sim, net=hipnet,
+                             evaluator=kind, dirichlet_alpha=None, dirichlet_epsilon=None, temp_max_step=-1, temp_min_step=0,
+                             tie_mode=TIE_RANDOM if self.tie_mode is None else self.tie_mode, noise_mode=NOISE_OFF, seed=seed, max_plies=plies, sample_capacity=16)
+        if external:
+            eng.set_evaluator(make_evaluator(net, self.game, self.H, self.W))
+        return eng
 
     def play_games(self, n_rounds, start_player=None, return_stats=True, shard=True, record_moves=False):
         """all rounds at once.  Inside a torch.distributed job (one process per GPU) the rounds are sharded over the

@@ -46,6 +46,7 @@
 #define ERR_PLY_CAP 4
 #define ERR_INTERNAL 8
 #define ERR_RNG 16  // the Gamma rejection sampler of the root noise gave up (p < 1e-38 per draw): reported, never papered over
+#define ERR_EVAL 32  // an external evaluator wrote a prior that is negative / not finite or a value that is not finite (k_ext_check)
 
 #define LPG 16          // lanes per game
 #define GPB (256 / LPG) // games per 256-thread block
@@ -1036,6 +1037,38 @@ __global__ void k_fakenet(EngDev E, const int *cnt) {
     E.value[g] = v;
 }
 
+// ---- AZ_EVAL_EXTERNAL: the caller evaluates the pending rows (az_engine_set_evaluator) ---------------------------------------
+// Before the callback: the absolute board (Board.grid, Board.player) and the slot of every pending row, so that the host can
+// rebuild the reference's Board.  Root pass: the fresh roots (k_root_prep); lock-step: the leaves k_step selected for evaluation.
+__global__ __launch_bounds__(256) void k_ext_export(EngDev E, int root_pass, int8_t *grids, int8_t *players, int *slots) {
+    const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (g >= E.G) return;
+    BB b;
+    if (root_pass) {
+        if (!E.root_fresh[g]) return;
+        b = {E.root_p1[g], E.root_m1[g], E.root_player[g]};
+    } else {
+        if (E.leaf_status[g] != LS_EVAL) return;
+        b = {E.leaf_p1[g], E.leaf_m1[g], E.leaf_player[g]};
+    }
+    const int row = E.row_of_slot[g];  // < G: rows are handed out once per pending slot
+    int8_t *dst = grids + (size_t)row * E.gd.cells;
+    for (int i = sub; i < E.gd.cells; i += LPG) dst[i] = (int8_t)az_cell_value(b, i / E.gd.W, i % E.gd.W);
+    if (sub == 0) { players[row] = (int8_t)b.player; slots[row] = g; }
+}
+
+// After the callback: outputs from outside the program are validated, never repaired.  A negative or non-finite prior or a
+// non-finite value raises ERR_EVAL and records the lowest offending slot.
+__global__ __launch_bounds__(256) void k_ext_check(EngDev E, const int *cnt, const int *slots, int *bad_slot) {
+    const int row = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (row >= E.G || row >= *cnt) return;
+    const float *pr = E.probs + (size_t)row * E.A;
+    bool bad = false;
+    for (int a = sub; a < E.A; a += LPG) bad |= !(pr[a] >= 0.0f) || __builtin_isinf(pr[a]);
+    if (sub == 0) bad |= !__builtin_isfinite(E.value[row]);
+    if (bad) { atomicOr(E.err, ERR_EVAL); atomicMin(bad_slot, slots[row]); }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -1062,6 +1095,13 @@ struct az_engine {
     int *scr_a = nullptr, *scr_b = nullptr;  // [G] int scratch of the arena entry points (moves in/out, status, scores)
     char *scr_c = nullptr;                   // [3 G] bytes
     int active_bound = 0;  // upper bound on the slots still searching (known per ply): caps the network batch, which picks the kernels
+    // AZ_EVAL_EXTERNAL only: the caller's evaluator and the rows it is shown besides nn_in
+    az_eval_fn ext_fn = nullptr;
+    void *ext_user = nullptr;
+    int8_t *ext_grids = nullptr, *ext_players = nullptr;
+    int *ext_slots = nullptr, *ext_bad = nullptr;  // ext_bad: lowest slot k_ext_check rejected
+    bool in_callback = false;  // the evaluator is running: calls into this engine are refused
+    bool unevaluated = false;  // a failed evaluation left leaves in the trees that were never evaluated (until set_roots / run)
 };
 
 int az_make_game_desc(int game, int H, int W, GameDesc *gd) {
@@ -1103,6 +1143,10 @@ static inline dim3 grid_for(int n, int bs) { return dim3((unsigned)((n + bs - 1)
 // the engine (they reorder host-side state -- sim_base, active_bound, the graph cache -- or read device state the search is writing)
 // refuses until the search has been ended
 #define AZ_NO_OPEN_SEARCH(e, who) AZ_REQUIRE(!(e)->search_open, AZ_ESTATE, who ": a search begun with az_engine_search_begin has not been ended (az_engine_search_end)")
+// AZ_EVAL_EXTERNAL: no call from inside the evaluator; none but set_roots / run (and destroy) after a failed evaluation
+#define AZ_NOT_IN_CALLBACK(e, who) AZ_REQUIRE(!(e)->in_callback, AZ_ESTATE, who ": called from inside the engine's own evaluator")
+#define AZ_USABLE(e, who) do { AZ_NOT_IN_CALLBACK(e, who); \
+    AZ_REQUIRE(!(e)->unevaluated, AZ_ESTATE, who ": an evaluation failed and left unevaluated leaves in the trees; az_engine_set_roots or az_engine_run resets the slots"); } while (0)
 
 extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *stream, az_engine **out) {
     AZ_REQUIRE(cfg && out, AZ_EINVAL, "null argument");
@@ -1113,6 +1157,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     AZ_REQUIRE(cfg->max_plies > 0 && cfg->sample_capacity > 0, AZ_EINVAL, "max_plies / sample_capacity must be positive");
     AZ_REQUIRE(cfg->temp_min_step >= cfg->temp_max_step, AZ_EINVAL,
                "temp_min_step should be greater than temp_max_step for linear scheduler.");  // schedulers.py:29-30
+    AZ_REQUIRE(cfg->evaluator >= AZ_EVAL_NET && cfg->evaluator <= AZ_EVAL_EXTERNAL, AZ_EINVAL, "unknown evaluator %d", cfg->evaluator);
     AZ_REQUIRE(cfg->evaluator != AZ_EVAL_NET || net != nullptr, AZ_ESTATE, "a network is required for AZ_EVAL_NET");
     if (cfg->evaluator == AZ_EVAL_NET)
         AZ_REQUIRE(az_net_action_size(net) == gd.A, AZ_EINVAL, "network action size %d != game action size %d",
@@ -1148,6 +1193,12 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_a, G);
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_b, G);
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_c, 3 * G);
+    if (cfg->evaluator == AZ_EVAL_EXTERNAL) {
+        if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_grids, G * gd.cells);
+        if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_players, G);
+        if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_slots, G);
+        if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_bad, 1);
+    }
     if (rc == AZ_OK && hipHostMalloc((void **)&e->h_ctr, sizeof(unsigned long long) * CTR_COUNT) != hipSuccess) rc = AZ_EHIP;
     if (rc == AZ_OK && hipHostMalloc((void **)&e->h_err, sizeof(int) * 3) != hipSuccess) rc = AZ_EHIP;
     if (rc != AZ_OK) { az_engine_destroy(e); return rc; }
@@ -1161,6 +1212,7 @@ static int check_err(az_engine *e);
 
 extern "C" void az_engine_destroy(az_engine *e) {
     if (!e) return;
+    if (e->in_callback) { fprintf(stderr, "az_engine_destroy: called from inside the engine's own evaluator; ignored\n"); return; }
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->search_open) {  // destroyed with a search still open: its errors would vanish with the engine -- say so
         e->search_open = false;
@@ -1176,9 +1228,36 @@ extern "C" void az_engine_destroy(az_engine *e) {
     delete e;
 }
 
-// network over the compacted leaf rows [0, *cnt)
-static int forward(az_engine *e, const int *cnt, int cap) {
+// AZ_EVAL_EXTERNAL: export the pending rows' boards, call the caller's evaluator, validate what it wrote.  `step`: the lock-step
+// index, -1 for the root-prior pass.  A failed callback ends the search here: nothing more is queued, the stream is drained.
+static int forward_external(az_engine *e, const int *cnt, int cap, int step) {
     EngDev &d = e->d;
+    dim3 gg((unsigned)((d.G + GPB - 1) / GPB)), gb(256);
+    hipLaunchKernelGGL(k_ext_export, gg, gb, 0, e->stream, d, step < 0 ? 1 : 0, e->ext_grids, e->ext_players, e->ext_slots);
+    AZ_HIP(hipGetLastError());
+    az_eval_batch b;
+    b.cap = cap; b.H = d.gd.H; b.W = d.gd.W; b.A = d.A;
+    b.d_count = cnt; b.d_input = d.nn_in; b.d_grids = e->ext_grids; b.d_players = e->ext_players; b.d_slots = e->ext_slots;
+    b.d_probs = d.probs; b.d_value = d.value;
+    e->in_callback = true;
+    const int rc = e->ext_fn(e->ext_user, &b, (void *)e->stream);
+    e->in_callback = false;
+    if (rc != 0) {
+        e->unevaluated = true;
+        (void)hipStreamSynchronize(e->stream);
+        if (step < 0) az_set_error("external evaluator returned %d in the root-prior pass", rc);
+        else az_set_error("external evaluator returned %d at lock-step %d", rc, step);
+        return AZ_EEVAL;
+    }
+    hipLaunchKernelGGL(k_ext_check, gg, gb, 0, e->stream, d, cnt, (const int *)e->ext_slots, e->ext_bad);
+    AZ_HIP(hipGetLastError());
+    return AZ_OK;
+}
+
+// network over the compacted leaf rows [0, *cnt)
+static int forward(az_engine *e, const int *cnt, int cap, int step) {
+    EngDev &d = e->d;
+    if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return forward_external(e, cnt, cap, step);
     if (e->cfg.evaluator == AZ_EVAL_FAKE) {
         hipLaunchKernelGGL(k_fakenet, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, cnt);
         return AZ_OK;
@@ -1198,12 +1277,12 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
         return AZ_OK;
     }
     hipLaunchKernelGGL(k_root_prep, gg, gb, 0, e->stream, d, 0, d.G);
-    AZ_TRY(forward(e, d.batch_cnt + 2, cap));
+    AZ_TRY(forward(e, d.batch_cnt + 2, cap, -1));
     hipLaunchKernelGGL(k_root_init, gg, gb, 0, e->stream, d, 0, d.G);
     for (int s = 0; s < n_sim; ++s) {
         if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
         else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
-        AZ_TRY(forward(e, d.batch_cnt + (s & 1), cap));
+        AZ_TRY(forward(e, d.batch_cnt + (s & 1), cap, s));
     }
     hipLaunchKernelGGL((k_step<true, false>), gg, gb, 0, e->stream, d, n_sim, 0, d.G);
     AZ_HIP(hipGetLastError());
@@ -1212,13 +1291,14 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
 
 static int do_search(az_engine *e, int n_sim) {
     EngDev &d = e->d;
+    AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL || e->ext_fn, AZ_ESTATE, "AZ_EVAL_EXTERNAL engine without an evaluator (az_engine_set_evaluator)");
     d.sim_base = e->sim_base;
     e->sim_base += (u32)n_sim;
     e->lockstep_iters += d.rollout ? n_sim : n_sim + 1;
     int cap = e->active_bound > 0 && e->active_bound < d.G ? e->active_bound : d.G;
     // graph replay needs launch parameters that do not change from search to search: the Philox counter base must be 0
     // (one search per root, as in self-play and the arena), no per-launch event recording, and a quantised batch cap
-    const bool graphable = e->graphs_ok && d.sim_base == 0 && !(e->net && az_net_profiling(e->net));
+    const bool graphable = e->graphs_ok && d.sim_base == 0 && !(e->net && az_net_profiling(e->net)) && e->cfg.evaluator != AZ_EVAL_EXTERNAL;
     // the quantised cap of the graph path also when the search runs as plain launches under az_net_profile: the profiled step then
     // launches the kernels the timed (graph-replayed) steps launch (an exact cap of 4095 -- one game of 4096 over, as happens from
     // ply ~11 on: Othello has early wipe-outs -- would hand the trunk to the one-board-per-wave kernel for the rest of the wave)
@@ -1262,6 +1342,13 @@ static int enter(az_engine *e) {
     return AZ_OK;
 }
 
+// set_roots / run reset every slot: the trees hold no unevaluated leaf any more
+static int reset_external(az_engine *e) {
+    e->unevaluated = false;
+    if (e->ext_bad) AZ_HIP(hipMemsetAsync(e->ext_bad, 0x7f, sizeof(int), e->stream));
+    return AZ_OK;
+}
+
 static int fetch_counters(az_engine *e) {
     AZ_HIP(hipMemcpyAsync(e->h_ctr, e->d.ctr, sizeof(unsigned long long) * CTR_COUNT, hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipMemcpyAsync(&e->h_err[0], e->d.err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -1273,6 +1360,13 @@ static int fetch_counters(az_engine *e) {
 
 static int check_err(az_engine *e) {
     int f = e->h_err[0];
+    if (f & ERR_EVAL) {  // first: the rejected rows were consumed by the step that followed
+        e->unevaluated = true;
+        int slot = -1;
+        AZ_HIP(hipMemcpy(&slot, e->ext_bad, sizeof(int), hipMemcpyDeviceToHost));
+        az_set_error("external evaluator: a prior that is negative or not finite, or a value that is not finite, for slot %d", slot);
+        return AZ_EINVAL;
+    }
     if (f & ERR_NODE_POOL) { az_set_error("tree node pool exhausted (node_capacity=%d)", e->cfg.node_capacity); return AZ_ECAPACITY; }
     if (f & ERR_SAMPLE_CAP) { az_set_error("sample buffer exhausted (sample_capacity=%lld)", (long long)e->cfg.sample_capacity); return AZ_ECAPACITY; }
     if (f & ERR_PLY_CAP) { az_set_error("game longer than max_plies=%d", e->cfg.max_plies); return AZ_ECAPACITY; }
@@ -1284,8 +1378,10 @@ static int check_err(az_engine *e) {
 extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_games) {
     AZ_REQUIRE(e && n_games > 0, AZ_EINVAL, "bad arguments");
     AZ_NO_OPEN_SEARCH(e, "az_engine_run");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_run");
     AZ_TRY(enter(e));
     EngDev &d = e->d;
+    AZ_TRY(reset_external(e));
     e->lockstep_iters = 0;
     hipLaunchKernelGGL(k_reset_all, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, (u32)first_game_id, (int)n_games);
     long long max_iters = ((long long)n_games / d.G + 2) * (long long)d.max_plies + 8;
@@ -1309,6 +1405,7 @@ extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_gam
 
 extern "C" int az_engine_get_stats(az_engine *e, az_engine_stats *out) {
     AZ_REQUIRE(e && out, AZ_EINVAL, "null argument");
+    AZ_USABLE(e, "az_engine_get_stats");
     AZ_TRY(enter(e));
     AZ_TRY(fetch_counters(e));
     out->games_done = (int64_t)e->h_ctr[CTR_GAMES_DONE];
@@ -1329,6 +1426,7 @@ extern "C" int az_engine_samples(az_engine *e, int64_t *n_samples, const int8_t 
                                  const int8_t **d_zs, const int32_t **d_meta, const int32_t **d_visits) {
     AZ_REQUIRE(e && n_samples, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_samples");
+    AZ_USABLE(e, "az_engine_samples");
     AZ_TRY(fetch_counters(e));
     long long s = (long long)e->h_ctr[CTR_SAMPLES];
     *n_samples = s < e->cfg.sample_capacity ? s : e->cfg.sample_capacity;
@@ -1344,10 +1442,12 @@ extern "C" int az_engine_set_roots(az_engine *e, const int8_t *h_grids, const in
                                    const int32_t *h_plies, int32_t n_roots) {
     AZ_REQUIRE(e && h_grids && h_players, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_set_roots");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_roots");
     e->sim_base = 0;
     EngDev &d = e->d;
     AZ_REQUIRE(n_roots > 0 && n_roots <= d.G, AZ_EINVAL, "n_roots must be in [1, n_slots]");
     AZ_TRY(enter(e));
+    AZ_TRY(reset_external(e));
     e->active_bound = n_roots;
     hipLaunchKernelGGL(k_reset_all, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, 0u, (int)n_roots);
     std::vector<u64> p1(n_roots), m1(n_roots);
@@ -1379,6 +1479,7 @@ extern "C" int az_engine_set_roots(az_engine *e, const int8_t *h_grids, const in
 extern "C" int az_engine_search(az_engine *e, int32_t n_sim) {
     AZ_REQUIRE(e && n_sim > 0, AZ_EINVAL, "bad arguments");
     AZ_NO_OPEN_SEARCH(e, "az_engine_search");
+    AZ_USABLE(e, "az_engine_search");
     AZ_TRY(enter(e));
     AZ_TRY(do_search(e, n_sim));
     AZ_TRY(fetch_counters(e));
@@ -1391,6 +1492,7 @@ extern "C" int az_engine_search(az_engine *e, int32_t n_sim) {
 extern "C" int az_engine_search_begin(az_engine *e, int32_t n_sim) {
     AZ_REQUIRE(e && n_sim > 0, AZ_EINVAL, "bad arguments");
     AZ_REQUIRE(!e->search_open, AZ_ESTATE, "az_engine_search_begin: the previous search has not been ended");
+    AZ_USABLE(e, "az_engine_search_begin");
     AZ_TRY(enter(e));
     AZ_TRY(do_search(e, n_sim));
     e->search_open = true;
@@ -1400,6 +1502,7 @@ extern "C" int az_engine_search_begin(az_engine *e, int32_t n_sim) {
 extern "C" int az_engine_search_end(az_engine *e) {
     AZ_REQUIRE(e, AZ_EINVAL, "null argument");
     AZ_REQUIRE(e->search_open, AZ_ESTATE, "az_engine_search_end without az_engine_search_begin");
+    AZ_USABLE(e, "az_engine_search_end");
     e->search_open = false;
     AZ_TRY(fetch_counters(e));
     return check_err(e);
@@ -1412,6 +1515,8 @@ extern "C" int az_engine_search_end(az_engine *e) {
 // new stream of the highest priority.  Call before b's first search.
 extern "C" int az_engine_pair(az_engine *a, az_engine *b) {
     AZ_REQUIRE(a && b && a != b, AZ_EINVAL, "two different engines are needed");
+    AZ_USABLE(a, "az_engine_pair");
+    AZ_USABLE(b, "az_engine_pair");
     AZ_REQUIRE(!a->search_open && !b->search_open, AZ_ESTATE, "az_engine_pair: a search is open");
     AZ_REQUIRE(b->graphs.empty(), AZ_ESTATE, "az_engine_pair must come before the second engine's searches");
     int least = 0, greatest = 0;  // numerically lower = higher priority
@@ -1428,6 +1533,7 @@ extern "C" int az_engine_pair(az_engine *a, az_engine *b) {
 extern "C" int az_engine_advance(az_engine *e) {
     AZ_REQUIRE(e, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_advance");
+    AZ_USABLE(e, "az_engine_advance");
     e->sim_base = 0;
     EngDev &d = e->d;
     // games that end here must not be refilled: cap the queue at what has been started
@@ -1441,6 +1547,7 @@ extern "C" int az_engine_root_children(az_engine *e, int32_t slot, int32_t *h_ac
                                        double *h_P, int32_t *count, int32_t *root_N) {
     AZ_REQUIRE(e && count, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_root_children");
+    AZ_USABLE(e, "az_engine_root_children");
     EngDev &d = e->d;
     AZ_REQUIRE(slot >= 0 && slot < d.G, AZ_EINVAL, "slot out of range");
     AZ_HIP(hipStreamSynchronize(e->stream));
@@ -1471,6 +1578,7 @@ extern "C" int az_engine_root_children(az_engine *e, int32_t slot, int32_t *h_ac
 extern "C" int az_engine_nodes_used(az_engine *e, int32_t slot, int32_t *n_nodes) {
     AZ_REQUIRE(e && n_nodes, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_nodes_used");
+    AZ_USABLE(e, "az_engine_nodes_used");
     AZ_REQUIRE(slot >= 0 && slot < e->d.G, AZ_EINVAL, "slot out of range");
     AZ_HIP(hipStreamSynchronize(e->stream));
     AZ_HIP(hipMemcpy(n_nodes, e->d.n_nodes + slot, sizeof(int), hipMemcpyDeviceToHost));
@@ -1482,6 +1590,7 @@ extern "C" int az_engine_nodes_used(az_engine *e, int32_t slot, int32_t *n_nodes
 extern "C" int az_engine_grow_pools(az_engine *e, int32_t node_capacity) {
     AZ_REQUIRE(e, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_grow_pools");
+    AZ_USABLE(e, "az_engine_grow_pools");
     EngDev &d = e->d;
     AZ_REQUIRE(node_capacity >= d.C, AZ_EINVAL, "pools can only grow (%d < %d)", node_capacity, d.C);
     if (node_capacity == d.C) return AZ_OK;
@@ -1510,6 +1619,7 @@ extern "C" int az_engine_grow_pools(az_engine *e, int32_t node_capacity) {
 extern "C" int az_engine_play(az_engine *e, const int32_t *h_actions, int32_t n, int32_t *h_status) {
     AZ_REQUIRE(e && h_actions && h_status, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_play");
+    AZ_USABLE(e, "az_engine_play");
     e->sim_base = 0;
     EngDev &d = e->d;
     AZ_REQUIRE(n > 0 && n <= d.G, AZ_EINVAL, "n must be in [1, n_slots]");
@@ -1536,6 +1646,7 @@ extern "C" int az_debug_read_step_probe(unsigned long long *h_out, int n_words) 
 extern "C" int az_engine_set_sides(az_engine *e, const int8_t *h_sides, int32_t n) {
     AZ_REQUIRE(e && h_sides && n > 0 && n <= e->d.G, AZ_EINVAL, "bad arguments");
     AZ_NO_OPEN_SEARCH(e, "az_engine_set_sides");
+    AZ_USABLE(e, "az_engine_set_sides");
     AZ_HIP(hipMemcpyAsync(e->d.side, h_sides, (size_t)n, hipMemcpyHostToDevice, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
     return AZ_OK;
@@ -1554,18 +1665,21 @@ static int moves_out(az_engine *e, int32_t *h_actions, int which, int kind, uint
 extern "C" int az_engine_best_moves(az_engine *e, int32_t *h_actions) {
     AZ_REQUIRE(e && h_actions, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_best_moves");
+    AZ_USABLE(e, "az_engine_best_moves");
     return moves_out(e, h_actions, 0, 0, 0);
 }
 
 extern "C" int az_engine_baseline_moves(az_engine *e, int32_t kind, uint32_t seed, int32_t *h_actions) {
     AZ_REQUIRE(e && h_actions && (kind == 0 || kind == 1), AZ_EINVAL, "bad arguments (kind: 0 random, 1 greedy)");
     AZ_NO_OPEN_SEARCH(e, "az_engine_baseline_moves");
+    AZ_USABLE(e, "az_engine_baseline_moves");
     return moves_out(e, h_actions, 1, kind, seed);
 }
 
 extern "C" int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h_over, int8_t *h_winner, int32_t *h_score) {
     AZ_REQUIRE(e && h_players && h_over && h_winner && h_score, AZ_EINVAL, "null argument");
     AZ_NO_OPEN_SEARCH(e, "az_engine_root_status");
+    AZ_USABLE(e, "az_engine_root_status");
     EngDev &d = e->d;
     char *buf = e->scr_c;
     size_t G = d.G;
@@ -1577,5 +1691,16 @@ extern "C" int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h
     AZ_HIP(hipMemcpyAsync(h_winner, wi, G, hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipMemcpyAsync(h_score, sc, G * sizeof(int), hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
+    return AZ_OK;
+}
+
+// ---- external evaluator (AZ_EVAL_EXTERNAL) ----------------------------------------------------------------
+extern "C" int az_engine_set_evaluator(az_engine *e, az_eval_fn fn, void *user) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null argument");
+    AZ_REQUIRE(e->cfg.evaluator == AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_evaluator: the engine was created with evaluator %d, not AZ_EVAL_EXTERNAL", e->cfg.evaluator);
+    AZ_REQUIRE(!e->search_open, AZ_EINVAL, "az_engine_set_evaluator: a search begun with az_engine_search_begin has not been ended");
+    AZ_USABLE(e, "az_engine_set_evaluator");
+    e->ext_fn = fn;
+    e->ext_user = user;
     return AZ_OK;
 }

@@ -2755,7 +2755,7 @@ extern "C" int az_net_create(int game, int H, int W, int max_batch, az_net **out
         // and 8x8 -- Connect4Net on the board sizes the engine plays (connect4.py:343-368) -- runs the one-board-per-wave kernel in the
         // direct form at any batch size.  Planes below 5x5 leave conv4 without an output (the reference's forward fails there too).
         bool ok = n->CH >= 5 && n->CH <= 8 && n->CW >= 5 && n->CW <= 8;
-        if (!ok) { delete n; az_set_error("no conv-trunk kernel instantiated for a %dx%d plane", n->CH, n->CW); return AZ_EINVAL; }
+        if (!ok) { az_set_error("no conv-trunk kernel instantiated for a %dx%d plane", n->CH, n->CW); delete n; return AZ_EINVAL; }
         int rc = AZ_OK;
         float *p;
 #define NA(field, cnt) if (rc == AZ_OK) { rc = net_alloc(n, &p, (cnt)); field = p; }

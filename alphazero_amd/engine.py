@@ -3,13 +3,14 @@
 torch is used for device memory and streams only; all computation is in libaz_amd.so.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (EVAL_FAKE, EVAL_NET, EVAL_ROLLOUT, GAME_IDS, NOISE_HASH, NOISE_OFF, NOISE_PHILOX, TIE_LOWEST, TIE_RANDOM,  # noqa: F401
-                   EngineCfg, EngineStats, check, lib)
+from ._lib import (EVAL_EXTERNAL, EVAL_FAKE, EVAL_NET, EVAL_ROLLOUT, GAME_IDS, NOISE_HASH, NOISE_OFF, NOISE_PHILOX, TIE_LOWEST,  # noqa: F401
+                   TIE_RANDOM, EngineCfg, EngineStats, AzError, check, lib)
 
 
 def _stream_ptr():
@@ -201,6 +202,16 @@ PROFILE_SLOTS = ["k_trunk2", "k_gemm fc1", "k_gemm fc2", "k_heads", "k_trunk", "
 
 
 # ---------------------------------------------------------------------------------------------- engine
+class ExternalBatch:
+    """what an EVAL_EXTERNAL engine hands its evaluator per root-prior pass / lock-step: zero-copy views of the engine's own
+    buffers, valid during the call only.  Rows [0, count[0]) are pending; `cap` bounds them (rows beyond are scratch).
+      x       float32 [cap, H, W]  player * grid (PolicyValueNetwork.evaluate's input, base.py:363)
+      grids   int8    [cap, H, W]  Board.grid       players int8 [cap]  Board.player       slots int32 [cap]  engine slot
+      probs   float32 [cap, A]     out: what predict() returns (exp(log_softmax)); the engine renormalises over the legal moves
+      value   float32 [cap]        out: predict()'s value, side-to-move frame (evaluate()'s v times Board.player)"""
+    __slots__ = ("cap", "H", "W", "A", "game_id", "count", "x", "grids", "players", "slots", "probs", "value")
+
+
 class SelfPlayEngine:
     """n_slots concurrent self-play games in lock-step on one GPU (AlphaZeroTrainer.self_play, trainer.py:215-273)."""
 
@@ -227,10 +238,70 @@ class SelfPlayEngine:
         h = C.c_void_p()
         check(lib().az_engine_create(C.byref(self.cfg), net.h if net is not None else None, _stream_ptr(), C.byref(h)))
         self.h = h
+        self._eval_cb = None     # the ctypes trampoline of set_evaluator: alive as long as the engine
+        self._eval_exc = None    # an exception the evaluator raised, re-raised by the engine call that ran it
+        self._eval_views = {}    # device pointer -> full-size view (the rows are sliced per call)
+        self._eval_streams = {}
+
+    # ---------------------------------------------------------------------------------------- external evaluator
+    def set_evaluator(self, fn):
+        """EVAL_EXTERNAL engines: fn(batch) evaluates the pending rows of every root-prior pass and lock-step (an ExternalBatch),
+        inside torch.cuda.stream(the engine's stream).  An exception raised by fn fails the engine call that ran it and is
+        re-raised from there unchanged (chained with the engine's message); the trees then need set_roots / run."""
+        if self.cfg.evaluator != EVAL_EXTERNAL:
+            raise ValueError(f"set_evaluator needs an engine created with evaluator=EVAL_EXTERNAL (this one: {self.cfg.evaluator})")
+
+        engine = weakref.ref(self)  # the engine holds the trampoline, not the other way round
+
+        def trampoline(user, batch, stream):
+            eng = engine()
+            try:
+                views = eng._batch_views(batch.contents, stream)
+                with torch.cuda.stream(eng._eval_streams[stream]):
+                    fn(views)
+                return 0
+            except BaseException as exc:  # ctypes would print and drop it: keep it for the engine call
+                eng._eval_exc = exc
+                return 1
+        cb = _lib.EVAL_FN(trampoline)
+        check(lib().az_engine_set_evaluator(self.h, cb, None))
+        self._eval_cb = cb
+
+    def _view(self, ptr, shape, dtype):
+        key = (ptr, dtype)
+        v = self._eval_views.get(key)
+        if v is None:
+            v = self._eval_views[key] = _wrap(ptr, shape, dtype, None)  # the engine owns the memory and these views
+        return v
+
+    def _batch_views(self, b, stream):
+        G, H, W, A = self.cfg.n_slots, b.H, b.W, b.A
+        out = ExternalBatch()
+        out.cap, out.H, out.W, out.A, out.game_id = b.cap, H, W, A, self.cfg.game
+        out.count = self._view(b.d_count, (1,), torch.int32)
+        out.x = self._view(b.d_input, (G, H, W), torch.float32)[: b.cap]
+        out.grids = self._view(b.d_grids, (G, H, W), torch.int8)[: b.cap]
+        out.players = self._view(b.d_players, (G,), torch.int8)[: b.cap]
+        out.slots = self._view(b.d_slots, (G,), torch.int32)[: b.cap]
+        out.probs = self._view(b.d_probs, (G, A), torch.float32)[: b.cap]
+        out.value = self._view(b.d_value, (G,), torch.float32)[: b.cap]
+        if stream not in self._eval_streams:
+            self._eval_streams[stream] = torch.cuda.ExternalStream(stream)
+        return out
+
+    def _evaluated(self, rc):
+        """check() for the calls that may run the evaluator: its own exception first, chained with the engine's message"""
+        exc, self._eval_exc = self._eval_exc, None
+        if exc is not None and rc != 0:
+            try:
+                check(rc)
+            except AzError as err:
+                raise exc from err
+        check(rc)
 
     def run(self, n_games, first_game_id=0):
         """plays n_games to completion; returns the samples as a dict of CUDA tensors (copies)."""
-        check(lib().az_engine_run(self.h, first_game_id, n_games))
+        self._evaluated(lib().az_engine_run(self.h, first_game_id, n_games))
         return self.samples()
 
     def samples(self, copy=True):
@@ -259,11 +330,11 @@ class SelfPlayEngine:
                                         pl.ctypes.data if pl is not None else None, len(p)))
 
     def search(self, n_sim):
-        check(lib().az_engine_search(self.h, n_sim))
+        self._evaluated(lib().az_engine_search(self.h, n_sim))
 
     def search_begin(self, n_sim):
         """queues the search and returns; search_end() waits for it (another engine may search in between: the arena's two players)"""
-        check(lib().az_engine_search_begin(self.h, n_sim))
+        self._evaluated(lib().az_engine_search_begin(self.h, n_sim))
 
     def pair_with(self, other):
         """puts `other`'s stream on a hardware queue of its own so that overlapped searches of the two engines run side by side"""

@@ -3,7 +3,9 @@
 The tree lives on the GPU -- one slot of the HIP self-play engine (csrc/az_engine.hip): `search` runs the
 simulations there, `change_root` re-roots / compacts the device tree.
 
-* eval_method "neural": PUCT with the policy/value network (lock-step k_step + network forward).
+* eval_method "neural": PUCT with the policy/value network (lock-step k_step + network forward).  A shipped network runs as the
+  HIP network; any other PolicyValueNetwork, or any object with evaluate(board), evaluates the engine's leaves through an external
+  evaluator (alphazero_amd.evaluators decides which).
 * eval_method "rollout": plain UCT with random playouts (BASELINE config 1), k_rollout_step -- one launch per
   simulation, no network.
 
@@ -52,8 +54,11 @@ class MCT:
         self._engine = None           # device tree (one engine slot)
         self._engine_board = None     # (game, H, W) the engine was built for
         self._hipnet = None
+        self._evaluator = None        # external evaluator of a network the HIP net does not serve (evaluators.route)
         self._root_key = None         # (grid bytes, player) of the position the device root stands for
         self._last_board = None
+        self._tie_mode = None         # tests: engine.TIE_LOWEST (None: fair_max draws among equals, utils.py:28-34)
+        self._noise_mode = None       # tests: engine.NOISE_HASH (None: Dirichlet noise from the Philox stream)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -66,6 +71,7 @@ class MCT:
             raise ValueError(f"Trying to set a neural network for the MCT but the evaluation method is {self.eval_method}")
         self._nn = nn
         self._hipnet = None
+        self._evaluator = None
         self._engine = None
         self._root_key = None
 
@@ -80,13 +86,13 @@ class MCT:
         self._sync_device_root(board, n_sim)
         if n_sim is not None:
             self._ensure_room(n_sim)
-            self._engine.search(n_sim)
+            self._device_search(n_sim)
             self.n_rollouts = n_sim
         else:
             chunk = 1 if self.eval_method == TreeEval.NEURAL else 8
             while time() - start < compute_time:
                 self._ensure_room(chunk)
-                self._engine.search(chunk)
+                self._device_search(chunk)
                 self.n_rollouts += chunk
         self.simulation_time = time() - start
 
@@ -118,16 +124,30 @@ class MCT:
         self._root_key = (b.grid.astype(np.int8).tobytes(), int(b.player))
 
     # ------------------------------------------------------------------ device tree
+    def _device_search(self, n_sim):
+        try:
+            self._engine.search(n_sim)
+        except BaseException:
+            if self._evaluator is not None:
+                # a failed external evaluation leaves leaves in the device tree that were never evaluated (the engine then
+                # accepts set_roots / run only): the next search starts the tree afresh from the board it is given
+                self._root_key = None
+            raise
+
     def _children(self):
         if self._engine is None:
             return [], [], [], [], 0
         return self._engine.root_children(0)
 
     def _sync_device_root(self, board, n_sim=None):
-        from .engine import EVAL_NET, EVAL_ROLLOUT, NOISE_OFF, NOISE_PHILOX, TIE_RANDOM, SelfPlayEngine
+        from .engine import EVAL_EXTERNAL, EVAL_NET, EVAL_ROLLOUT, NOISE_OFF, NOISE_PHILOX, TIE_RANDOM, SelfPlayEngine
+        from .evaluators import check_game, check_normalizer, make_evaluator, route
+        check_game(board)
         neural = self.eval_method == TreeEval.NEURAL
         if neural and self._nn is None:
             raise ValueError("The MCT has no neural network to evaluate positions with.")
+        if neural:
+            check_normalizer(self._nn)
         H, W = board.grid.shape
         if self._engine is not None and self._engine_board != (board.game, H, W):
             # the device storage was carried over a reset() from a game on another board (players.py keeps the engine); the
@@ -137,17 +157,21 @@ class MCT:
             if self._hipnet is not None and (self._hipnet.H, self._hipnet.W) != (H, W):
                 self._hipnet = None
         if self._engine is None:
-            if neural and self._hipnet is None:
+            external = neural and route(self._nn) != "hip"
+            if neural and not external and self._hipnet is None:
                 self._hipnet = self._nn.to_hip(max_batch=16)
             noisy = self.dirichlet_alpha is not None and self.dirichlet_epsilon is not None
-            self._engine = SelfPlayEngine(_GAME_IDS[board.game], H, W, n_slots=1, n_sim=1, net=self._hipnet,
+            self._engine = SelfPlayEngine(_GAME_IDS[board.game], H, W, n_slots=1, n_sim=1, net=None if external else self._hipnet,
                                           dirichlet_alpha=self.dirichlet_alpha, dirichlet_epsilon=self.dirichlet_epsilon,
-                                          temp_max_step=-1, temp_min_step=0, tie_mode=TIE_RANDOM,
-                                          noise_mode=NOISE_PHILOX if noisy else NOISE_OFF,
-                                          evaluator=EVAL_NET if neural else EVAL_ROLLOUT,
+                                          temp_max_step=-1, temp_min_step=0, tie_mode=TIE_RANDOM if self._tie_mode is None else self._tie_mode,
+                                          noise_mode=(NOISE_PHILOX if noisy else NOISE_OFF) if self._noise_mode is None else self._noise_mode,
+                                          evaluator=EVAL_EXTERNAL if external else (EVAL_NET if neural else EVAL_ROLLOUT),
                                           seed=self._seed, sample_capacity=4 * H * W + 16, max_plies=4 * H * W + 16,
                                           # one slot: the pools start small and grow on demand (_ensure_room)
                                           node_capacity=1 << 14)
+            if external:
+                self._evaluator = make_evaluator(self._nn, board.game, H, W)
+                self._engine.set_evaluator(self._evaluator)
             self._engine_board = (board.game, H, W)
             self._plies = 0
         key = (board.grid.astype(np.int8).tobytes(), int(board.player))

@@ -93,6 +93,7 @@ class AlphaZeroPlayer(MCTSPlayer):
                        dirichlet_epsilon=old.dirichlet_epsilon)
         # keep the uploaded weights and the device tree storage: a reset only drops the tree
         self.mct._hipnet, self.mct._engine, self.mct._engine_board = old._hipnet, old._engine, old._engine_board
+        self.mct._evaluator = old._evaluator  # the carried engine calls it (external evaluation, evaluators.route)
         if self.mct._engine is not None:
             self.mct._plies = 0
 

@@ -18,8 +18,11 @@ def _stream():
 
 def supports(module, batch_size):
     """the hand-written step covers the conv nets at batch sizes that are multiples of 16 up to 512 and the TicTacToe MLP at any batch
-    size from 2 to 256 (the reference's defaults: 64)"""
+    size from 2 to 256 (the reference's defaults: 64), for modules that compute the shipped function (evaluators.hip_serves)"""
     if not hasattr(module, "hip_shape"):
+        return False
+    from .evaluators import hip_serves
+    if not hip_serves(module, search=False):  # a forward() of its own, or other layers: the stock step trains it
         return False
     gid, H, W = module.hip_shape()
     if gid == 2:

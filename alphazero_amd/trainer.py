@@ -136,13 +136,21 @@ class AlphaZeroTrainer:
         return game_shape(self.game, getattr(c, "board_size", None), getattr(c, "board_width", 7), getattr(c, "board_height", 6))
 
     def _ensure_engine(self):
-        from .engine import SelfPlayEngine
+        from .engine import EVAL_EXTERNAL, EVAL_NET, SelfPlayEngine
+        from .evaluators import check_normalizer, make_evaluator, route
         gid, H, W, A = self._shape()
         c = self.config
         if c.simulations is None:
             raise ValueError("the batched engine needs config.simulations (compute_time-bounded search is host-only)")
         slots = max(1, min(self.engine_slots, c.episodes))
-        if self._hipnet is None:
+        # a network the HIP net does not serve evaluates the leaves itself (external evaluator, evaluators.route)
+        external = route(self.nn) != "hip"
+        if self._engine is not None and (self._engine.cfg.evaluator == EVAL_EXTERNAL) != external:
+            self._engine.close()
+            self._engine = None
+        if external:
+            check_normalizer(self.nn)
+        elif self._hipnet is None:
             self._hipnet = self.nn.to_hip(max_batch=slots)
         else:
             self._hipnet.load_state_dict(self.nn.state_dict())
@@ -152,11 +160,25 @@ class AlphaZeroTrainer:
             else:
                 tmax, tmin = c.temp_max_step, c.temp_min_step
             plies = 2 * H * W if gid == 0 else H * W + 1
-            self._engine = SelfPlayEngine(gid, H, W, n_slots=slots, n_sim=c.simulations, net=self._hipnet,
+            self._engine = SelfPlayEngine(gid, H, W, n_slots=slots, n_sim=c.simulations, net=None if external else self._hipnet,
                                           dirichlet_alpha=c.dirichlet_alpha, dirichlet_epsilon=c.dirichlet_epsilon,
                                           temp_max_step=tmax, temp_min_step=tmin, seed=self.seed, max_plies=plies,
-                                          sample_capacity=c.episodes * plies)
+                                          sample_capacity=c.episodes * plies, evaluator=EVAL_EXTERNAL if external else EVAL_NET)
+        if external:  # a fresh evaluator for the network of this wave (update_network replaces self.nn)
+            self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
         return self._engine
+
+    def _run_engine(self, eng, n_games, first_game_id):
+        from .engine import EVAL_EXTERNAL
+        try:
+            return eng.run(n_games, first_game_id=first_game_id)
+        except BaseException:
+            if eng.cfg.evaluator == EVAL_EXTERNAL:
+                # a failed external evaluation leaves the engine refusing everything but set_roots / run, set_evaluator
+                # included: the next wave builds a fresh engine
+                eng.close()
+                self._engine = None
+            raise
 
     @staticmethod
     def _dist():
@@ -175,14 +197,14 @@ class AlphaZeroTrainer:
         n = self.config.episodes
         rank, world = self._dist()
         if world == 1:
-            smp = eng.run(n, first_game_id=iter_idx * n)
+            smp = self._run_engine(eng, n, iter_idx * n)
         else:
             # the episodes are sharded by game id (disjoint Philox streams, no collective while playing), then every
             # rank receives all samples: the same memory a single process would have built
             from .dist import all_gather_samples, shard_range
             lo, cnt, _ = shard_range(n, rank, world)
             if cnt > 0:
-                smp = eng.run(cnt, first_game_id=iter_idx * n + lo)
+                smp = self._run_engine(eng, cnt, iter_idx * n + lo)
             else:
                 smp = {"state": torch.zeros((0, H, W), dtype=torch.int8, device="cuda"), "pi": torch.zeros((0, A), device="cuda"),
                        "z": torch.zeros(0, dtype=torch.int8, device="cuda"), "meta": torch.zeros((0, 4), dtype=torch.int32, device="cuda"),

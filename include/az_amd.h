@@ -37,6 +37,7 @@ extern "C" {
 #define AZ_ESTATE (-3)   /* call order / missing weights */
 #define AZ_ECAPACITY (-4)/* node pool or sample buffer exhausted */
 #define AZ_EILLEGAL (-5) /* illegal move (reference: ValueError, othello.py:199-200) */
+#define AZ_EEVAL (-6)    /* the external evaluator (az_engine_set_evaluator) reported a failure */
 
 #define AZ_TIE_MODE_LOWEST 0  /* fair_max ties -> lowest action index (deterministic, tests) */
 #define AZ_TIE_MODE_RANDOM 1  /* fair_max ties -> uniform (utils.py:28-34), Philox stream */
@@ -46,6 +47,7 @@ extern "C" {
 #define AZ_EVAL_NET 0          /* PolicyValueNetwork.evaluate (base.py:357-367) on the HIP network */
 #define AZ_EVAL_FAKE 1         /* closed-form fake network (tests; tools/closed_form.py) */
 #define AZ_EVAL_ROLLOUT 2      /* TreeEval.ROLLOUT: plain UCT with random playouts, no network (mcts.py:38-42, 173-180) */
+#define AZ_EVAL_EXTERNAL 3     /* the caller's evaluator (az_engine_set_evaluator): PolicyValueNetwork.evaluate, base.py:357-367 */
 
 const char *az_last_error(void);
 int az_version(void);
@@ -195,6 +197,36 @@ int az_engine_search_begin(az_engine *e, int32_t n_sim);
 int az_engine_pair(az_engine *a, az_engine *b);
 int az_engine_search_end(az_engine *e);
 int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h_over, int8_t *h_winner, int32_t *h_score);
+
+/* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
+ * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
+ * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves
+ * to the caller instead of its HIP network: where AZ_EVAL_NET launches the network -- the root-prior pass and every lock-step
+ * of az_engine_search, az_engine_run and az_engine_search_begin -- it calls `fn` on the calling thread.  `stream` is the
+ * engine's own stream: what the callback queues there runs before the next step kernel.  Such a search is never captured as
+ * a HIP graph (a host callback cannot be replayed).
+ *   - the callback fills d_probs / d_value for rows [0, *d_count): probs as PolicyValueNetwork.predict returns them
+ *     (exp(log_softmax), not yet renormalised: the engine applies the shipped get_normalized_probs rule), value in the
+ *     side-to-move frame (evaluate()'s v times Board.player).  A prior that is negative or not finite, or a value that
+ *     is not finite, fails the call with AZ_EINVAL naming the lowest such slot; nothing is rescaled or clamped.
+ *   - a non-zero return fails the call with AZ_EEVAL: nothing more is queued for that search (az_engine_search_begin then
+ *     leaves no search open).  After that, or after rejected outputs, the trees hold leaves that were never evaluated:
+ *     every call except az_engine_destroy, az_engine_set_roots and az_engine_run returns AZ_ESTATE until one of those two
+ *     has reset the slots.  A call into the same engine from inside the callback returns AZ_ESTATE.
+ *   - az_engine_set_evaluator returns AZ_EINVAL on an engine that is not AZ_EVAL_EXTERNAL or while a search is open; a
+ *     search with no evaluator set returns AZ_ESTATE. */
+typedef struct {
+    int32_t cap, H, W, A;       /* cap: host-side upper bound on the rows present (the network's batch cap) */
+    const int32_t *d_count;     /* DEVICE: rows [0, *d_count) are pending leaves; rows beyond are scratch */
+    const float *d_input;       /* [cap][H*W] player*grid, float32 (base.py:363) */
+    const int8_t *d_grids;      /* [cap][H*W] Board.grid of the row's position */
+    const int8_t *d_players;    /* [cap] Board.player */
+    const int32_t *d_slots;     /* [cap] engine slot the row belongs to */
+    float *d_probs;             /* out [cap][A] */
+    float *d_value;             /* out [cap] */
+} az_eval_batch;
+typedef int (*az_eval_fn)(void *user, const az_eval_batch *batch, void *stream);
+int az_engine_set_evaluator(az_engine *e, az_eval_fn fn, void *user);
 
 /* ---- symmetry augmentation on the device ------------------------------------
  * replaces the loop of AlphaZeroTrainer.self_play (trainer.py:275-284) over Sample.create_reflection_twin /
