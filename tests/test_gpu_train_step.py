@@ -5,7 +5,10 @@
   * against golden G6 (the REFERENCE's optimize_network, tools/gen_golden.py::gen_sgd) through AlphaZeroTrainer with sgd_backend "hip";
   * dropout law, run-to-run determinism, and that the stock PyTorch loop stays selectable.
 Tolerance: float32 against float64: 2e-4 of the buffer's largest magnitude (measured: 1e-6).  A ReLU input that is zero to rounding
-may take the other branch in float64; the seeds used here have no such tie (tools/check_train_step.py prints where an error sits)."""
+may take the other branch in float64; the seeds used here have no such tie (tools/check_train_step.py prints where an error sits).
+That tolerance is at the PARAMETER's scale, which one step of weight decay moves by 0.025 of it: the update itself -- every tensor's
+gradient, weight decay, momentum, set_lr, per-step changes over three steps, the eight-step graph and the AZ_TRAIN_* switches -- is
+tested at its own scale in tests/test_gpu_train_update.py."""
 import ast
 import os
 import sys

@@ -2,7 +2,10 @@
 """The hand-written training step (csrc/az_train.hip) against torch autograd in float64 on the CPU: every activation, every
 gradient the step keeps in its workspace, the losses, and the parameters / BatchNorm statistics after k steps.
     python tools/check_train_step.py [tag] [batch] [steps] [dropout]      tag: othello8 | othello6 | connect4
-Prints one line per buffer (max abs error, scale); tests/test_gpu_train_step.py asserts on the same report."""
+Prints one line per buffer (max abs error, scale); tests/test_gpu_train_step.py asserts on the same report.
+    python tools/check_train_step.py --update-profile
+The parameter update at its own scale (gradients from one step at momentum 0 / weight decay 0, the hyper-parameters as identities of
+the step with itself): the helpers of tests/test_gpu_train_update.py, and the figures of profiles/r07_update_parity.txt."""
 import copy
 import os
 import sys
@@ -100,15 +103,22 @@ def relu_ties(keep, rel=2e-6):
     return out
 
 
-def report(tag="othello8", B=64, steps=3, dropout=0.0, verbose=True, seed=0):
-    """-> rows (buffer, max abs error, scale); report.ties = relu_ties() of every step (empty: no unit of the run sits on a ReLU kink)"""
-    from alphazero_amd.train_step import HipTrainStep
-    report.ties = []
+def problem(tag, B, steps, seed=0):
+    """-> (net, state, pi, z, perm): the network, samples and batch order of report(tag, B, steps, seed=seed)"""
     net = make_net(tag, seed)
     S = B * steps + 7
     state, pi, z = make_samples(net, S, seed=1 + 17 * seed)
     perm = torch.randperm(S, generator=torch.Generator().manual_seed(5 + seed))[: B * steps].contiguous()
-    lr, mom, wd = 0.05, 0.9, 1e-4
+    return net, state, pi, z, perm
+
+
+def report(tag="othello8", B=64, steps=3, dropout=0.0, verbose=True, seed=0, lr=0.05, mom=0.9, wd=1e-4):
+    """-> rows (buffer, max abs error, scale); report.ties = relu_ties() of every step (empty: no unit of the run sits on a ReLU kink).
+    step<s>.delta.<name> is the change step s made to a tensor of the state dict, p_s - p_(s-1), with the float64 run's largest change
+    as its scale: the update at its own scale (update_bad() judges those rows; with mom = wd = 0 a delta is -lr times the gradient)"""
+    from alphazero_amd.train_step import HipTrainStep
+    report.ties = []
+    net, state, pi, z, perm = problem(tag, B, steps, seed)
     ref = copy.deepcopy(net).double().train()
     opt = torch.optim.SGD(ref.parameters(), lr=lr, momentum=mom, weight_decay=wd)
     hip = HipTrainStep(net, max_batch=B)
@@ -138,6 +148,10 @@ def report(tag="othello8", B=64, steps=3, dropout=0.0, verbose=True, seed=0):
     gid, H, W = net.hip_shape()
     A = net.action_size
     NHP = (A + 1 + 15) // 16 * 16
+    floats = [kname for kname, v in net.state_dict().items() if v.dtype == torch.float32]
+    before = {kname: net.state_dict()[kname].detach().double().cpu().clone() for kname in floats}
+    report.pmax = {kname: float(before[kname].abs().max()) for kname in floats}  # largest magnitude a tensor had at any step: the rounding of a stored value
+    rbefore = {kname: ref.state_dict()[kname].detach().clone() for kname in floats}
     for s in range(steps):
         rws = perm[s * B:(s + 1) * B]
         # one step at a time so that the workspace of step s can be inspected: a separate perm / loss slice per call
@@ -168,9 +182,14 @@ def report(tag="othello8", B=64, steps=3, dropout=0.0, verbose=True, seed=0):
             cmp(pre + "dz2", hip.debug("dz2")[: B * F2].view(B, F2), keep["y2"].grad); cmp(pre + "dz1", hip.debug("dz1")[: B * F1].view(B, F1), keep["y1"].grad)
         cmp(f"step{s}.loss_pi", lpi[s:s + 1], torch.tensor([t_pi])); cmp(f"step{s}.loss_v", lv[s:s + 1], torch.tensor([t_v]))
         opt.step()
-    out = copy.deepcopy(net)
-    hip.store(out)
-    rsd = ref.state_dict()
+        out = copy.deepcopy(net)  # a fresh copy every time: store() adds the steps done so far to num_batches_tracked
+        hip.store(out)
+        rsd = ref.state_dict()
+        for kname in floats:
+            now, rnow = out.state_dict()[kname].detach().double().cpu(), rsd[kname].detach().clone()
+            cmp(f"step{s}.delta.{kname}", now - before[kname], rnow - rbefore[kname])
+            report.pmax[kname] = max(report.pmax[kname], float(now.abs().max()))
+            before[kname], rbefore[kname] = now, rnow
     for kname, v in out.state_dict().items():
         if v.dtype == torch.float32:
             cmp("final." + kname, v, rsd[kname])
@@ -180,8 +199,203 @@ def report(tag="othello8", B=64, steps=3, dropout=0.0, verbose=True, seed=0):
     return rows
 
 
+# ---------------------------------------------------------------------------------------------------------------- the update at its own scale
+# (tests/test_gpu_train_update.py).  No weight gradient of the step is readable: the update happens in the epilogue of the gradient tiles
+# (fc1 / fc2), in sgd() from several kernels, and in k_ttt_step.  What IS readable is the parameter before and after a step, and
+# begin()'s hyper-parameters are free: momentum 0, weight decay 0 and a power-of-two learning rate L turn one step into
+# p1 = p0 - L g, so (p0 - p1) / L is the gradient; the other hyper-parameters are checked as identities of the step with itself.
+UPDATE_CASES = ([("othello8", b) for b in (16, 64, 128, 144, 320, 512)] + [("othello6", b) for b in (48, 80, 400)] + [("connect4", b) for b in (32, 144, 512)]
+                + [("connect4_5x8", 64)] + [("tictactoe", b) for b in (2, 64, 250)])
+EPS = 2.0 ** -24  # half an ulp of a float32 relative to its magnitude: one rounding
+# One step at L = 16: the stored p1 is rounded to EPS |p1|, EPS |p| / L = 6e-9 in gradient units for the largest parameters (BatchNorm
+# weights, 1.5) -- under the float32 noise of their gradients (1e-6 of 1e-2) -- and one step at L = 16 is still a finite network.
+GRAD_L = 16.0
+# Biases that feed a BatchNorm have a true gradient of zero (the batch mean removes them); a float32 step leaves rounding there.
+# Measured on the stock float32 torch step on the CPU over UPDATE_CASES x seeds 0-2 (profiles/r07_update_parity.txt), largest value:
+# conv nets 4.17e-7, TicTacToeNet at 64 / 250 rows 4.1e-8, TicTacToeNet at 2 rows 1.05e-5 (two rows: 1 / sqrt(var + eps) of a variance
+# that may be tiny multiplies the rounding).  The allowance is 8x that: the kernels sum the same terms in another order.
+GRAD_FLOOR = {"conv": 8 * 4.17e-7, "tictactoe": 8 * 4.1e-8, "tictactoe2": 8 * 1.05e-5}
+IDENTITY_SLACK = 2.0  # over the derived rounding bounds of the identities (emulated fmaf chains reach 0.98 of them)
+
+
+def grad_floor(tag, B):
+    return GRAD_FLOOR["conv" if tag != "tictactoe" else ("tictactoe2" if B == 2 else "tictactoe")]
+
+
+def zero_gradient(name):
+    return name in ("conv1.bias", "conv2.bias", "conv3.bias", "conv4.bias", "fc1.bias", "fc2.bias")
+
+
+def update_rows(rows, lr, tag, B, pmax):
+    """the step<s>.delta.<name> rows of report() against their allowance -> [(row name, error / allowance)].  Allowance: 2e-4 of the
+    float64 run's largest change of that tensor (the project's float32-against-float64 figure, at the change's own scale) plus, for the
+    zero-gradient biases, lr x grad_floor; for every other tensor only the rounding of the two stored values the change is the
+    difference of (2 EPS max|p|, never more than lr x grad_floor)"""
+    out = []
+    for n, e, s in rows:
+        if ".delta." in n:
+            k = n.split(".delta.")[1]
+            fl = lr * grad_floor(tag, B)
+            out.append((n, e / (2e-4 * s + (fl if zero_gradient(k) else min(fl, 2 * EPS * pmax[k])))))
+    return out
+
+
+def gradient_check(tag, B, seed=0, L=GRAD_L):
+    """one step at momentum 0, weight decay 0, dropout 0, learning rate L against float64 autograd: every tensor's gradient
+    (p0 - p1) / L through update_rows(), and the step's workspace, losses and counters under report()'s own rule (a kernel that reads a
+    weight another kernel of the same step has already updated shows there, magnified by L; the final.* rows of the float tensors are
+    the delta rows again at the parameter's scale, where L x the zero-gradient floor does not belong)"""
+    rows = report(tag, B, 1, 0.0, verbose=False, seed=seed, lr=L, mom=0.0, wd=0.0)
+    ratios = update_rows(rows, L, tag, B, report.pmax)
+    assert len(ratios) == len(report.pmax)
+    g = {n.split(".delta.")[1]: (e / L, s / L) for n, e, s in rows if ".delta." in n and "running_" not in n}
+    return {"ratio": max(r for _, r in ratios), "bad": [(n, r) for n, r in ratios if not r <= 1.0][:6],
+            "workspace_bad": [(n, e, s) for n, e, s in rows if ".delta." not in n and not (n.startswith("final.") and not n.endswith("num_batches_tracked")) and not e <= 2e-4 * max(s, 1e-3) + 1e-6][:6], "ties": report.ties[:4],
+            "rel": max(e / s for k, (e, s) in g.items() if not zero_gradient(k)), "zero": max([e for k, (e, s) in g.items() if zero_gradient(k)] or [0.0])}
+
+
+def stock_float32_noise(tag, B, seed=0):
+    """the same gradient figures ("rel", "zero") for the stock float32 torch step on the CPU against float64: the reference's own error"""
+    net, state, pi, z, perm = problem(tag, B, 1, seed)
+    g = {}
+    for dt in (torch.float64, torch.float32):
+        m = copy.deepcopy(net).to(dt).train()
+        torch_step(m, state[perm].to(dt), pi[perm].to(dt), z[perm].to(dt).unsqueeze(1), B)
+        g[dt] = {k: p.grad.double() for k, p in m.named_parameters()}
+    err = {k: (float((g[torch.float32][k] - v).abs().max()), float(v.abs().max())) for k, v in g[torch.float64].items()}
+    return {"rel": max(e / s for k, (e, s) in err.items() if not zero_gradient(k)), "zero": max(e for k, (e, s) in err.items() if zero_gradient(k))}
+
+
+class UpdateRun:
+    """one trainer on problem(tag, B, steps, seed): begin() reloads the initial weights, step(s, n) runs steps s .. s+n-1 in ONE call
+    (its permutation / loss pointers are those of step s: the same s gives the same pointers, so a captured graph is replayed),
+    snap() reads the state dict back (float64 copies on the CPU; exact, every float32 is a float64)"""
+
+    def __init__(self, tag, B, steps, seed=0):
+        from alphazero_amd.train_step import HipTrainStep
+        self.net, state, pi, z, perm = problem(tag, B, steps, seed)
+        self.B = B
+        self.hip = HipTrainStep(self.net, max_batch=B)
+        self.net.cuda()
+        self.state, self.pi, self.z, self.perm = state.cuda(), pi.cuda(), z.cuda(), perm.cuda()
+        self.lp, self.lv = torch.zeros(steps, device="cuda"), torch.zeros(steps, device="cuda")
+        self.p0 = {k: v.detach().double().cpu() for k, v in self.net.state_dict().items() if v.dtype == torch.float32}
+
+    def begin(self, lr, mom, wd, dropout=0.0):
+        self.hip.load(self.net)
+        self.hip.begin(lr, mom, wd, dropout, seed=3)
+
+    def step(self, s, n=1):
+        self.hip.steps(self.state, self.pi, self.z, self.perm[s * self.B:], n, self.B, self.lp[s:], self.lv[s:])
+
+    def stored(self):
+        out = copy.deepcopy(self.net)  # fresh every time: store() adds the steps done to num_batches_tracked
+        self.hip.store(out)
+        return out.state_dict()
+
+    def snap(self):
+        return {k: v.detach().double().cpu() for k, v in self.stored().items() if v.dtype == torch.float32}
+
+    def close(self):
+        self.hip.close()
+
+
+def identity_check(tag, B, seed=0, L=1.0, w=0.5, mu=0.5):
+    """weight decay, momentum and learning rate as identities of the step with itself, on every tensor; no reference and no measured
+    tolerance.  The step is bit-reproducible, and the hyper-parameters enter only through
+        gg = fmaf(wd, p, g);  mm = fmaf(momentum, m, gg);  m = mm;  p = fmaf(-lr, mm, p)
+    (sgd(), the epilogues of fc_wgrad_tile / fc_wgrad_tile_ks, k_ttt_step), each rounding once, by at most EPS of its result.
+    -> worst observed / (IDENTITY_SLACK x bound) per identity ("wd", "mom", "lr": must be <= 1), "exact": every bit-equality held"""
+    r = UpdateRun(tag, B, 2, seed)
+    par = [k for k, _ in r.net.named_parameters()]
+    stats = [k for k in r.p0 if k not in par]
+    p0, res, exact = r.p0, {}, True
+
+    def worst(diff, bound):
+        return float((diff.abs() / (IDENTITY_SLACK * bound).clamp_min(1e-300)).max())
+    # weight decay: gg(0) = g exactly and mm = gg at momentum 0, so p1(0) = rnd(p0 - L g), p1(w) = rnd(p0 - L rnd(g + w p0)):
+    # p1(w) - p1(0) = -L w p0 within EPS (L |gg| + |p1(0)| + |p1(w)|), L |gg| read off the run as |p1(w) - p0|
+    r.begin(L, 0.0, 0.0); r.step(0); a = r.snap()
+    r.begin(L, 0.0, w); r.step(0); b = r.snap()
+    res["wd"] = max(worst((b[k] - a[k]) + L * w * p0[k], EPS * ((b[k] - p0[k]).abs() + a[k].abs() + b[k].abs())) for k in par)
+    exact &= all(torch.equal(a[k], b[k]) for k in stats)
+    # momentum: the buffers start at zero (begin() clears what the runs above left), so step 1 is the same bits at any momentum;
+    # step 2 then sees the same weights and batch, hence the same g2, and mm2 = rnd(mu gg1 + gg2) against gg2:
+    # p2(mu) - p2(0) = -L mu gg1 = mu (p1 - p0) within EPS (L |mm2| + |p2(0)| + |p2(mu)| + |p1|), L |mm2| read off as |p2(mu) - p1|
+    r.begin(L, 0.0, 0.0); r.step(0); a1 = r.snap(); r.step(1); a2 = r.snap()
+    r.begin(L, mu, 0.0); r.step(0); b1 = r.snap(); r.step(1); b2 = r.snap()
+    exact &= all(torch.equal(a1[k], b1[k]) for k in a1) and all(torch.equal(a2[k], b2[k]) for k in stats)
+    res["mom"] = max(worst((b2[k] - a2[k]) - mu * (a1[k] - p0[k]), EPS * ((b2[k] - a1[k]).abs() + a2[k].abs() + b2[k].abs() + a1[k].abs())) for k in par)
+    # learning rate: two steps in one call (a plain step, then the captured one-step graph), then a third call on the same pointers,
+    # which replays that graph -- once as it is, once after set_lr(2 lr).  mm3 does not depend on lr, so the third step's change
+    # doubles: (p3' - p2) = 2 (p3 - p2) within the rounding of the two stored values, EPS (|p3'| + 2 |p3|)
+    lr = L / 8
+    r.begin(lr, mu, 1e-4); r.step(0, 2); c2 = r.snap(); r.step(0); c3 = r.snap()
+    r.begin(lr, mu, 1e-4); r.step(0, 2); d2 = r.snap(); r.hip.set_lr(2 * lr); r.step(0); d3 = r.snap()
+    exact &= all(torch.equal(c2[k], d2[k]) for k in c2) and all(torch.equal(c3[k], d3[k]) for k in stats)
+    res["lr"] = max(worst((d3[k] - c2[k]) - 2 * (c3[k] - c2[k]), EPS * (d3[k].abs() + 2 * c3[k].abs())) for k in par)
+    res["moved"] = min(float((c3[k] - c2[k]).abs().max()) for k in par) > 0.0  # every tensor took part
+    res["exact"] = bool(exact)
+    r.close()
+    return res
+
+
+def many_steps(tag, B, n=11, dropout=0.3, one_call=True, seed=0):
+    """n steps at the reference's hyper-parameters in one steps() call (a plain step, graphs of AZ_TRAIN_GRAPH_STEPS steps, one-step
+    replays) or as n calls of one step -> {name: numpy array} of the losses and the whole state dict"""
+    r = UpdateRun(tag, B, n, seed)
+    r.begin(0.1, 0.9, 1e-4, dropout)
+    if one_call:
+        r.step(0, n)
+    else:
+        for s in range(n):
+            r.step(s)
+    out = {k: v.detach().cpu().numpy() for k, v in r.stored().items()}
+    out["loss_pi"], out["loss_v"] = r.lp.cpu().numpy(), r.lv.cpu().numpy()
+    r.close()
+    return out
+
+
+MANY_STEPS_CASES = [("othello8", 64, 0.3), ("othello8", 512, 0.3), ("tictactoe", 64, 0.0)]  # (TicTacToeNet has no dropout)
+
+
+def update_child(spec):
+    """a child process of tests/test_gpu_train_update.py (the AZ_TRAIN_* switches are read once per process): gradient_check and
+    identity_check on spec["cases"] ([tag, batch, seed]), many_steps on MANY_STEPS_CASES into spec["npz"] if given -> one JSON-able dict"""
+    out = {"cases": {}}
+    for tag, B, seed in spec.get("cases", []):
+        out["cases"][f"{tag}/{B}/{seed}"] = {"grad": gradient_check(tag, B, seed), "identity": identity_check(tag, B, seed)}
+    if spec.get("npz"):
+        res = {}
+        for tag, B, p in MANY_STEPS_CASES:
+            res.update({f"{tag}/{B}/{k}": v for k, v in many_steps(tag, B, 11, p, True).items()})
+        np.savez(spec["npz"], **res)
+    return out
+
+
+def update_profile():
+    """the figures of profiles/r07_update_parity.txt, one line per (case, seed)"""
+    print(f"L = {GRAD_L}; floors {GRAD_FLOOR}; identity slack {IDENTITY_SLACK}")
+    print("case seed | HIP step: worst err / max|g_ref| over real-gradient tensors, largest zero-gradient bias | stock float32 torch (CPU): the same two | allowance used | ReLU ties")
+    for tag, B in UPDATE_CASES:
+        for seed in (0, 1, 2):
+            g, f = gradient_check(tag, B, seed), stock_float32_noise(tag, B, seed)
+            print(f"{tag:13s}{B:4d} {seed} | {g['rel']:9.2e} {g['zero']:9.2e} | {f['rel']:9.2e} {f['zero']:9.2e} | {g['ratio']:8.2e} | {g['ties']}", flush=True)
+    print("case | identities, worst observed / derived bound: weight decay, momentum, learning rate | bit-equalities")
+    for tag, B in UPDATE_CASES:
+        i = identity_check(tag, B, 0)
+        print(f"{tag:13s}{B:4d} | {i['wd'] * IDENTITY_SLACK:6.3f} {i['mom'] * IDENTITY_SLACK:6.3f} {i['lr'] * IDENTITY_SLACK:6.3f} | {i['exact']}", flush=True)
+
+
 if __name__ == "__main__":
     a = sys.argv[1:]
+    if a and a[0] == "--update-child":
+        import json
+        print(json.dumps(update_child(json.loads(a[1]))))
+        sys.exit(0)
+    if a and a[0] == "--update-profile":
+        update_profile()
+        sys.exit(0)
     rows = report(a[0] if a else "othello8", int(a[1]) if len(a) > 1 else 64, int(a[2]) if len(a) > 2 else 3, float(a[3]) if len(a) > 3 else 0.0)
     bad = [(n, e, s) for n, e, s in rows if e > 2e-4 * max(s, 1e-3) + 1e-6]
     print("WORST", sorted(rows, key=lambda r: -r[1] / max(r[2], 1e-3))[:5])
