@@ -42,6 +42,12 @@ class EvalBatch(C.Structure):
                 ("d_probs", C.c_void_p), ("d_value", C.c_void_p)]
 
 
+class RootReadout(C.Structure):
+    """az_root_readout: the device buffers az_engine_root_readout fills (None = not wanted)"""
+    _fields_ = [("d_visits", C.c_void_p), ("d_pi", C.c_void_p), ("d_Q", C.c_void_p), ("d_P", C.c_void_p), ("d_child", C.c_void_p),
+                ("d_action", C.c_void_p), ("d_root_N", C.c_void_p), ("d_pv", C.c_void_p), ("pv_len", C.c_int32)]
+
+
 # az_eval_fn: int (*)(void *user, const az_eval_batch *batch, void *stream)
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(EvalBatch), C.c_void_p)
 
@@ -53,7 +59,7 @@ SYMBOLS = [
     "az_net_action_size",
     "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
     "az_engine_get_stats", "az_engine_samples", "az_engine_set_roots", "az_engine_search", "az_engine_search_begin", "az_engine_search_end", "az_engine_pair", "az_engine_advance",
-    "az_engine_root_children", "az_engine_nodes_used", "az_engine_grow_pools", "az_engine_play", "az_augment_count", "az_augment",
+    "az_engine_root_children", "az_engine_root_readout", "az_engine_nodes_used", "az_engine_grow_pools", "az_engine_play", "az_augment_count", "az_augment",
     "az_engine_set_sides", "az_engine_best_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
     "az_trainer_steps", "az_trainer_check", "az_trainer_debug",
@@ -112,6 +118,7 @@ def lib():
     L.az_augment_count.argtypes = [C.c_int, vp, i64, C.POINTER(i64), vp]
     L.az_augment.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.az_engine_root_children.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.az_engine_root_readout.argtypes = [vp, vp, i32, C.POINTER(RootReadout)]
     L.az_engine_nodes_used.argtypes = [vp, i32, C.POINTER(i32)]
     L.az_engine_grow_pools.argtypes = [vp, i32]
     L.az_trainer_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]

@@ -746,6 +746,51 @@ AZ_D double linear_temp(int step, int tmax, int tmin) {  // schedulers.py:33-40
     return 1.0 - (double)(step - tmax) / (double)(tmin - tmax);
 }
 
+// get_action_probs (mcts.py:95-116) + the move choice (players.py:184-189) over the root's children pool[fc .. fc + nc): writes
+// pi[action] of every child into the (already zeroed) row `pi` when one is given and returns the index of the chosen child.
+// One lane; sum and running total in child-index order in float64.  k_move (which then plays the move) and k_root_readout (which
+// only reports it) both call this, so what a readout shows is what an advance would record and play.
+AZ_D int move_policy(const EngDev &E, const Node *pool, int fc, int nc, double temp, u32 gid, int ply, float *pi) {
+    if (temp == 0.0) {  // fair_max by N
+        int best = -1, cnt = 0, first = 0;
+        for (int i = 0; i < nc; ++i) {
+            int n = pool[fc + i].N;
+            if (n > best) { best = n; cnt = 1; first = i; } else if (n == best) cnt++;
+        }
+        int pick = first;
+        if (E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {
+            Philox4 r = az_philox(E.seed, gid, (u32)ply, 0xFFFFu, AZ_P_TIE_MOVE, 0);
+            int k = (int)(((u64)r.x * (u64)cnt) >> 32);
+            for (int i = 0; i < nc; ++i)
+                if (pool[fc + i].N == best) { if (k == 0) { pick = i; break; } --k; }
+        }
+        if (pi) pi[pool[fc + pick].act] = 1.0f;
+        return pick;
+    }
+    const double inv_temp = 1.0 / temp;
+    double sum = 0.0;
+    for (int i = 0; i < nc; ++i) {
+        double n = (double)pool[fc + i].N;
+        sum += (temp == 1.0) ? n : az_det_pow(n, inv_temp);
+    }
+    double u = 2.0, cum = 0.0;
+    if (nc > 1) {
+        Philox4 r = az_philox(E.seed, gid, (u32)ply, 0xFFFFu, AZ_P_MOVE_SAMPLE, 0);
+        u = az_u53(r.x, r.y);
+    }
+    int chosen = 0, last = 0; bool found = false;
+    for (int i = 0; i < nc; ++i) {
+        double n = (double)pool[fc + i].N;
+        double p = ((temp == 1.0) ? n : az_det_pow(n, inv_temp)) / sum;
+        if (pi) pi[pool[fc + i].act] = (float)p;
+        if (p > 0.0) last = i;
+        cum += p;
+        if (!found && u < cum) { chosen = i; found = true; }
+    }
+    if (!found) chosen = nc == 1 ? 0 : last;
+    return chosen;
+}
+
 // get_action_probs (mcts.py:95-116) + move choice (players.py:184-189) + Sample (trainer.py:244-250)
 // + play_move / change_root (trainer.py:253-256) + end-of-game bookkeeping (trainer.py:262-268).
 // Once per ply: one thread per slot.
@@ -769,45 +814,7 @@ __global__ void k_move(EngDev E) {
     int *vis = si >= 0 ? E.o_visits + (size_t)si * E.A : nullptr;
     if (si >= 0) for (int a = 0; a < E.A; ++a) { pi[a] = 0.0f; vis[a] = 0; }
 
-    int chosen = fc;
-    if (temp == 0.0) {  // fair_max by N
-        int best = -1, cnt = 0, first = 0;
-        for (int i = 0; i < nc; ++i) {
-            int n = pool[fc + i].N;
-            if (n > best) { best = n; cnt = 1; first = i; } else if (n == best) cnt++;
-        }
-        int pick = first;
-        if (E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {
-            Philox4 r = az_philox(E.seed, gid, (u32)ply, 0xFFFFu, AZ_P_TIE_MOVE, 0);
-            int k = (int)(((u64)r.x * (u64)cnt) >> 32);
-            for (int i = 0; i < nc; ++i)
-                if (pool[fc + i].N == best) { if (k == 0) { pick = i; break; } --k; }
-        }
-        chosen = fc + pick;
-        if (si >= 0) pi[pool[chosen].act] = 1.0f;
-    } else {
-        const double inv_temp = 1.0 / temp;
-        double sum = 0.0;
-        for (int i = 0; i < nc; ++i) {
-            double n = (double)pool[fc + i].N;
-            sum += (temp == 1.0) ? n : az_det_pow(n, inv_temp);
-        }
-        double u = 2.0, cum = 0.0;
-        if (nc > 1) {
-            Philox4 r = az_philox(E.seed, gid, (u32)ply, 0xFFFFu, AZ_P_MOVE_SAMPLE, 0);
-            u = az_u53(r.x, r.y);
-        }
-        int last = 0; bool found = false;
-        for (int i = 0; i < nc; ++i) {
-            double n = (double)pool[fc + i].N;
-            double p = ((temp == 1.0) ? n : az_det_pow(n, inv_temp)) / sum;
-            if (si >= 0) pi[pool[fc + i].act] = (float)p;
-            if (p > 0.0) last = i;
-            cum += p;
-            if (!found && u < cum) { chosen = fc + i; found = true; }
-        }
-        if (!found) chosen = fc + (nc == 1 ? 0 : last);
-    }
+    const int chosen = fc + move_policy(E, pool, fc, nc, temp, gid, ply, pi);
     int action = pool[chosen].act;
     if (si >= 0) {
         for (int i = 0; i < nc; ++i) vis[pool[fc + i].act] = pool[fc + i].N;
@@ -952,6 +959,105 @@ __global__ void k_best_moves(EngDev E, int *actions) {
             if (pool[fc + i].N == best) { if (k == 0) { pick = i; break; } --k; }
     }
     actions[g] = pool[fc + pick].act;
+}
+
+// Root readout for slots [0, n) in one launch: everything Player.get_move returns (players.py:158-191: the move, get_action_probs,
+// the visit counts, get_prior_probs of mcts.py:95-116) plus Q and the principal line, as dense rows indexed by action.  Reads only:
+// trees, boards, counters, sample buffers and the Philox state (a pure function of seed, game id and ply) stay as they are.
+// 16 lanes per game: lane `sub` owns the actions sub, sub + 16, ... of every row (coalesced stores); the float64 policy arithmetic
+// is move_policy in lane 0.  A slot is served when this engine searches it and its root is expanded with children; the rest get
+// action -1, root_N 0, zero rows and an empty line.  Whole groups diverge together and the group steps are width-16 shuffles.
+struct RootOut {
+    int *visits; float *pi; double *Q, *P; uint8_t *child;
+    int *action, *root_N, *pv;
+    int pv_len;
+};
+#define RO_ROWS ((AZ_MAX_ACTIONS + LPG - 1) / LPG)  // dense-row entries per lane
+
+AZ_D int sel4i(const int (&v)[4], int r) { return r == 0 ? v[0] : (r == 1 ? v[1] : (r == 2 ? v[2] : v[3])); }
+AZ_D u64 grp_max_u64(u64 v) {
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) { const u64 o = (u64)__shfl_xor((long long)v, m, LPG); v = o > v ? o : v; }
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_root_readout(EngDev E, int n, const double *temps, RootOut o) {
+    const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (g >= n) return;
+    const int A = E.A;
+    const Node *pool = pool_of(E, g);
+    bool served = searches(E, g);
+    Node rn = fresh_node(0, -1, 0.0, 0);
+    if (served) {
+        rn = load_node(pool + E.root[g]);  // one address for the group: a broadcast
+        served = (rn.flags & F_EXPANDED) && rn.nch > 0;
+    }
+    const int fc = served ? rn.first : 0, nc = served ? rn.nch : 0;
+    // which child holds each action this lane owns: the children's actions go round the group once
+    int cact[4], idx[RO_ROWS];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const int i = r * LPG + sub; cact[r] = i < nc ? (int)pool[fc + i].act : -1; }
+#pragma unroll
+    for (int r = 0; r < RO_ROWS; ++r) idx[r] = -1;
+    for (int i = 0; i < nc; ++i) {
+        const int ai = __shfl(sel4i(cact, i >> 4), i & 15, LPG);
+#pragma unroll
+        for (int r = 0; r < RO_ROWS; ++r) if (ai == r * LPG + sub) idx[r] = i;
+    }
+#pragma unroll
+    for (int r = 0; r < RO_ROWS; ++r) {
+        const int a = r * LPG + sub;
+        if (a >= A) continue;
+        const bool has = idx[r] >= 0;
+        Node c = fresh_node(0, -1, 0.0, 0);
+        if (has) c = load_node(pool + fc + idx[r]);
+        const size_t at = (size_t)g * A + a;
+        if (o.visits) o.visits[at] = has ? c.N : 0;
+        if (o.Q) o.Q[at] = has ? c.Q : 0.0;
+        if (o.P) o.P[at] = has ? c.P : 0.0;
+        if (o.child) o.child[at] = has ? 1 : 0;
+        if (o.pi) o.pi[at] = 0.0f;
+    }
+    // lane 0 writes pi[action] over the zeros the other lanes have just stored: those stores must have landed
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (sub == 0) {
+        int act = -1;
+        if (served && (o.pi || o.action)) {
+            const int ply = E.ply[g];
+            const double temp = temps ? temps[g] : linear_temp(ply, E.tmax, E.tmin);
+            act = pool[fc + move_policy(E, pool, fc, nc, temp, E.game_id[g], ply, o.pi ? o.pi + (size_t)g * A : nullptr)].act;
+        }
+        if (o.action) o.action[g] = act;
+        if (o.root_N) o.root_N[g] = served ? rn.N : 0;
+    }
+    if (!o.pv) return;
+    // principal line: from the root, the child with the greatest N (lowest action among equals) while there is one with N > 0
+    bool on = served;
+    int nf = fc, nn = nc;
+    for (int step = 0; step < o.pv_len; ++step) {
+        int out = -1;
+        if (on) {
+            u64 key = 0;  // N | 255 - action | child index: the maximum is the most visited child, the lowest action among equals
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = r * LPG + sub;
+                if (i < nn) {
+                    const Node c = load_node(pool + nf + i);
+                    const u64 k = ((u64)(u32)c.N << 16) | ((u64)(255 - c.act) << 8) | (u64)i;
+                    if (c.N > 0 && k > key) key = k;
+                }
+            }
+            key = grp_max_u64(key);
+            on = key != 0;
+            if (on) {
+                out = 255 - (int)((key >> 8) & 255);
+                const Node c = load_node(pool + nf + (int)(key & 255));
+                on = (c.flags & F_EXPANDED) && c.nch > 0;
+                nf = c.first; nn = c.nch;
+            }
+        }
+        if (sub == 0) o.pv[(size_t)g * o.pv_len + step] = out;
+    }
 }
 
 // TicTacToeBoard.get_score (tictactoe.py:119-126) is +inf when the side to move holds two cells of an alignment whose
@@ -1102,6 +1208,7 @@ struct az_engine {
     int *ext_slots = nullptr, *ext_bad = nullptr;  // ext_bad: lowest slot k_ext_check rejected
     bool in_callback = false;  // the evaluator is running: calls into this engine are refused
     bool unevaluated = false;  // a failed evaluation left leaves in the trees that were never evaluated (until set_roots / run)
+    double *ro_temps = nullptr;  // [G] per-slot temperatures of az_engine_root_readout (allocated at its first use)
 };
 
 int az_make_game_desc(int game, int H, int W, GameDesc *gd) {
@@ -1570,6 +1677,35 @@ extern "C" int az_engine_root_children(az_engine *e, int32_t slot, int32_t *h_ac
         if (h_Q) h_Q[i] = ch[i].Q;
         if (h_P) h_P[i] = ch[i].P;
     }
+    return AZ_OK;
+}
+
+// Player.get_move's results (players.py:158-191; MCT.get_action_probs / get_prior_probs, mcts.py:95-116) for slots [0, n) at once:
+// one launch of k_root_readout into the caller's device buffers, no per-slot host copy (az_engine_root_children is the one-slot form).
+extern "C" int az_engine_root_readout(az_engine *e, const double *h_temps, int32_t n, const az_root_readout *out) {
+    AZ_REQUIRE(e && out, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_root_readout");
+    AZ_USABLE(e, "az_engine_root_readout");
+    EngDev &d = e->d;
+    AZ_REQUIRE(n >= 1 && n <= d.G, AZ_EINVAL, "n must be in [1, n_slots], got %d", n);
+    AZ_REQUIRE(out->pv_len >= 0 && out->pv_len <= 16, AZ_EINVAL, "pv_len must be in [0, 16], got %d", out->pv_len);
+    AZ_REQUIRE(!(out->d_pv && out->pv_len == 0), AZ_EINVAL, "d_pv given with pv_len 0");
+    if (h_temps)
+        for (int i = 0; i < n; ++i)
+            AZ_REQUIRE(h_temps[i] >= 0.0 && h_temps[i] <= 1.7976931348623157e308, AZ_EINVAL,
+                       "temperature of slot %d is negative or not finite (%g)", i, h_temps[i]);
+    AZ_TRY(enter(e));
+    if (h_temps) {
+        if (!e->ro_temps) AZ_TRY(dev_alloc(e, &e->ro_temps, (size_t)d.G));
+        AZ_HIP(hipMemcpyAsync(e->ro_temps, h_temps, sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
+    }
+    RootOut o;
+    o.visits = out->d_visits; o.pi = out->d_pi; o.Q = out->d_Q; o.P = out->d_P; o.child = out->d_child;
+    o.action = out->d_action; o.root_N = out->d_root_N; o.pv = out->pv_len > 0 ? out->d_pv : nullptr; o.pv_len = out->pv_len;
+    hipLaunchKernelGGL(k_root_readout, dim3((unsigned)((n + GPB - 1) / GPB)), dim3(256), 0, e->stream, d, (int)n,
+                       (const double *)(h_temps ? e->ro_temps : nullptr), o);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipStreamSynchronize(e->stream));
     return AZ_OK;
 }
 

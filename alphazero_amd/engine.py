@@ -381,6 +381,45 @@ class SelfPlayEngine:
         k = k.value
         return a[:k].copy(), n[:k].copy(), q[:k].copy(), p[:k].copy(), rn.value
 
+    _READOUT = (("visits", torch.int32, True), ("pi", torch.float32, True), ("Q", torch.float64, True), ("P", torch.float64, True),
+                ("child", torch.uint8, True), ("action", torch.int32, False), ("root_N", torch.int32, False))
+
+    def root_readout(self, temps=None, pv_len=0, n=None, out=None):
+        """Player.get_move's results (players.py:158-191) for slots 0..n-1 (default: all) in one kernel launch: a dict of CUDA tensors
+        visits int32 [n, A], pi float32 [n, A], Q / P float64 [n, A], child uint8 [n, A] (1: the root holds a child for the action),
+        action int32 [n], root_N int32 [n] and, when pv_len > 0, pv int32 [n, pv_len] (the principal line, -1 padded).  pi and action
+        are what advance() would record and play now at the slot's temperature: `temps` (one number or one per slot; 0 = most
+        visited under the engine's tie mode), or the engine's scheduler at the slot's ply when None.  A slot this engine does not
+        search now, or whose root is not expanded, reads action -1 and zeros.  Nothing in the engine changes.  `out` may bring
+        tensors to fill (same names, at least n rows: rows beyond n stay as they are); what it lacks is allocated."""
+        G, A = self.cfg.n_slots, self.A
+        n = G if n is None else int(n)
+        rows = max(n, 0)
+        res, ro = {}, _lib.RootReadout()
+        shapes = [(k, dt, (rows, A) if wide else (rows,)) for k, dt, wide in self._READOUT]
+        if pv_len > 0 or (out is not None and "pv" in out):
+            shapes.append(("pv", torch.int32, (rows, max(int(pv_len), 0))))
+        for k, dt, shape in shapes:
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device="cuda")
+            elif k == "pv" and pv_len <= 0 and t.is_cuda and t.dtype == dt:
+                pass  # a line buffer without a length: the library refuses it
+            elif not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.shape[0] >= rows and tuple(t.shape[1:]) == shape[1:]):
+                raise ValueError(f"root_readout: out[{k!r}] must be a contiguous CUDA {dt} tensor of shape {shape} (or more rows)")
+            res[k] = t
+            setattr(ro, "d_" + k, t.data_ptr() if t.numel() else None)
+        ro.pv_len = int(pv_len)
+        tp = None
+        if temps is not None:
+            t = np.asarray(temps, np.float64)
+            t = np.full(rows, float(t), np.float64) if t.ndim == 0 else np.ascontiguousarray(t.reshape(-1))
+            if len(t) != rows:
+                raise ValueError(f"root_readout: {len(t)} temperatures for {rows} slots")
+            tp = t.ctypes.data
+        check(lib().az_engine_root_readout(self.h, tp, n, C.byref(ro)))
+        return res
+
     def nodes_used(self, slot=0):
         n = C.c_int32()
         check(lib().az_engine_nodes_used(self.h, slot, C.byref(n)))

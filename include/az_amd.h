@@ -172,6 +172,30 @@ int az_engine_play(az_engine *e, const int32_t *h_actions, int32_t n, int32_t *h
 /* root statistics of one slot to HOST arrays (capacity AZ_MAX 65): actions, N, Q, P */
 int az_engine_root_children(az_engine *e, int32_t slot, int32_t *h_actions, int32_t *h_N, double *h_Q,
                             double *h_P, int32_t *count, int32_t *root_N);
+/* Root readout of slots 0..n-1 in ONE kernel launch, with no per-slot host copy: everything Player.get_move returns -- (move,
+ * action_probs, visit_counts, prior_probs), players.py:158-191 -- and what MCT.get_action_probs / get_prior_probs read
+ * (mcts.py:95-116), for many positions at once.  az_engine_root_children is the one-slot form.  Rows are dense, indexed by action:
+ *   d_visits int32 [n][A] child N;  d_Q, d_P float64 [n][A] the child's Q and (noised) prior, bit for bit;
+ *   d_child uint8 [n][A] 1 where the root holds a child for the action (0 visits does not tell a legal unvisited move from an
+ *   illegal one);  d_root_N int32 [n] the root's N;
+ *   d_pi float32 [n][A], d_action int32 [n]: exactly the policy az_engine_advance would record and the move it would play now, at
+ *   the slot's temperature: h_temps[g] (0 = fair_max over N under the engine's tie_mode, else N^(1/t) / sum and the sampled move),
+ *   or the engine's LinearTemperatureScheduler at the slot's ply when h_temps is NULL;
+ *   d_pv int32 [n][pv_len], 0 <= pv_len <= 16: the principal line -- from the root, step to the child with the greatest N (lowest
+ *   action among equals) until a node is not expanded, has no children or its best child has N = 0; unused entries are -1.
+ *   d_pv[g][0] is the deterministic most-visited move and may differ from d_action[g], which draws among equals under
+ *   AZ_TIE_MODE_RANDOM and samples at a temperature above 0.
+ * A slot is served when the engine searches it (active; in arena mode its colour to move) and its root is expanded with children;
+ * any other slot gets action -1, root_N 0, zero rows and a line of -1.  Rows beyond n are not touched.  The call changes nothing:
+ * trees, boards, counters, samples and random streams are as if it had not run.  Blocks until the outputs are written.
+ * AZ_EINVAL: null e / out, n outside [1, n_slots], pv_len outside [0, 16], d_pv with pv_len 0, a temperature that is negative or
+ * not finite (the message names the lowest such slot). */
+typedef struct {            /* DEVICE pointers; any may be NULL = not wanted */
+    int32_t *d_visits; float *d_pi; double *d_Q, *d_P; uint8_t *d_child;
+    int32_t *d_action, *d_root_N, *d_pv; int32_t pv_len;
+} az_root_readout;
+/* h_temps: HOST double[n] or NULL (the engine's scheduler at each slot's ply) */
+int az_engine_root_readout(az_engine *e, const double *h_temps, int32_t n, const az_root_readout *out);
 /* The reference's tree (mcts.py:8-47 Node objects) grows without bound while MCT.search is called again and again on one root;
  * the engine's pools have a fixed size: nodes the slot's live pool holds, and re-allocation of all pools with a larger capacity
  * (trees kept).  The single-game MCT mirror grows its pools before a search could exhaust them. */
