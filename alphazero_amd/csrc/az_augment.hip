@@ -18,19 +18,6 @@ __global__ void k_aug_flags(const int *meta, long long S, int *flags) {
     if (i < S) flags[i] = meta[i * 4 + 1] >= 2 ? 1 : 0;  // trainer.py:278
 }
 
-// source cell (r,c) of output cell (i,j) under transform code t: 0 none, 1 reflH, 2 rot90, 3 reflH+rot90, 4 rot180, ...
-// np.flip(axis=1): out[i][j] = in[i][W-1-j];  np.rot90(m,k): k=1 out[i][j] = in[j][n-1-i], k=2 in[n-1-i][n-1-j], k=3 in[n-1-j][i]
-AZ_D void aug_source(int t, int n, int W, int i, int j, int *r, int *c) {
-    int k = t >> 1;  // quarter turns
-    int rr, cc;
-    if (k == 0) { rr = i; cc = j; }
-    else if (k == 1) { rr = j; cc = n - 1 - i; }
-    else if (k == 2) { rr = n - 1 - i; cc = n - 1 - j; }
-    else { rr = n - 1 - j; cc = i; }
-    if (t & 1) cc = W - 1 - cc;  // the rotation acts on the reflected board
-    *r = rr; *c = cc;
-}
-
 __global__ void k_augment(GameDesc gd, int n_twins, const int8_t *state, const float *pi, const int8_t *z, const int *meta,
                           const int *flags, const int *offs, long long S, int8_t *o_state, float *o_pi, int8_t *o_z, int *o_meta) {
     long long i = (long long)blockIdx.x;

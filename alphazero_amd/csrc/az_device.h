@@ -397,3 +397,21 @@ AZ_D u64 az_board_hash(const GameDesc& gd, const BB& b) {
         }
     return az_splitmix64(h);
 }
+
+// ---------------------------------------------------------------------------------------------
+// board symmetries (az_augment.hip: the trainer's twins; az_symmetry.hip: ensemble inference)
+// ---------------------------------------------------------------------------------------------
+// source cell (r,c) of output cell (i,j) under transform code t: 0 none, 1 reflH, 2 rot90, 3 reflH+rot90, 4 rot180, ...
+// np.flip(axis=1): out[i][j] = in[i][W-1-j];  np.rot90(m,k): k=1 out[i][j] = in[j][n-1-i], k=2 in[n-1-i][n-1-j], k=3 in[n-1-j][i]
+AZ_D void aug_source(int t, int n, int W, int i, int j, int *r, int *c) {
+    int k = t >> 1;  // quarter turns
+    int rr, cc;
+    if (k == 0) { rr = i; cc = j; }
+    else if (k == 1) { rr = j; cc = n - 1 - i; }
+    else if (k == 2) { rr = n - 1 - i; cc = n - 1 - j; }
+    else { rr = n - 1 - j; cc = i; }
+    if (t & 1) cc = W - 1 - cc;  // the rotation acts on the reflected board
+    *r = rr; *c = cc;
+}
+// code of the inverse transform: reflections (with or without a rotation) are involutions, rot90 <-> rot270
+AZ_D int aug_inverse(int t) { return (t & 1) ? t : ((8 - t) & 7); }

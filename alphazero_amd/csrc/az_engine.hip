@@ -1209,6 +1209,10 @@ struct az_engine {
     bool in_callback = false;  // the evaluator is running: calls into this engine are refused
     bool unevaluated = false;  // a failed evaluation left leaves in the trees that were never evaluated (until set_roots / run)
     double *ro_temps = nullptr;  // [G] per-slot temperatures of az_engine_root_readout (allocated at its first use)
+    // az_engine_set_symmetry: the transform codes every leaf is averaged over (0: off) and the twins' rows, [sym_rows] each
+    int sym_mask = 0, sym_n = 0, sym_rows = 0;
+    float *sym_in = nullptr, *sym_p = nullptr, *sym_v = nullptr;
+    int *sym_cnt = nullptr;  // sym_n * the pending count, written by k_sym_expand for az_net_forward_dyn
 };
 
 int az_make_game_desc(int game, int H, int W, GameDesc *gd) {
@@ -1369,7 +1373,11 @@ static int forward(az_engine *e, const int *cnt, int cap, int step) {
         hipLaunchKernelGGL(k_fakenet, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, cnt);
         return AZ_OK;
     }
-    return az_net_forward_dyn(e->net, d.nn_in, cnt, cap, d.probs, d.value, e->stream);
+    if (e->sym_mask == 0) return az_net_forward_dyn(e->net, d.nn_in, cnt, cap, d.probs, d.value, e->stream);
+    // ensemble over the board's symmetries: twins of the pending rows -> the network on sym_n * count rows -> mapped back and averaged
+    AZ_TRY(az_sym_expand(&d.gd, e->sym_mask, d.nn_in, cnt, cap, e->sym_in, e->sym_cnt, e->stream));
+    AZ_TRY(az_net_forward_dyn(e->net, e->sym_in, e->sym_cnt, e->sym_n * cap, e->sym_p, e->sym_v, e->stream));
+    return az_sym_reduce(&d.gd, e->sym_mask, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
 }
 
 // MCT.search for every active slot: one root-prior pass (mcts.py:231-233; empty unless a slot holds a
@@ -1827,6 +1835,37 @@ extern "C" int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h
     AZ_HIP(hipMemcpyAsync(h_winner, wi, G, hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipMemcpyAsync(h_score, sc, G * sizeof(int), hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
+    return AZ_OK;
+}
+
+// ---- leaf evaluation over the board's symmetries (az_symmetry.hip; forward() above) --------------------------
+extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_symmetry");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_symmetry");
+    EngDev &d = e->d;
+    AZ_REQUIRE(e->cfg.evaluator == AZ_EVAL_NET, AZ_EINVAL, "az_engine_set_symmetry needs an engine created with evaluator = AZ_EVAL_NET (this one: %d)",
+               e->cfg.evaluator);
+    int n = 0;
+    AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
+    AZ_REQUIRE((long long)n * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
+               "%d symmetries of %d slots are %lld rows, the network's max_batch is %d", n, d.G, (long long)n * d.G, az_net_max_batch(e->net));
+    if (mask == e->sym_mask) return AZ_OK;
+    AZ_TRY(enter(e));
+    const int rows = n * d.G;
+    if (rows > e->sym_rows) {  // the rows of a smaller mask stay allocated until the engine goes (e->allocs)
+        AZ_TRY(dev_alloc(e, &e->sym_in, (size_t)rows * d.gd.cells));
+        AZ_TRY(dev_alloc(e, &e->sym_p, (size_t)rows * d.A));
+        AZ_TRY(dev_alloc(e, &e->sym_v, (size_t)rows));
+        if (!e->sym_cnt) AZ_TRY(dev_alloc(e, &e->sym_cnt, 1));
+        AZ_HIP(hipStreamSynchronize(e->stream));
+        e->sym_rows = rows;
+    }
+    e->sym_mask = mask; e->sym_n = n;
+    // the launch sequence of a search changes: nothing captured before may be replayed
+    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
+    e->graphs.clear();
+    e->graph_seen.clear();
     return AZ_OK;
 }
 

@@ -2711,6 +2711,7 @@ struct az_net {
     size_t qd_rows = 0;  // rows of a digit plane of qd_a (max_batch rounded up to a whole tile)
     MlpParams mlp;           // host staging of the TicTacToe MLP
     MlpParams *mlp_dev = nullptr;  // what k_mlp reads
+    float *sym_in = nullptr, *sym_p = nullptr, *sym_v = nullptr;  // az_net_forward_sym: twins and their outputs, [max_batch] rows (first use)
     bool committed;
     // live per-stage timing (az_net_profile): HIP events around every stage launch, harvested in batches
     bool prof = false;
@@ -2805,6 +2806,21 @@ extern "C" void az_net_destroy(az_net *n) {
 }
 
 extern "C" int az_net_action_size(const az_net *n) { return n ? n->A : 0; }
+
+// what az_symmetry.hip needs of a network (az_host.h)
+int az_net_max_batch(const az_net *n) { return n->max_batch; }
+void az_net_shape(const az_net *n, int *game, int *H, int *W) { *game = n->game; *H = n->H; *W = n->W; }
+int az_net_sym_scratch(az_net *n, float **d_in, float **d_p, float **d_v) {
+    if (!n->sym_in) {
+        float *a = nullptr, *b = nullptr, *c = nullptr;
+        AZ_TRY(net_alloc(n, &a, (size_t)n->max_batch * n->H * n->W));
+        AZ_TRY(net_alloc(n, &b, (size_t)n->max_batch * n->A));
+        AZ_TRY(net_alloc(n, &c, (size_t)n->max_batch));
+        n->sym_in = a; n->sym_p = b; n->sym_v = c;
+    }
+    *d_in = n->sym_in; *d_p = n->sym_p; *d_v = n->sym_v;
+    return AZ_OK;
+}
 
 extern "C" int64_t az_net_flops_per_board(const az_net *n) {
     if (!n) return 0;

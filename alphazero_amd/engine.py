@@ -154,6 +154,18 @@ class HipNet:
         check(lib().az_net_forward_dyn(self.h, x.data_ptr(), count.data_ptr(), B, probs.data_ptr(), v.data_ptr(), _stream_ptr()))
         return probs, v
 
+    def forward_sym(self, x, symmetry="all"):
+        """forward() averaged over the board's symmetries (az_net_forward_sym): `symmetry` is "all", None (off), a mask or an
+        iterable of transform codes (alphazero_amd.symmetry).  Needs len(members) * B <= max_batch."""
+        from .symmetry import resolve
+        x = x.contiguous().view(-1, self.H * self.W)
+        assert x.is_cuda and x.dtype == torch.float32
+        B = x.shape[0]
+        probs = torch.empty((B, self.A), dtype=torch.float32, device=x.device)
+        v = torch.empty(B, dtype=torch.float32, device=x.device)
+        check(lib().az_net_forward_sym(self.h, x.data_ptr(), B, resolve(symmetry), probs.data_ptr(), v.data_ptr(), _stream_ptr()))
+        return probs, v
+
     def flops_per_board(self):
         return int(lib().az_net_flops_per_board(self.h))
 
@@ -298,6 +310,12 @@ class SelfPlayEngine:
             except AzError as err:
                 raise exc from err
         check(rc)
+
+    def set_symmetry(self, symmetry):
+        """every leaf evaluation of this engine (EVAL_NET only) averaged over the board's symmetries: "all", None (off), a mask
+        or an iterable of transform codes (alphazero_amd.symmetry).  The network needs max_batch >= len(members) * n_slots."""
+        from .symmetry import resolve
+        check(lib().az_engine_set_symmetry(self.h, resolve(symmetry)))
 
     def run(self, n_games, first_game_id=0):
         """plays n_games to completion; returns the samples as a dict of CUDA tensors (copies)."""

@@ -7,7 +7,7 @@ from time import sleep
 import numpy as np
 
 from .base import Player
-from .mcts import MCT, _action_of, _move_of
+from .mcts import MCT, _action_of, _move_of, check_symmetry
 from .utils import fair_max
 
 
@@ -80,20 +80,27 @@ class MCTSPlayer(Player):
 
 
 class AlphaZeroPlayer(MCTSPlayer):
-    def __init__(self, n_sim=None, compute_time=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, verbose=False):
+    def __init__(self, n_sim=None, compute_time=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, verbose=False,
+                 symmetry=None):
         super().__init__(n_sim=n_sim, compute_time=compute_time, verbose=verbose)
-        self.mct = MCT(eval_method="neural", nn=nn, dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon)
+        self.mct = MCT(eval_method="neural", nn=nn, dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
+                       symmetry=symmetry)
+
+    @property
+    def symmetry(self):
+        """the symmetries every leaf evaluation is averaged over (alphazero_amd.symmetry; None: off)"""
+        return self.mct.symmetry
 
     def clone(self):
         return AlphaZeroPlayer(n_sim=self.n_sim, compute_time=self.compute_time,
                                nn=self.mct.nn.clone() if self.mct.nn is not None else None,
                                dirichlet_alpha=self.mct.dirichlet_alpha, dirichlet_epsilon=self.mct.dirichlet_epsilon,
-                               verbose=self.verbose)
+                               verbose=self.verbose, symmetry=self.mct.symmetry)
 
     def reset(self):
         old = self.mct
         self.mct = MCT(eval_method="neural", nn=old.nn, dirichlet_alpha=old.dirichlet_alpha,
-                       dirichlet_epsilon=old.dirichlet_epsilon)
+                       dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry)
         # keep the uploaded weights and the device tree storage: a reset only drops the tree
         self.mct._hipnet, self.mct._engine, self.mct._engine_board = old._hipnet, old._engine, old._engine_board
         self.mct._evaluator = old._evaluator  # the carried engine calls it (external evaluation, evaluators.route)
@@ -121,7 +128,7 @@ class BatchedMCTSPlayer(Player):
         if int(n_slots) < 1:
             raise ValueError("n_slots must be a positive integer")
         self.n_sim, self.n_slots = int(n_sim), int(n_slots)
-        self.nn, self.dirichlet_alpha, self.dirichlet_epsilon = None, None, None
+        self.nn, self.dirichlet_alpha, self.dirichlet_epsilon, self.symmetry = None, None, None, None
         self._seed = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         self._engine = None           # n_slots device trees
         self._engine_board = None     # (game, H, W) the engine was built for
@@ -173,6 +180,7 @@ class BatchedMCTSPlayer(Player):
     def _build(self, first):
         from .engine import (EVAL_EXTERNAL, EVAL_NET, EVAL_ROLLOUT, GAME_IDS, NOISE_OFF, NOISE_PHILOX, TIE_RANDOM, SelfPlayEngine)
         from .evaluators import make_evaluator, route
+        from .symmetry import members
         H, W = first.grid.shape
         if self._engine is not None and self._engine_board != (first.game, H, W):
             self._engine.close()  # built for another board: rebuild rather than search with the wrong rules
@@ -181,8 +189,9 @@ class BatchedMCTSPlayer(Player):
             return
         neural = self._eval_method == "neural"
         external = neural and route(self.nn) != "hip"  # evaluates the leaves itself, as in BatchedArena._engine
+        sym = members(first.game, H, W, check_symmetry(self.symmetry, self.nn if neural else None))
         if neural and not external:
-            self._hipnet = self.nn.to_hip(max_batch=self.n_slots)
+            self._hipnet = self.nn.to_hip(max_batch=max(1, len(sym)) * self.n_slots)  # every slot's leaf in each of its twins
         noisy = self.dirichlet_alpha is not None and self.dirichlet_epsilon is not None
         self._engine = SelfPlayEngine(GAME_IDS[first.game], H, W, n_slots=self.n_slots, n_sim=self.n_sim,
                                       net=self._hipnet if neural and not external else None,
@@ -194,6 +203,8 @@ class BatchedMCTSPlayer(Player):
         if external:
             self._evaluator = make_evaluator(self.nn, first.game, H, W)
             self._engine.set_evaluator(self._evaluator)
+        if sym:
+            self._engine.set_symmetry(sym)
         self._engine_board = (first.game, H, W)
 
     def _sync(self, boards, first):
@@ -283,12 +294,17 @@ class BatchedMCTSPlayer(Player):
 
 class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
     """AlphaZeroPlayer (players.py:194-247) for up to n_slots games at once: PUCT with the network `nn` (the HIP network for a shipped
-    architecture, else the network's own evaluate / predict through an external evaluator), optional root Dirichlet noise"""
+    architecture, else the network's own evaluate / predict through an external evaluator), optional root Dirichlet noise and an
+    optional ensemble over the board's symmetries (`symmetry`: "all", a mask or transform codes; HIP network only)"""
     _eval_method = "neural"
 
-    def __init__(self, n_sim=None, nn=None, n_slots=1, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, verbose=False):
+    def __init__(self, n_sim=None, nn=None, n_slots=1, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, verbose=False,
+                 symmetry=None):
         super().__init__(n_sim=n_sim, n_slots=n_slots, seed=seed, verbose=verbose)
         self.nn, self.dirichlet_alpha, self.dirichlet_epsilon = nn, dirichlet_alpha, dirichlet_epsilon
+        # leaf evaluations averaged over the board's symmetries (alphazero_amd.symmetry; None: off); HIP-routed networks only
+        self.symmetry = symmetry
+        check_symmetry(symmetry, nn)
 
 
 PLAYERS_SET = {"human", "random", "greedy", "mcts", "alphazero"}

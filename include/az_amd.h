@@ -94,6 +94,18 @@ int az_net_forward(az_net *net, const float *d_input, int B, float *d_probs, flo
  * earlier kernel on `stream` (the engine compacts the leaves that need an evaluation into the front rows). */
 int az_net_forward_dyn(az_net *net, const float *d_input, const int32_t *d_count, int max_B, float *d_probs,
                        float *d_value, void *stream);
+/* Evaluation averaged over the board's symmetries (ensemble inference: AlphaGo Zero evaluates each leaf in one of the eight
+ * orientations, Silver et al. 2017 "Mastering the game of Go without human knowledge", Methods; KataGo's analysis mode averages
+ * over all of them).  The reference has no counterpart: it uses the symmetries for training samples only (trainer.py:275-284).
+ * A mask is a set of transform codes, bit t = code t: the codes of az_augment below (t & 1 horizontal reflection first, t >> 1
+ * quarter turns of np.rot90) plus 0 for the identity.  Any subset on a square Othello / TicTacToe board, a subset of {0, 1} for
+ * Connect4 (gravity rules rotations out on any board); AZ_SYM_ALL = every valid code; 0 = off.  The n = popcount(mask) members
+ * are visited in ascending code order: each row is expanded into its n twins, the ordinary forward runs on the n * B rows, and
+ *   d_probs[r][a] = (sum_j p[r n + j][cell of twin j that holds original action a]) / (float)n,   d_value[r] = (sum_j v[r n + j]) / (float)n
+ * with float32 sums taken sequentially in member order (Othello's pass entry stays in place, Connect4 flips its columns).
+ * Needs n * B <= max_batch (AZ_EINVAL otherwise); the scratch rows belong to the net and are allocated at the first call. */
+#define AZ_SYM_ALL (-1)
+int az_net_forward_sym(az_net *net, const float *d_input, int B, int32_t mask, float *d_probs, float *d_value, void *stream);
 int az_net_action_size(const az_net *net);
 /* algorithmic FLOPs of one forward per board (2*MAC) */
 int64_t az_net_flops_per_board(const az_net *net);
@@ -221,6 +233,13 @@ int az_engine_search_begin(az_engine *e, int32_t n_sim);
 int az_engine_pair(az_engine *a, az_engine *b);
 int az_engine_search_end(az_engine *e);
 int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h_over, int8_t *h_winner, int32_t *h_score);
+
+/* Every leaf evaluation of this engine -- the root-prior pass and every lock-step -- averaged over the symmetries in `mask`
+ * (az_net_forward_sym above: same codes, same arithmetic, on the pending rows only).  Off (mask 0) by default and after
+ * az_engine_set_symmetry(e, 0), when the launch sequence is exactly the plain one.  Costs two small launches per lock-step and n
+ * times the network rows.  The engine's cached search graphs are dropped.  AZ_EINVAL: a code the game or board does not have,
+ * an engine whose evaluator is not AZ_EVAL_NET, a net with max_batch < n * n_slots; AZ_ESTATE while a search is open. */
+int az_engine_set_symmetry(az_engine *e, int32_t mask);
 
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
