@@ -12,6 +12,7 @@ TIE_LOWEST, TIE_RANDOM = 0, 1
 NOISE_OFF, NOISE_PHILOX, NOISE_HASH = 0, 1, 2
 EVAL_NET, EVAL_FAKE, EVAL_ROLLOUT, EVAL_EXTERNAL = 0, 1, 2, 3
 SYM_ALL = -1  # AZ_SYM_ALL: every transform code the board has
+MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH
 
 
 class AzError(RuntimeError):
@@ -61,7 +62,7 @@ SYMBOLS = [
     "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
     "az_engine_get_stats", "az_engine_samples", "az_engine_set_roots", "az_engine_search", "az_engine_search_begin", "az_engine_search_end", "az_engine_pair", "az_engine_advance",
     "az_engine_root_children", "az_engine_root_readout", "az_engine_nodes_used", "az_engine_grow_pools", "az_engine_play", "az_augment_count", "az_augment",
-    "az_engine_set_sides", "az_engine_best_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator", "az_engine_set_symmetry",
+    "az_engine_set_sides", "az_engine_best_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator", "az_engine_set_symmetry", "az_engine_set_leaf_batch", "az_engine_collisions",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
     "az_trainer_steps", "az_trainer_check", "az_trainer_debug",
 ]
@@ -118,6 +119,8 @@ def lib():
     L.az_engine_root_status.argtypes = [vp, vp, vp, vp, vp]
     L.az_engine_set_evaluator.argtypes = [vp, EVAL_FN, vp]
     L.az_engine_set_symmetry.argtypes = [vp, i32]
+    L.az_engine_set_leaf_batch.argtypes = [vp, i32]
+    L.az_engine_collisions.argtypes = [vp, C.POINTER(i64)]
     L.az_augment_count.argtypes = [C.c_int, vp, i64, C.POINTER(i64), vp]
     L.az_augment.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.az_engine_root_children.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]

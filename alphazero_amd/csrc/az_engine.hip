@@ -2,7 +2,8 @@
 //
 // G concurrent games each advance ONE simulation per lock-step; the G pending leaves form one
 // batch for the policy-value network.  Every tree still sees strictly sequential simulations, so
-// per-game semantics equal the reference's MCT.search (mcts.py:226-269) exactly -- no virtual loss.
+// per-game semantics equal the reference's MCT.search (mcts.py:226-269) exactly -- no virtual loss.  (Opt-in, default off:
+// az_engine_set_leaf_batch walks K simulations per game and lock-step with virtual loss -- k_step_multi below, another search.)
 //
 // HBM layout
 //   boards   : 2 x u64 bitboards + int8 side-to-move per slot (root and current leaf), SoA over slots
@@ -40,6 +41,7 @@
 #define LS_NONE 0
 #define LS_EVAL 1
 #define LS_TERM 2
+#define LS_DUP 16  // leaf_batch > 1 only: LS_DUP + i = the walker landed on the pending (LS_EVAL) leaf of walker i of the same lock-step
 
 #define ERR_NODE_POOL 1
 #define ERR_SAMPLE_CAP 2
@@ -52,6 +54,10 @@
 #define GPB (256 / LPG) // games per 256-thread block
 
 enum { CTR_SAMPLES = 0, CTR_GAMES_DONE, CTR_NET_EVALS, CTR_NEXT_GAME, CTR_TOTAL_GAMES, CTR_FIRST_ID, CTR_PLIES, CTR_COUNT };
+// entries beyond CTR_COUNT live as long as the engine (k_reset_all clears [0, CTR_COUNT) only)
+enum { CTR_COLLISIONS = CTR_COUNT, CTR_ALLOC };
+#define MLB AZ_MAX_LEAF_BATCH  // walkers per slot and lock-step: one per lane of the game's group
+static_assert(MLB == LPG, "walker j's pending leaf is kept by lane j of the game's group");
 
 struct __attribute__((aligned(16))) Node {
     double Q, P;
@@ -86,6 +92,11 @@ struct EngDev {
     unsigned long long *ctr;
     int *err, *max_nodes;
     int *max_path;  // longest root..leaf path (nodes) of any simulation, recorded only beyond LPG (the parent-chasing backup)
+    // az_engine_set_leaf_batch (k_step_multi): K walkers per slot and lock-step; their pending leaves, [G][MLB] (m_path [G][MLB][LPG]).
+    // nn_in / probs / value then hold K * G rows.  K == 1: k_step and the fields above, these stay unallocated.
+    int K;
+    int *m_leaf; u64 *m_leaf_p1, *m_leaf_m1; int8_t *m_leaf_player, *m_leaf_status, *m_leaf_winner;
+    int *m_row, *m_path, *m_path_len;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -588,6 +599,236 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
         o[7] = (unsigned long long)depth;
     }
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------
+// leaf_batch = K > 1 (az_engine_set_leaf_batch): K simulations per slot and lock-step, kept apart by virtual loss.
+// The reference searches strictly one simulation after the other (mcts.py:127-171 select_node, 197-223 back_propagate,
+// 254-262 the loop of search): this is a different search, opt-in.  Contract:
+//   lock-step t runs the walkers j = 0 .. k_t - 1 of every searching slot, simulation index t * K + j, one after the other;
+//   walker j scores a child c of parent p with v(x) = the number of walkers i < j of this lock-step whose recorded path holds x:
+//     Q term   v(c) == 0 ? c.Q : ((double)c.N * c.Q - (double)v(c)) / (double)(c.N + v(c))
+//     U term   (c.P * sqrt((double)(p.N + v(p)))) / (double)(1 + c.N + v(c))
+//   (every v = 0: pick_child_grp's expression, bit for bit); break tests and flags use the real N; a path position at depth >= LPG
+//   is not recorded and counts 0.  A walker that lands on the pending leaf of an earlier walker i is a duplicate of i: no network
+//   row, and at backup it propagates i's outcome.  Backup runs in ascending j (the bump allocator advances in that order).
+// Virtual counts are never stored in a node: lane d of the group keeps the d-th node of every earlier walker's path (vpath), and a
+// child at depth d + 1 is compared with path_i[d + 1] fetched from lane d + 1 by shuffle.
+// ---------------------------------------------------------------------------------------------
+AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
+                           int ply, int sim, int depth, int sub, Node &chosen) {
+    const int fc = parent.first, nc = parent.nch;
+    int vp = 0, vc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < MLB; ++i) {
+        if (i < j) {  // uniform over the group
+            const int pd = depth < LPG ? __shfl(vpath[i], depth & (LPG - 1), LPG) : -1;
+            const int cd = depth + 1 < LPG ? __shfl(vpath[i], (depth + 1) & (LPG - 1), LPG) : -1;
+            vp += pd == pnode ? 1 : 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vc[r] += cd == fc + r * LPG + sub ? 1 : 0;
+        }
+    }
+    const double sq = sqrt((double)(parent.N + vp));
+    double key[4];
+    int cN[4], cfirst[4];
+    u32 cpack[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        key[r] = -__builtin_inf();
+        cN[r] = 0; cfirst[r] = -1; cpack[r] = 0;
+        int i = r * LPG + sub;
+        if (i < nc) {
+            Node c = load_node(pool + fc + i);
+            const double q = vc[r] == 0 ? c.Q : ((double)c.N * c.Q - (double)vc[r]) / (double)(c.N + vc[r]);
+            key[r] = q + (c.P * sq) / (double)(1 + c.N + vc[r]);
+            cN[r] = c.N; cfirst[r] = c.first;
+            cpack[r] = (u32)c.nch | ((u32)c.act << 8) | ((u32)c.flags << 16) | ((u32)(uint8_t)c.win << 24);
+        }
+    }
+    double best = grp_max(fmax(fmax(key[0], key[1]), fmax(key[2], key[3])));
+    u32 mask[4];
+    int cnt = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { mask[r] = grp_ballot(key[r] == best); cnt += __popc(mask[r]); }
+    if (cnt == 0 && sub == 0) atomicOr(E.err, ERR_INTERNAL);  // NaN scores (a diverged network): no key equals the maximum
+    int k = 0;
+    if (E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {
+        Philox4 rr = az_philox(E.seed, E.game_id[g], (u32)ply, (u32)sim + E.sim_base, AZ_P_TIE_SELECT, (u32)depth);
+        k = (int)(((u64)rr.x * (u64)cnt) >> 32);
+    }
+    int rsel = 0, lsel = 0;
+    bool found = false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        int pc = __popc(mask[r]);
+        if (!found) {
+            if (k < pc) { rsel = r; lsel = kth_set_bit(mask[r], k); found = true; }
+            else k -= pc;
+        }
+    }
+    const int vN = rsel == 0 ? cN[0] : (rsel == 1 ? cN[1] : (rsel == 2 ? cN[2] : cN[3]));
+    const int vF = rsel == 0 ? cfirst[0] : (rsel == 1 ? cfirst[1] : (rsel == 2 ? cfirst[2] : cfirst[3]));
+    const u32 vP = rsel == 0 ? cpack[0] : (rsel == 1 ? cpack[1] : (rsel == 2 ? cpack[2] : cpack[3]));
+    chosen.N = __shfl(vN, lsel, LPG);
+    chosen.first = __shfl(vF, lsel, LPG);
+    const u32 pk = (u32)__shfl((int)vP, lsel, LPG);
+    chosen.nch = (uint8_t)(pk & 0xff); chosen.act = (uint8_t)((pk >> 8) & 0xff); chosen.flags = (uint8_t)((pk >> 16) & 0xff);
+    chosen.win = (int8_t)(pk >> 24);
+    chosen.Q = 0.0; chosen.P = 0.0; chosen.parent = 0;  // not needed by the walk
+    return fc + rsel * LPG + lsel;
+}
+
+// One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
+// SELECT of kt walkers.  Lane j of the game's group owns walker j's pending words (loaded / stored coalesced, handed round by
+// shuffle); the walkers themselves run one after the other on all 16 lanes, as a simulation of k_step does.
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_multi(EngDev E, int t, int kb, int kt) {
+    const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { E.batch_cnt[(t + 1) & 1] = 0; if (!SELECT) E.batch_cnt[2] = 0; }
+    // groups beyond the last slot stay as inert groups: every __syncthreads() below is reached by every wave once (see k_step)
+    const bool in_range = g < E.G;
+    const int gs = in_range ? g : E.G - 1;
+    Node *pool = pool_of(E, gs);
+    const size_t wj = (size_t)gs * MLB + sub;  // this lane's walker
+    // ---- every per-slot and per-walker word in one batch of independent loads
+    const int p_st = (BACKUP && in_range && sub < kb) ? E.m_leaf_status[wj] : LS_NONE;
+    const int p_leaf = BACKUP ? E.m_leaf[wj] : 0;
+    const u64 p_p1 = BACKUP ? E.m_leaf_p1[wj] : 0, p_m1 = BACKUP ? E.m_leaf_m1[wj] : 0;
+    const int p_pl = BACKUP ? E.m_leaf_player[wj] : 1, p_win = BACKUP ? E.m_leaf_winner[wj] : 0;
+    const int p_row = BACKUP ? E.m_row[wj] : 0, p_plen = BACKUP ? E.m_path_len[wj] : 0;
+    int path_cur = (BACKUP && kb > 0) ? E.m_path[(size_t)gs * MLB * LPG + sub] : 0;
+    int n_nodes = E.n_nodes[gs];
+    int evals = E.evals[gs];
+    bool active = in_range && searches(E, gs);
+    const int ply = E.ply[gs];
+    const BB rb = {E.root_p1[gs], E.root_m1[gs], E.root_player[gs]};
+    const int root = E.root[gs];
+    if (BACKUP) {
+        double p_out = 0.0;  // lane j: the outcome walker j propagated (a duplicate of j propagates it again)
+        bool dead = false;
+        for (int j = 0; j < kb; ++j) {
+            // the next walker's path indices travel while this one is backed up
+            const int path_next = (j + 1 < kb) ? E.m_path[((size_t)gs * MLB + j + 1) * LPG + sub] : 0;
+            const int st = __shfl(p_st, j, LPG);
+            if (st != LS_NONE && !dead) {
+                const int leaf = __shfl(p_leaf, j, LPG), plen = __shfl(p_plen, j, LPG);
+                const BB lb = {(u64)__shfl((long long)p_p1, j, LPG), (u64)__shfl((long long)p_m1, j, LPG), __shfl(p_pl, j, LPG)};
+                Node mine;
+                const bool on_path = plen <= LPG && sub < plen;
+                if (on_path) mine = load_node(pool + path_cur);
+                double outcome;
+                bool ok = true;
+                if (st == LS_EVAL) {
+                    const int row = __shfl(p_row, j, LPG);
+                    const float v = E.value[row];
+                    int k = create_children_grp(E, g, pool, n_nodes, leaf, lb, E.probs + (size_t)row * E.A, sub);
+                    ok = k > 0;
+                    n_nodes += ok ? k : 0;
+                    outcome = (double)lb.player * (double)v;  // base.py:366
+                    if (ok) evals += 1;
+                    if (sub == j) p_out = outcome;
+                } else if (st >= LS_DUP) {
+                    outcome = __shfl(p_out, st - LS_DUP, LPG);
+                } else {
+                    outcome = (double)__shfl(p_win, j, LPG);
+                }
+                if (ok) back_propagate_grp(pool, plen, path_cur, mine, leaf, lb.player, outcome, sub);
+                else { dead = true; active = false; if (sub == 0) E.active[g] = 0; }
+                // this walker's stores (other lanes) must be visible to the next walker's loads
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            }
+            path_cur = path_next;
+        }
+        if (sub == 0 && in_range) E.evals[g] = evals;
+        if (!SELECT && in_range) E.m_leaf_status[wj] = LS_NONE;
+    }
+    if (!SELECT) return;
+    // From here on no group may leave early: all walks first, then the rows of the whole block behind two barriers (one LDS count
+    // of the LS_EVAL walkers, one global atomic).  No barrier inside the walker loop.
+    __shared__ int s_need, s_base;
+    if (threadIdx.x == 0) s_need = 0;
+    int k_st = LS_NONE, k_leaf = 0, k_pl = 1, k_w = 0, k_plen = 0;  // lane j: walker j's pending leaf
+    u64 k_p1 = 0, k_m1 = 0;
+    int vpath[MLB];  // vpath[i]: the sub-th node of walker i's path (-1: none)
+#pragma unroll
+    for (int i = 0; i < MLB; ++i) vpath[i] = -1;
+    if (active) {
+        Node rootn = load_node(pool + root);
+        int ndup = 0;
+        for (int j = 0; j < kt; ++j) {
+            const int sim = t * E.K + j;
+            BB b = rb;
+            int node = root, depth = 0, plen = 1, w = 0;
+            bool bad = false;
+            Node cur = rootn;
+            if (E.noise_mode != AZ_NOISE_OFF && E.alpha >= 0.0 && E.eps >= 0.0 && (cur.flags & F_EXPANDED) && !(cur.flags & F_NOISED)) {
+                apply_root_noise_grp(E, g, pool, node, cur, b, ply, sim, sub);
+                cur.flags |= F_NOISED;
+                rootn.flags = cur.flags;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            }
+            int my_path = sub == 0 ? node : -1;  // lane i keeps the i-th node of the root..leaf path
+            for (;;) {
+                bool fresh = false;
+                if (!(cur.flags & F_EXPANDED)) {
+                    if (cur.flags & F_TERMINAL) break;  // mcts.py:146-147
+                    if (!(cur.flags & F_EVALUATED)) { bad = true; break; }
+                    cur.flags |= F_EXPANDED;  // mcts.py:151-160 : children become visible now, also to the walkers that follow
+                    if (sub == 0) pool[node].flags = cur.flags;
+                    if (depth == 0) rootn.flags = cur.flags;
+                    fresh = true;
+                }
+                Node ch;
+                const int c = pick_child_vl_grp(E, g, pool, cur, node, vpath, j, ply, sim, depth, sub, ch);
+                ++depth;
+                node = c; cur = ch;
+                if (sub == plen) my_path = c;
+                ++plen;
+                az_play_grp(E.gd, b, cur.act, sub);
+                if (fresh || cur.N == 0) break;  // mcts.py:143-144
+            }
+            E.m_path[((size_t)g * MLB + j) * LPG + sub] = my_path;
+#pragma unroll
+            for (int i = 0; i < MLB; ++i) vpath[i] = i == j ? my_path : vpath[i];
+            if (plen > LPG && sub == 0) atomicMax(E.max_path, plen);
+            int status = LS_NONE;
+            if (bad) { if (sub == 0) atomicOr(E.err, ERR_INTERNAL); }
+            else if (cur.flags & F_TERMINAL) { status = LS_TERM; w = cur.win; }
+            else if (az_status_grp(E.gd, b, &w, sub)) {  // mcts.py:185-186
+                status = LS_TERM;
+                if (sub == 0) { pool[node].flags = cur.flags | F_TERMINAL; pool[node].win = (int8_t)w; }
+            } else {
+                const u32 m = grp_ballot(sub < j && k_st == LS_EVAL && k_leaf == node);  // pending leaf of an earlier walker?
+                status = m ? LS_DUP + (__ffs((int)m) - 1) : LS_EVAL;
+                ndup += m ? 1 : 0;
+            }
+            if (sub == j) { k_st = status; k_leaf = node; k_p1 = b.p1; k_m1 = b.m1; k_pl = b.player; k_w = w; k_plen = plen; }
+            // flag stores of this walker (F_EXPANDED, F_TERMINAL, the noised priors) must be visible to the next walker's loads
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+        if (ndup > 0 && sub == 0) atomicAdd(&E.ctr[CTR_COLLISIONS], (unsigned long long)ndup);
+    }
+    __syncthreads();
+    int rank = 0;
+    if (k_st == LS_EVAL) rank = atomicAdd(&s_need, 1);  // LDS atomic, one per LS_EVAL walker
+    __syncthreads();
+    if (threadIdx.x == 0) s_base = s_need > 0 ? atomicAdd(E.batch_cnt + (t & 1), s_need) : 0;
+    __syncthreads();
+    const int k_row = s_base + rank;  // < K * G: at most one row per walker
+    for (int j = 0; j < kt; ++j) {
+        if (__shfl(k_st, j, LPG) == LS_EVAL) {
+            const BB bj = {(u64)__shfl((long long)k_p1, j, LPG), (u64)__shfl((long long)k_m1, j, LPG), __shfl(k_pl, j, LPG)};
+            write_nn_input_grp(E, __shfl(k_row, j, LPG), bj, sub);
+        }
+    }
+    if (in_range) {
+        E.m_leaf_status[wj] = (int8_t)k_st;
+        if (k_st != LS_NONE) {
+            E.m_leaf[wj] = k_leaf; E.m_leaf_p1[wj] = k_p1; E.m_leaf_m1[wj] = k_m1; E.m_leaf_player[wj] = (int8_t)k_pl;
+            E.m_leaf_winner[wj] = (int8_t)k_w; E.m_row[wj] = k_row; E.m_path_len[wj] = k_plen;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1125,7 +1366,7 @@ __global__ void k_root_status(EngDev E, int8_t *players, uint8_t *over, int8_t *
 // closed-form fake network (tests): reads the canonical board back from nn_in
 __global__ void k_fakenet(EngDev E, const int *cnt) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.G || g >= *cnt) return;
+    if (g >= E.G * E.K || g >= *cnt) return;
     const float *in = E.nn_in + (size_t)g * E.gd.cells;
     u64 h = 0x9E3779B97F4A7C15ULL;
     for (int i = 0; i < E.gd.cells; ++i) h = (h ^ (u64)((int)in[i] + 1)) * 0x100000001B3ULL;
@@ -1213,6 +1454,8 @@ struct az_engine {
     int sym_mask = 0, sym_n = 0, sym_rows = 0;
     float *sym_in = nullptr, *sym_p = nullptr, *sym_v = nullptr;
     int *sym_cnt = nullptr;  // sym_n * the pending count, written by k_sym_expand for az_net_forward_dyn
+    // az_engine_set_leaf_batch: walkers per slot and lock-step (1: k_step) and the rows nn_in / probs / value hold
+    int leaf_batch = 1, net_rows = 0;
 };
 
 int az_make_game_desc(int game, int H, int W, GameDesc *gd) {
@@ -1289,6 +1532,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.rollout = cfg->evaluator == AZ_EVAL_ROLLOUT ? 1 : 0;
     d.noise_mode = cfg->noise_mode; d.tmax = cfg->temp_max_step; d.tmin = cfg->temp_min_step; d.seed = cfg->seed;
     d.sample_cap = cfg->sample_capacity;
+    d.K = 1; e->net_rows = d.G;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -1299,7 +1543,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     A_(nn_in, G * gd.cells); A_(probs, G * gd.A); A_(value, G); A_(row_of_slot, G); A_(evals, G); A_(batch_cnt, 4);
     A_(samp_idx, G * (size_t)d.max_plies);
     A_(o_state, S * gd.cells); A_(o_pi, S * gd.A); A_(o_z, S); A_(o_meta, S * 4); A_(o_visits, S * gd.A);
-    A_(ctr, CTR_COUNT); A_(err, 1); A_(max_nodes, 1); A_(max_path, 1);
+    A_(ctr, CTR_ALLOC); A_(err, 1); A_(max_nodes, 1); A_(max_path, 1);
 #undef A_
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_a, G);
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_b, G);
@@ -1310,7 +1554,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
         if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_slots, G);
         if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_bad, 1);
     }
-    if (rc == AZ_OK && hipHostMalloc((void **)&e->h_ctr, sizeof(unsigned long long) * CTR_COUNT) != hipSuccess) rc = AZ_EHIP;
+    if (rc == AZ_OK && hipHostMalloc((void **)&e->h_ctr, sizeof(unsigned long long) * CTR_ALLOC) != hipSuccess) rc = AZ_EHIP;
     if (rc == AZ_OK && hipHostMalloc((void **)&e->h_err, sizeof(int) * 3) != hipSuccess) rc = AZ_EHIP;
     if (rc != AZ_OK) { az_engine_destroy(e); return rc; }
     if (hipStreamSynchronize(e->stream) != hipSuccess) { az_engine_destroy(e); az_set_error("stream sync failed"); return AZ_EHIP; }
@@ -1370,7 +1614,7 @@ static int forward(az_engine *e, const int *cnt, int cap, int step) {
     EngDev &d = e->d;
     if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return forward_external(e, cnt, cap, step);
     if (e->cfg.evaluator == AZ_EVAL_FAKE) {
-        hipLaunchKernelGGL(k_fakenet, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, cnt);
+        hipLaunchKernelGGL(k_fakenet, grid_for(d.G * d.K, TB), dim3(TB), 0, e->stream, d, cnt);
         return AZ_OK;
     }
     if (e->sym_mask == 0) return az_net_forward_dyn(e->net, d.nn_in, cnt, cap, d.probs, d.value, e->stream);
@@ -1394,6 +1638,18 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
     hipLaunchKernelGGL(k_root_prep, gg, gb, 0, e->stream, d, 0, d.G);
     AZ_TRY(forward(e, d.batch_cnt + 2, cap, -1));
     hipLaunchKernelGGL(k_root_init, gg, gb, 0, e->stream, d, 0, d.G);
+    if (d.K > 1) {  // ceil(n_sim / K) lock-steps of up to K walkers per slot (k_step_multi), then the backup of the last ones
+        const int K = d.K, L = (n_sim + K - 1) / K;
+        for (int t = 0; t < L; ++t) {
+            const int kt = n_sim - t * K < K ? n_sim - t * K : K;
+            if (t == 0) hipLaunchKernelGGL((k_step_multi<false, true>), gg, gb, 0, e->stream, d, t, 0, kt);
+            else hipLaunchKernelGGL((k_step_multi<true, true>), gg, gb, 0, e->stream, d, t, K, kt);
+            AZ_TRY(forward(e, d.batch_cnt + (t & 1), cap, t));
+        }
+        hipLaunchKernelGGL((k_step_multi<true, false>), gg, gb, 0, e->stream, d, L, n_sim - (L - 1) * K, 0);
+        AZ_HIP(hipGetLastError());
+        return AZ_OK;
+    }
     for (int s = 0; s < n_sim; ++s) {
         if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
         else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
@@ -1409,15 +1665,17 @@ static int do_search(az_engine *e, int n_sim) {
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL || e->ext_fn, AZ_ESTATE, "AZ_EVAL_EXTERNAL engine without an evaluator (az_engine_set_evaluator)");
     d.sim_base = e->sim_base;
     e->sim_base += (u32)n_sim;
-    e->lockstep_iters += d.rollout ? n_sim : n_sim + 1;
-    int cap = e->active_bound > 0 && e->active_bound < d.G ? e->active_bound : d.G;
+    e->lockstep_iters += d.rollout ? n_sim : (n_sim + d.K - 1) / d.K + 1;
+    // network rows: every searching slot brings up to K leaves per lock-step (K = 1 unless az_engine_set_leaf_batch)
+    const int R = d.G * d.K;
+    int cap = (e->active_bound > 0 && e->active_bound < d.G ? e->active_bound : d.G) * d.K;
     // graph replay needs launch parameters that do not change from search to search: the Philox counter base must be 0
     // (one search per root, as in self-play and the arena), no per-launch event recording, and a quantised batch cap
     const bool graphable = e->graphs_ok && d.sim_base == 0 && !(e->net && az_net_profiling(e->net)) && e->cfg.evaluator != AZ_EVAL_EXTERNAL;
     // the quantised cap of the graph path also when the search runs as plain launches under az_net_profile: the profiled step then
     // launches the kernels the timed (graph-replayed) steps launch (an exact cap of 4095 -- one game of 4096 over, as happens from
     // ply ~11 on: Othello has early wipe-outs -- would hand the trunk to the one-board-per-wave kernel for the rest of the wave)
-    const int cap_q = (d.G >= 4096 && cap < 4096) ? (cap + 511) / 512 * 512 : d.G;  // below 4096 rows the network picks other kernels
+    const int cap_q = (R >= 4096 && cap < 4096) ? (cap + 511) / 512 * 512 : R;  // below 4096 rows the network picks other kernels
     if (!graphable) return enqueue_search(e, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
     cap = cap_q;
     const unsigned long long key = ((unsigned long long)n_sim << 32) | (unsigned)cap;
@@ -1465,7 +1723,7 @@ static int reset_external(az_engine *e) {
 }
 
 static int fetch_counters(az_engine *e) {
-    AZ_HIP(hipMemcpyAsync(e->h_ctr, e->d.ctr, sizeof(unsigned long long) * CTR_COUNT, hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipMemcpyAsync(e->h_ctr, e->d.ctr, sizeof(unsigned long long) * CTR_ALLOC, hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipMemcpyAsync(&e->h_err[0], e->d.err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipMemcpyAsync(&e->h_err[1], e->d.max_nodes, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipMemcpyAsync(&e->h_err[2], e->d.max_path, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -1848,6 +2106,7 @@ extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
                e->cfg.evaluator);
     int n = 0;
     AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
+    AZ_REQUIRE(mask == 0 || e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with leaf_batch %d > 1 (az_engine_set_leaf_batch)", e->leaf_batch);
     AZ_REQUIRE((long long)n * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "%d symmetries of %d slots are %lld rows, the network's max_batch is %d", n, d.G, (long long)n * d.G, az_net_max_batch(e->net));
     if (mask == e->sym_mask) return AZ_OK;
@@ -1877,5 +2136,52 @@ extern "C" int az_engine_set_evaluator(az_engine *e, az_eval_fn fn, void *user) 
     AZ_USABLE(e, "az_engine_set_evaluator");
     e->ext_fn = fn;
     e->ext_user = user;
+    return AZ_OK;
+}
+
+// ---- several leaves per slot and lock-step, kept apart by virtual loss (k_step_multi) --------------------------------
+extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_leaf_batch");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_leaf_batch");
+    EngDev &d = e->d;
+    AZ_REQUIRE(k >= 1 && k <= AZ_MAX_LEAF_BATCH, AZ_EINVAL, "leaf_batch must be in [1, %d], got %d", AZ_MAX_LEAF_BATCH, k);
+    AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_leaf_batch: an AZ_EVAL_EXTERNAL engine searches one leaf per lock-step (external evaluator)");
+    AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_ROLLOUT, AZ_EINVAL, "az_engine_set_leaf_batch: a rollout engine (AZ_EVAL_ROLLOUT) evaluates no leaf with a network");
+    AZ_REQUIRE(e->sym_mask == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the engine evaluates over a symmetry mask (0x%x); the ensemble does not combine with leaf_batch", e->sym_mask);
+    const long long rows = (long long)k * d.G;
+    if (e->cfg.evaluator == AZ_EVAL_NET)
+        AZ_REQUIRE(rows <= az_net_max_batch(e->net), AZ_EINVAL, "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", k, d.G,
+                   rows, az_net_max_batch(e->net));
+    if (k == e->leaf_batch) return AZ_OK;
+    AZ_TRY(enter(e));
+    if (k > 1 && !d.m_leaf) {  // the walkers' pending leaves, at the first k > 1
+        const size_t W = (size_t)d.G * MLB;
+        AZ_TRY(dev_alloc(e, &d.m_leaf, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_p1, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_m1, W));
+        AZ_TRY(dev_alloc(e, &d.m_leaf_player, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_status, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_winner, W));
+        AZ_TRY(dev_alloc(e, &d.m_row, W)); AZ_TRY(dev_alloc(e, &d.m_path, W * LPG)); AZ_TRY(dev_alloc(e, &d.m_path_len, W));
+    }
+    if (rows > e->net_rows) {  // K * G rows for the network (the smaller buffers stay allocated until the engine goes: e->allocs)
+        AZ_TRY(dev_alloc(e, &d.nn_in, (size_t)rows * d.gd.cells));
+        AZ_TRY(dev_alloc(e, &d.probs, (size_t)rows * d.A));
+        AZ_TRY(dev_alloc(e, &d.value, (size_t)rows));
+        e->net_rows = (int)rows;
+    }
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    e->leaf_batch = k; d.K = k;
+    // the launch sequence of a search changes: nothing captured before may be replayed
+    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
+    e->graphs.clear();
+    e->graph_seen.clear();
+    return AZ_OK;
+}
+
+extern "C" int az_engine_collisions(az_engine *e, int64_t *n) {
+    AZ_REQUIRE(e && n, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_collisions");
+    AZ_USABLE(e, "az_engine_collisions");
+    AZ_TRY(enter(e));
+    AZ_TRY(fetch_counters(e));
+    *n = (int64_t)e->h_ctr[CTR_COLLISIONS];
     return AZ_OK;
 }

@@ -317,6 +317,17 @@ class SelfPlayEngine:
         from .symmetry import resolve
         check(lib().az_engine_set_symmetry(self.h, resolve(symmetry)))
 
+    def set_leaf_batch(self, k):
+        """k simulations per slot and lock-step, kept apart by virtual loss (az_engine_set_leaf_batch; 1: the plain search, the
+        default).  EVAL_NET / EVAL_FAKE engines without a symmetry ensemble; the network needs max_batch >= k * n_slots."""
+        check(lib().az_engine_set_leaf_batch(self.h, int(k)))
+
+    def collisions(self):
+        """walkers that landed on the pending leaf of an earlier walker of their lock-step, since the engine was created"""
+        n = C.c_int64()
+        check(lib().az_engine_collisions(self.h, C.byref(n)))
+        return n.value
+
     def run(self, n_games, first_game_id=0):
         """plays n_games to completion; returns the samples as a dict of CUDA tensors (copies)."""
         self._evaluated(lib().az_engine_run(self.h, first_game_id, n_games))

@@ -53,8 +53,37 @@ def check_symmetry(symmetry, nn):
     return mask
 
 
+MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
+
+
+def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
+    """the walkers per lock-step of `leaf_batch` (None: 1); ValueError -- before any device work -- for a bool, a non-integer or a
+    value outside 1..16, and for a value above 1 with a network evaluated through an external evaluator (evaluators.route), a
+    rollout-mode tree (`neural` False) or a symmetry ensemble: virtual-loss batching runs on the HIP network's plain evaluation only"""
+    if leaf_batch is None:
+        return 1
+    if isinstance(leaf_batch, (bool, np.bool_)) or not isinstance(leaf_batch, (int, np.integer)):
+        raise ValueError(f"leaf_batch must be an integer in 1..{MAX_LEAF_BATCH}, got {leaf_batch!r}")
+    k = int(leaf_batch)
+    if not 1 <= k <= MAX_LEAF_BATCH:
+        raise ValueError(f"leaf_batch must be in 1..{MAX_LEAF_BATCH}, got {k}")
+    if k > 1:
+        if not neural:
+            raise ValueError(f"leaf_batch={k} needs eval_method 'neural': random playouts evaluate no leaf with a network")
+        if nn is not None:
+            from .evaluators import route
+            if route(nn) != "hip":
+                raise ValueError(f"leaf_batch={k} needs a network the HIP network serves; {type(nn).__name__} evaluates its leaves "
+                                 f"through an external evaluator, which takes one leaf per lock-step")
+        from .symmetry import resolve
+        if resolve(symmetry) != 0:
+            raise ValueError(f"leaf_batch={k} does not combine with symmetry={symmetry!r}")
+    return k
+
+
 class MCT:
-    def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None):
+    def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None,
+                 leaf_batch=None):
         self.n_rollouts = 0
         self.simulation_time = 0
         self.eval_method = TreeEval.to_dict()["rollout" if eval_method is None else eval_method]
@@ -66,6 +95,7 @@ class MCT:
         self._seed = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         self._engine = None           # device tree (one engine slot)
         self._engine_board = None     # (game, H, W) the engine was built for
+        self._engine_lb = 1           # the leaf_batch the engine is set to
         self._hipnet = None
         self._evaluator = None        # external evaluator of a network the HIP net does not serve (evaluators.route)
         self._root_key = None         # (grid bytes, player) of the position the device root stands for
@@ -75,6 +105,9 @@ class MCT:
         # leaf evaluations averaged over the board's symmetries (alphazero_amd.symmetry; None: off); HIP-routed networks only
         self.symmetry = symmetry
         check_symmetry(symmetry, self._nn)
+        # simulations per lock-step, kept apart by virtual loss (None / 1: the reference's sequential search); HIP-routed networks only
+        self.leaf_batch = leaf_batch
+        check_leaf_batch(leaf_batch, self._nn, symmetry, self.eval_method == TreeEval.NEURAL)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -86,6 +119,7 @@ class MCT:
         if self.eval_method != TreeEval.NEURAL:
             raise ValueError(f"Trying to set a neural network for the MCT but the evaluation method is {self.eval_method}")
         check_symmetry(self.symmetry, nn)
+        check_leaf_batch(self.leaf_batch, nn, self.symmetry)
         self._nn = nn
         self._hipnet = None
         self._evaluator = None
@@ -106,7 +140,8 @@ class MCT:
             self._device_search(n_sim)
             self.n_rollouts = n_sim
         else:
-            chunk = 1 if self.eval_method == TreeEval.NEURAL else 8
+            # one lock-step per chunk: a simulation, or leaf_batch of them
+            chunk = check_leaf_batch(self.leaf_batch, None) if self.eval_method == TreeEval.NEURAL else 8
             while time() - start < compute_time:
                 self._ensure_room(chunk)
                 self._device_search(chunk)
@@ -179,8 +214,9 @@ class MCT:
             sym = members(board.game, H, W, check_symmetry(self.symmetry, self._nn if neural else None))
             if sym and not neural:
                 raise ValueError("symmetry needs eval_method 'neural': random playouts evaluate no leaf")
+            check_leaf_batch(self.leaf_batch, self._nn if neural else None, self.symmetry, neural)
             if neural and not external and self._hipnet is None:
-                self._hipnet = self._nn.to_hip(max_batch=16)  # >= the 8 twins of the one slot
+                self._hipnet = self._nn.to_hip(max_batch=16)  # >= the 8 twins / the 16 walkers of the one slot
             noisy = self.dirichlet_alpha is not None and self.dirichlet_epsilon is not None
             self._engine = SelfPlayEngine(_GAME_IDS[board.game], H, W, n_slots=1, n_sim=1, net=None if external else self._hipnet,
                                           dirichlet_alpha=self.dirichlet_alpha, dirichlet_epsilon=self.dirichlet_epsilon,
@@ -197,6 +233,11 @@ class MCT:
                 self._engine.set_symmetry(sym)
             self._engine_board = (board.game, H, W)
             self._plies = 0
+            self._engine_lb = 1
+        lb = check_leaf_batch(self.leaf_batch, self._nn if neural else None, self.symmetry, neural)
+        if self._engine_lb != lb:
+            self._engine.set_leaf_batch(lb)
+            self._engine_lb = lb
         key = (board.grid.astype(np.int8).tobytes(), int(board.player))
         if key != self._root_key:  # tree restarted from an unexplored state (mcts.py:124-125, 231-233)
             self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8),

@@ -7,7 +7,7 @@ from time import sleep
 import numpy as np
 
 from .base import Player
-from .mcts import MCT, _action_of, _move_of, check_symmetry
+from .mcts import MCT, _action_of, _move_of, check_leaf_batch, check_symmetry
 from .utils import fair_max
 
 
@@ -57,7 +57,7 @@ class MCTSPlayer(Player):
         old = self.mct
         self.mct = MCT()
         # a reset drops the tree, not the device storage behind it (one engine slot: node pools, sample buffers)
-        self.mct._engine, self.mct._engine_board = old._engine, old._engine_board
+        self.mct._engine, self.mct._engine_board, self.mct._engine_lb = old._engine, old._engine_board, old._engine_lb
 
     def apply_move(self, move, player=None):
         self.mct.change_root(move)
@@ -81,28 +81,34 @@ class MCTSPlayer(Player):
 
 class AlphaZeroPlayer(MCTSPlayer):
     def __init__(self, n_sim=None, compute_time=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, verbose=False,
-                 symmetry=None):
+                 symmetry=None, leaf_batch=None):
         super().__init__(n_sim=n_sim, compute_time=compute_time, verbose=verbose)
         self.mct = MCT(eval_method="neural", nn=nn, dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
-                       symmetry=symmetry)
+                       symmetry=symmetry, leaf_batch=leaf_batch)
 
     @property
     def symmetry(self):
         """the symmetries every leaf evaluation is averaged over (alphazero_amd.symmetry; None: off)"""
         return self.mct.symmetry
 
+    @property
+    def leaf_batch(self):
+        """simulations per lock-step, kept apart by virtual loss (None / 1: the sequential search)"""
+        return self.mct.leaf_batch
+
     def clone(self):
         return AlphaZeroPlayer(n_sim=self.n_sim, compute_time=self.compute_time,
                                nn=self.mct.nn.clone() if self.mct.nn is not None else None,
                                dirichlet_alpha=self.mct.dirichlet_alpha, dirichlet_epsilon=self.mct.dirichlet_epsilon,
-                               verbose=self.verbose, symmetry=self.mct.symmetry)
+                               verbose=self.verbose, symmetry=self.mct.symmetry, leaf_batch=self.mct.leaf_batch)
 
     def reset(self):
         old = self.mct
         self.mct = MCT(eval_method="neural", nn=old.nn, dirichlet_alpha=old.dirichlet_alpha,
-                       dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry)
+                       dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry, leaf_batch=old.leaf_batch)
         # keep the uploaded weights and the device tree storage: a reset only drops the tree
         self.mct._hipnet, self.mct._engine, self.mct._engine_board = old._hipnet, old._engine, old._engine_board
+        self.mct._engine_lb = old._engine_lb
         self.mct._evaluator = old._evaluator  # the carried engine calls it (external evaluation, evaluators.route)
         if self.mct._engine is not None:
             self.mct._plies = 0
@@ -128,7 +134,7 @@ class BatchedMCTSPlayer(Player):
         if int(n_slots) < 1:
             raise ValueError("n_slots must be a positive integer")
         self.n_sim, self.n_slots = int(n_sim), int(n_slots)
-        self.nn, self.dirichlet_alpha, self.dirichlet_epsilon, self.symmetry = None, None, None, None
+        self.nn, self.dirichlet_alpha, self.dirichlet_epsilon, self.symmetry, self.leaf_batch = None, None, None, None, None
         self._seed = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         self._engine = None           # n_slots device trees
         self._engine_board = None     # (game, H, W) the engine was built for
@@ -190,8 +196,10 @@ class BatchedMCTSPlayer(Player):
         neural = self._eval_method == "neural"
         external = neural and route(self.nn) != "hip"  # evaluates the leaves itself, as in BatchedArena._engine
         sym = members(first.game, H, W, check_symmetry(self.symmetry, self.nn if neural else None))
+        lb = check_leaf_batch(self.leaf_batch, self.nn if neural else None, self.symmetry, neural)
         if neural and not external:
-            self._hipnet = self.nn.to_hip(max_batch=max(1, len(sym)) * self.n_slots)  # every slot's leaf in each of its twins
+            # every slot's leaf in each of its twins, or every slot's leaf_batch walkers
+            self._hipnet = self.nn.to_hip(max_batch=max(1, len(sym), lb) * self.n_slots)
         noisy = self.dirichlet_alpha is not None and self.dirichlet_epsilon is not None
         self._engine = SelfPlayEngine(GAME_IDS[first.game], H, W, n_slots=self.n_slots, n_sim=self.n_sim,
                                       net=self._hipnet if neural and not external else None,
@@ -205,6 +213,8 @@ class BatchedMCTSPlayer(Player):
             self._engine.set_evaluator(self._evaluator)
         if sym:
             self._engine.set_symmetry(sym)
+        if lb > 1:
+            self._engine.set_leaf_batch(lb)
         self._engine_board = (first.game, H, W)
 
     def _sync(self, boards, first):
@@ -299,12 +309,15 @@ class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
     _eval_method = "neural"
 
     def __init__(self, n_sim=None, nn=None, n_slots=1, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, verbose=False,
-                 symmetry=None):
+                 symmetry=None, leaf_batch=None):
         super().__init__(n_sim=n_sim, n_slots=n_slots, seed=seed, verbose=verbose)
         self.nn, self.dirichlet_alpha, self.dirichlet_epsilon = nn, dirichlet_alpha, dirichlet_epsilon
         # leaf evaluations averaged over the board's symmetries (alphazero_amd.symmetry; None: off); HIP-routed networks only
         self.symmetry = symmetry
         check_symmetry(symmetry, nn)
+        # simulations per lock-step and game, kept apart by virtual loss (None / 1: the sequential search); HIP-routed networks only
+        self.leaf_batch = leaf_batch
+        check_leaf_batch(leaf_batch, nn, symmetry)
 
 
 PLAYERS_SET = {"human", "random", "greedy", "mcts", "alphazero"}

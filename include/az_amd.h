@@ -241,6 +241,25 @@ int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h_over, int8
  * an engine whose evaluator is not AZ_EVAL_NET, a net with max_batch < n * n_slots; AZ_ESTATE while a search is open. */
 int az_engine_set_symmetry(az_engine *e, int32_t mask);
 
+/* Several leaves per slot and lock-step, kept apart by virtual loss.  The reference searches strictly one simulation after the
+ * other (mcts.py:127-171 select_node, 197-223 back_propagate, 254-262 the loop of MCT.search); with leaf_batch = K > 1 a search of
+ * n_sim simulations is ceil(n_sim / K) lock-steps, each walking up to K simulations ("walkers") per slot before ONE network call
+ * on up to K * n_slots rows.  Walker j scores a child c of parent p as if every walker i < j of the same lock-step had already
+ * lost through the nodes of its path: with v(x) = the number of those walkers whose path holds x,
+ *   Q term  v(c) == 0 ? c.Q : (c.N * c.Q - v(c)) / (c.N + v(c)),     U term  c.P * sqrt(p.N + v(p)) / (1 + c.N + v(c))
+ * in float64, one operation at a time.  Nothing virtual is stored: after the search the trees hold real statistics only and every
+ * root has grown by exactly n_sim visits.  A walker that lands on the still unevaluated leaf of an earlier walker of its lock-step
+ * (a collision) takes no network row and backs up that walker's value; az_engine_collisions counts them since the engine was
+ * created.  This is a different search from the reference's: opt-in, default 1, and at 1 the launch sequence and every bit are
+ * the plain ones.  For K > 1 the result depends on how simulations are split over search calls (search(3); search(5) walks
+ * [3] [4,1], search(8) walks [4,4]); it still depends on nothing but (seed, game id, K) otherwise.  net_evals counts rows.
+ * AZ_EINVAL: k outside [1, AZ_MAX_LEAF_BATCH], an AZ_EVAL_EXTERNAL or AZ_EVAL_ROLLOUT engine, k * n_slots beyond the network's
+ * max_batch, a symmetry mask in force (and az_engine_set_symmetry refuses a mask while k > 1); AZ_ESTATE while a search is open
+ * or from inside an evaluator.  The engine's cached search graphs are dropped. */
+#define AZ_MAX_LEAF_BATCH 16
+int az_engine_set_leaf_batch(az_engine *e, int32_t k);
+int az_engine_collisions(az_engine *e, int64_t *n);
+
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
  * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves
