@@ -1416,6 +1416,56 @@ __global__ __launch_bounds__(256) void k_ext_check(EngDev E, const int *cnt, con
     if (bad) { atomicOr(E.err, ERR_EVAL); atomicMin(bad_slot, slots[row]); }
 }
 
+// ---- one randomly drawn board symmetry per evaluation (az_engine_set_symmetry_random) ----------------------------
+// Every pending row is evaluated in ONE member of the candidate mask.  members = the mask's codes in ascending order, n of them:
+//   r = az_philox(seed, game_id[slot], ply[slot], s, AZ_P_SYMMETRY, 0),  m = (u32)(((u64)r.x * n) >> 32),  code = members[m]
+// s = (u32)(sim + sim_base) for the leaf of simulation sim (leaf_batch K: walker j of lock-step t has sim = t * K + j, k_step_multi's
+// own index), 0xFFFFFFFF for the root-prior pass; ply is the root's.  A function of the game alone: never of the slot, the row, the
+// batch shape or the GPU.  The kernel is slot-major (only the slot knows its game id and ply) with the pending predicate and the
+// row of k_ext_export; slots that do not search hold root_fresh 0 (k_root_prep), LS_NONE (k_step) and LS_NONE for every walker
+// (k_step_multi) -- all three are written for every slot of the engine, arena mode (az_engine_set_sides) included.  It writes the
+// twin of nn_in[row] to sym_in[row] (out of place) and the code to sym_code[row]; k_sym_unpick (az_symmetry.hip) maps the network's
+// answer back.  No barrier: groups without a pending row leave at once.
+#define AZ_P_SYMMETRY 8
+#define SYM_ROOT_PASS 0xFFFFFFFFu
+
+AZ_D int sym_draw(const EngDev &E, int g, u32 ply, u32 s, int mask, int n) {
+    const Philox4 r = az_philox(E.seed, E.game_id[g], ply, s, AZ_P_SYMMETRY, 0);
+    return kth_set_bit((u32)mask, (int)(((u64)r.x * (u64)n) >> 32));
+}
+
+AZ_D void sym_pick_row_grp(const EngDev &E, int row, int code, float *sym_in, uint8_t *sym_code, int sub) {
+    const float *src = E.nn_in + (size_t)row * E.gd.cells;
+    float *dst = sym_in + (size_t)row * E.gd.cells;
+    for (int i = sub; i < E.gd.cells; i += LPG) {
+        int rr, cc;
+        aug_source(code, E.gd.H, E.gd.W, i / E.gd.W, i % E.gd.W, &rr, &cc);
+        dst[i] = src[rr * E.gd.W + cc];
+    }
+    if (sub == 0) sym_code[row] = (uint8_t)code;
+}
+
+// step: -1 the root-prior pass; K == 1: the simulation index k_step was launched with; K > 1: the lock-step t of k_step_multi and its kt
+__global__ __launch_bounds__(256) void k_sym_pick(EngDev E, int mask, int n, int step, int kt, float *sym_in, uint8_t *sym_code) {
+    const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (g >= E.G) return;
+    if (step < 0 || E.K == 1) {
+        if (step < 0 ? !E.root_fresh[g] : E.leaf_status[g] != LS_EVAL) return;
+        const int code = sym_draw(E, g, (u32)E.ply[g], step < 0 ? SYM_ROOT_PASS : (u32)step + E.sim_base, mask, n);
+        sym_pick_row_grp(E, E.row_of_slot[g], code, sym_in, sym_code, sub);
+        return;
+    }
+    // lane j: walker j's status, row and draw; the rows are then permuted one after the other by the whole group
+    const size_t wj = (size_t)g * MLB + sub;
+    const bool mine = sub < kt && E.m_leaf_status[wj] == LS_EVAL;
+    const int my_row = mine ? E.m_row[wj] : -1;
+    const int my_code = mine ? sym_draw(E, g, (u32)E.ply[g], (u32)(step * E.K + sub) + E.sim_base, mask, n) : 0;
+    for (int j = 0; j < kt; ++j) {
+        const int row = __shfl(my_row, j, LPG), code = __shfl(my_code, j, LPG);
+        if (row >= 0) sym_pick_row_grp(E, row, code, sym_in, sym_code, sub);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -1454,6 +1504,10 @@ struct az_engine {
     int sym_mask = 0, sym_n = 0, sym_rows = 0;
     float *sym_in = nullptr, *sym_p = nullptr, *sym_v = nullptr;
     int *sym_cnt = nullptr;  // sym_n * the pending count, written by k_sym_expand for az_net_forward_dyn
+    // az_engine_set_symmetry_random: the candidate codes one of which is drawn per evaluation (0: off; never together with sym_mask)
+    // and the code of every pending row, [sym_rows] bytes; the twins and their outputs use sym_in / sym_p / sym_v, K * G rows
+    int symr_mask = 0, symr_n = 0;
+    uint8_t *sym_code = nullptr;
     // az_engine_set_leaf_batch: walkers per slot and lock-step (1: k_step) and the rows nn_in / probs / value hold
     int leaf_batch = 1, net_rows = 0;
 };
@@ -1610,12 +1664,19 @@ static int forward_external(az_engine *e, const int *cnt, int cap, int step) {
 }
 
 // network over the compacted leaf rows [0, *cnt)
-static int forward(az_engine *e, const int *cnt, int cap, int step) {
+static int forward(az_engine *e, const int *cnt, int cap, int step, int kt = 0) {
     EngDev &d = e->d;
     if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return forward_external(e, cnt, cap, step);
     if (e->cfg.evaluator == AZ_EVAL_FAKE) {
         hipLaunchKernelGGL(k_fakenet, grid_for(d.G * d.K, TB), dim3(TB), 0, e->stream, d, cnt);
         return AZ_OK;
+    }
+    if (e->symr_mask != 0) {  // one drawn member per pending row: twin -> the network on the same rows -> mapped back (copies)
+        hipLaunchKernelGGL(k_sym_pick, dim3((unsigned)((d.G + GPB - 1) / GPB)), dim3(256), 0, e->stream, d, e->symr_mask, e->symr_n, step, kt, e->sym_in,
+                           e->sym_code);
+        AZ_HIP(hipGetLastError());
+        AZ_TRY(az_net_forward_dyn(e->net, e->sym_in, cnt, cap, e->sym_p, e->sym_v, e->stream));
+        return az_sym_unpick(&d.gd, e->sym_code, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
     }
     if (e->sym_mask == 0) return az_net_forward_dyn(e->net, d.nn_in, cnt, cap, d.probs, d.value, e->stream);
     // ensemble over the board's symmetries: twins of the pending rows -> the network on sym_n * count rows -> mapped back and averaged
@@ -1644,7 +1705,7 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
             const int kt = n_sim - t * K < K ? n_sim - t * K : K;
             if (t == 0) hipLaunchKernelGGL((k_step_multi<false, true>), gg, gb, 0, e->stream, d, t, 0, kt);
             else hipLaunchKernelGGL((k_step_multi<true, true>), gg, gb, 0, e->stream, d, t, K, kt);
-            AZ_TRY(forward(e, d.batch_cnt + (t & 1), cap, t));
+            AZ_TRY(forward(e, d.batch_cnt + (t & 1), cap, t, kt));
         }
         hipLaunchKernelGGL((k_step_multi<true, false>), gg, gb, 0, e->stream, d, L, n_sim - (L - 1) * K, 0);
         AZ_HIP(hipGetLastError());
@@ -2097,6 +2158,26 @@ extern "C" int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h
 }
 
 // ---- leaf evaluation over the board's symmetries (az_symmetry.hip; forward() above) --------------------------
+// the scratch rows of both symmetry modes (twins, their outputs, the per-row codes); smaller ones stay allocated until the engine goes
+static int sym_reserve(az_engine *e, int rows) {
+    EngDev &d = e->d;
+    if (rows <= e->sym_rows) return AZ_OK;
+    AZ_TRY(dev_alloc(e, &e->sym_in, (size_t)rows * d.gd.cells));
+    AZ_TRY(dev_alloc(e, &e->sym_p, (size_t)rows * d.A));
+    AZ_TRY(dev_alloc(e, &e->sym_v, (size_t)rows));
+    AZ_TRY(dev_alloc(e, &e->sym_code, (size_t)rows));
+    if (!e->sym_cnt) AZ_TRY(dev_alloc(e, &e->sym_cnt, 1));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    e->sym_rows = rows;
+    return AZ_OK;
+}
+
+static void drop_graphs(az_engine *e) {
+    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
+    e->graphs.clear();
+    e->graph_seen.clear();
+}
+
 extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
     AZ_REQUIRE(e, AZ_EINVAL, "null engine");
     AZ_NO_OPEN_SEARCH(e, "az_engine_set_symmetry");
@@ -2106,25 +2187,37 @@ extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
                e->cfg.evaluator);
     int n = 0;
     AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
+    AZ_REQUIRE(mask == 0 || e->symr_mask == 0, AZ_EINVAL, "az_engine_set_symmetry: the engine draws one symmetry per evaluation (az_engine_set_symmetry_random, mask 0x%x); switch that mode off first", (unsigned)e->symr_mask);
     AZ_REQUIRE(mask == 0 || e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with leaf_batch %d > 1 (az_engine_set_leaf_batch)", e->leaf_batch);
     AZ_REQUIRE((long long)n * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "%d symmetries of %d slots are %lld rows, the network's max_batch is %d", n, d.G, (long long)n * d.G, az_net_max_batch(e->net));
     if (mask == e->sym_mask) return AZ_OK;
     AZ_TRY(enter(e));
-    const int rows = n * d.G;
-    if (rows > e->sym_rows) {  // the rows of a smaller mask stay allocated until the engine goes (e->allocs)
-        AZ_TRY(dev_alloc(e, &e->sym_in, (size_t)rows * d.gd.cells));
-        AZ_TRY(dev_alloc(e, &e->sym_p, (size_t)rows * d.A));
-        AZ_TRY(dev_alloc(e, &e->sym_v, (size_t)rows));
-        if (!e->sym_cnt) AZ_TRY(dev_alloc(e, &e->sym_cnt, 1));
-        AZ_HIP(hipStreamSynchronize(e->stream));
-        e->sym_rows = rows;
-    }
+    AZ_TRY(sym_reserve(e, n * d.G));
     e->sym_mask = mask; e->sym_n = n;
     // the launch sequence of a search changes: nothing captured before may be replayed
-    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-    e->graphs.clear();
-    e->graph_seen.clear();
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+// one member of `mask`, drawn per evaluation (k_sym_pick above): the rows of the plain search, so it composes with leaf_batch
+extern "C" int az_engine_set_symmetry_random(az_engine *e, int32_t mask) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_symmetry_random");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_symmetry_random");
+    EngDev &d = e->d;
+    AZ_REQUIRE(e->cfg.evaluator == AZ_EVAL_NET, AZ_EINVAL, "az_engine_set_symmetry_random needs an engine created with evaluator = AZ_EVAL_NET (this one: %d)",
+               e->cfg.evaluator);
+    int n = 0;
+    AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
+    AZ_REQUIRE(mask == 0 || e->sym_mask == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the engine averages over a symmetry mask (az_engine_set_symmetry, mask 0x%x); switch the ensemble off first", (unsigned)e->sym_mask);
+    AZ_REQUIRE((long long)e->leaf_batch * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
+               "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", e->leaf_batch, d.G, (long long)e->leaf_batch * d.G, az_net_max_batch(e->net));
+    if (mask == e->symr_mask) return AZ_OK;
+    AZ_TRY(enter(e));
+    if (mask != 0) AZ_TRY(sym_reserve(e, e->leaf_batch * d.G));
+    e->symr_mask = mask; e->symr_n = n;
+    drop_graphs(e);
     return AZ_OK;
 }
 
@@ -2167,12 +2260,11 @@ extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
         AZ_TRY(dev_alloc(e, &d.value, (size_t)rows));
         e->net_rows = (int)rows;
     }
+    if (e->symr_mask != 0) AZ_TRY(sym_reserve(e, (int)rows));  // the twins of the random symmetry mode follow K * G
     AZ_HIP(hipStreamSynchronize(e->stream));
     e->leaf_batch = k; d.K = k;
     // the launch sequence of a search changes: nothing captured before may be replayed
-    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-    e->graphs.clear();
-    e->graph_seen.clear();
+    drop_graphs(e);
     return AZ_OK;
 }
 

@@ -40,6 +40,11 @@ int az_sym_expand(const GameDesc *gd, int32_t mask, const float *d_in, const int
 // the n member outputs of every row, mapped back and averaged (float32, member order) into d_probs / d_value rows [0, rows)
 int az_sym_reduce(const GameDesc *gd, int32_t mask, const float *d_p, const float *d_v, const int32_t *d_count, int B, float *d_probs,
                   float *d_value, hipStream_t st);
+// one member per row, d_codes[r] its transform code (trusted: a code the board does not have is read as the identity): the twin of
+// rows [0, min(*d_count, B)) of d_in, and the twins' outputs gathered back through the inverse code (copies only)
+int az_sym_twin(const GameDesc *gd, const uint8_t *d_codes, const float *d_in, const int32_t *d_count, int B, float *d_out, hipStream_t st);
+int az_sym_unpick(const GameDesc *gd, const uint8_t *d_codes, const float *d_p, const float *d_v, const int32_t *d_count, int B, float *d_probs,
+                  float *d_value, hipStream_t st);
 // az_net.hip: what az_symmetry.hip needs of a network
 struct az_net;
 int az_net_max_batch(const az_net *net);

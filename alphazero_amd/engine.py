@@ -166,6 +166,26 @@ class HipNet:
         check(lib().az_net_forward_sym(self.h, x.data_ptr(), B, resolve(symmetry), probs.data_ptr(), v.data_ptr(), _stream_ptr()))
         return probs, v
 
+    def forward_sym_codes(self, x, codes):
+        """forward() with row r evaluated in the one orientation codes[r] (az_net_forward_sym_codes): the row's twin goes through
+        the network and its policy is mapped back, copies only.  `codes`: one transform code per row (alphazero_amd.symmetry), a
+        sequence, numpy array or tensor; a code the board does not have is a ValueError."""
+        from .symmetry import members
+        x = x.contiguous().view(-1, self.H * self.W)
+        assert x.is_cuda and x.dtype == torch.float32
+        B = x.shape[0]
+        c = torch.as_tensor(codes).reshape(-1)
+        if c.dtype.is_floating_point or c.dtype == torch.bool or c.numel() != B:
+            raise ValueError(f"codes: {B} integer transform codes expected, one per row")
+        if B and (int(c.min()) < 0 or int(c.max()) > 7):
+            raise ValueError("codes: transform codes are the integers 0..7")
+        members({v: k for k, v in GAME_IDS.items()}[self.game_id], self.H, self.W, sorted(set(c.tolist())))  # ValueError: not this board's
+        c = c.to(device=x.device, dtype=torch.uint8).contiguous()
+        probs = torch.empty((B, self.A), dtype=torch.float32, device=x.device)
+        v = torch.empty(B, dtype=torch.float32, device=x.device)
+        check(lib().az_net_forward_sym_codes(self.h, x.data_ptr(), B, c.data_ptr(), probs.data_ptr(), v.data_ptr(), _stream_ptr()))
+        return probs, v
+
     def flops_per_board(self):
         return int(lib().az_net_flops_per_board(self.h))
 
@@ -254,6 +274,7 @@ class SelfPlayEngine:
         self._eval_exc = None    # an exception the evaluator raised, re-raised by the engine call that ran it
         self._eval_views = {}    # device pointer -> full-size view (the rows are sliced per call)
         self._eval_streams = {}
+        self._sym_mode = None    # which symmetry mode set_symmetry last put in force: None, "ensemble" or "random"
 
     # ---------------------------------------------------------------------------------------- external evaluator
     def set_evaluator(self, fn):
@@ -313,13 +334,28 @@ class SelfPlayEngine:
 
     def set_symmetry(self, symmetry):
         """every leaf evaluation of this engine (EVAL_NET only) averaged over the board's symmetries: "all", None (off), a mask
-        or an iterable of transform codes (alphazero_amd.symmetry).  The network needs max_batch >= len(members) * n_slots."""
-        from .symmetry import resolve
-        check(lib().az_engine_set_symmetry(self.h, resolve(symmetry)))
+        or an iterable of transform codes (alphazero_amd.symmetry).  The network needs max_batch >= len(members) * n_slots.
+        "random" / ("random", members): every leaf in ONE member drawn per evaluation instead (az_engine_set_symmetry_random): the
+        rows of the plain search, composes with set_leaf_batch.  The two modes exclude each other: the other one is switched off."""
+        from .symmetry import parse
+        mask, rnd = parse(symmetry)
+        if rnd:
+            if self._sym_mode == "ensemble":
+                check(lib().az_engine_set_symmetry(self.h, 0))
+                self._sym_mode = None
+            check(lib().az_engine_set_symmetry_random(self.h, mask))
+            self._sym_mode = "random" if mask != 0 else None
+        else:
+            if self._sym_mode == "random":
+                check(lib().az_engine_set_symmetry_random(self.h, 0))
+                self._sym_mode = None
+            check(lib().az_engine_set_symmetry(self.h, mask))
+            self._sym_mode = "ensemble" if mask != 0 else None
 
     def set_leaf_batch(self, k):
         """k simulations per slot and lock-step, kept apart by virtual loss (az_engine_set_leaf_batch; 1: the plain search, the
-        default).  EVAL_NET / EVAL_FAKE engines without a symmetry ensemble; the network needs max_batch >= k * n_slots."""
+        default).  EVAL_NET / EVAL_FAKE engines without a symmetry ensemble (the random symmetry mode combines); the network needs
+        max_batch >= k * n_slots."""
         check(lib().az_engine_set_leaf_batch(self.h, int(k)))
 
     def collisions(self):

@@ -41,10 +41,10 @@ def _move_of(board, action):
 
 
 def check_symmetry(symmetry, nn):
-    """the mask of `symmetry` (symmetry.resolve); ValueError -- before any device work -- for a malformed one, or when `nn` would
-    evaluate the leaves through an external evaluator (evaluators.route): the ensemble runs on the HIP network only"""
-    from .symmetry import resolve
-    mask = resolve(symmetry)
+    """the mask of `symmetry` (symmetry.parse: an ensemble or a random spec); ValueError -- before any device work -- for a malformed
+    one, or when `nn` would evaluate the leaves through an external evaluator (evaluators.route): both modes run on the HIP network only"""
+    from .symmetry import parse
+    mask, _ = parse(symmetry)
     if mask != 0 and nn is not None:
         from .evaluators import route
         if route(nn) != "hip":
@@ -59,7 +59,8 @@ MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
 def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
     """the walkers per lock-step of `leaf_batch` (None: 1); ValueError -- before any device work -- for a bool, a non-integer or a
     value outside 1..16, and for a value above 1 with a network evaluated through an external evaluator (evaluators.route), a
-    rollout-mode tree (`neural` False) or a symmetry ensemble: virtual-loss batching runs on the HIP network's plain evaluation only"""
+    rollout-mode tree (`neural` False) or a symmetry ensemble: virtual-loss batching runs on the HIP network's plain evaluation, or
+    with one random symmetry per evaluation (a "random" spec), only"""
     if leaf_batch is None:
         return 1
     if isinstance(leaf_batch, (bool, np.bool_)) or not isinstance(leaf_batch, (int, np.integer)):
@@ -75,8 +76,9 @@ def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
             if route(nn) != "hip":
                 raise ValueError(f"leaf_batch={k} needs a network the HIP network serves; {type(nn).__name__} evaluates its leaves "
                                  f"through an external evaluator, which takes one leaf per lock-step")
-        from .symmetry import resolve
-        if resolve(symmetry) != 0:
+        from .symmetry import parse
+        mask, rnd = parse(symmetry)
+        if mask != 0 and not rnd:
             raise ValueError(f"leaf_batch={k} does not combine with symmetry={symmetry!r}")
     return k
 
@@ -102,7 +104,8 @@ class MCT:
         self._last_board = None
         self._tie_mode = None         # tests: engine.TIE_LOWEST (None: fair_max draws among equals, utils.py:28-34)
         self._noise_mode = None       # tests: engine.NOISE_HASH (None: Dirichlet noise from the Philox stream)
-        # leaf evaluations averaged over the board's symmetries (alphazero_amd.symmetry; None: off); HIP-routed networks only
+        # leaf evaluations averaged over the board's symmetries, or ("random") each in one drawn at random (alphazero_amd.symmetry;
+        # None: off); HIP-routed networks only
         self.symmetry = symmetry
         check_symmetry(symmetry, self._nn)
         # simulations per lock-step, kept apart by virtual loss (None / 1: the reference's sequential search); HIP-routed networks only
@@ -194,7 +197,7 @@ class MCT:
     def _sync_device_root(self, board, n_sim=None):
         from .engine import EVAL_EXTERNAL, EVAL_NET, EVAL_ROLLOUT, NOISE_OFF, NOISE_PHILOX, TIE_RANDOM, SelfPlayEngine
         from .evaluators import check_game, check_normalizer, make_evaluator, route
-        from .symmetry import members
+        from .symmetry import members, parse
         check_game(board)
         neural = self.eval_method == TreeEval.NEURAL
         if neural and self._nn is None:
@@ -230,7 +233,7 @@ class MCT:
                 self._evaluator = make_evaluator(self._nn, board.game, H, W)
                 self._engine.set_evaluator(self._evaluator)
             if sym:
-                self._engine.set_symmetry(sym)
+                self._engine.set_symmetry(("random", sym) if parse(self.symmetry)[1] else sym)
             self._engine_board = (board.game, H, W)
             self._plies = 0
             self._engine_lb = 1

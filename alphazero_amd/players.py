@@ -186,7 +186,7 @@ class BatchedMCTSPlayer(Player):
     def _build(self, first):
         from .engine import (EVAL_EXTERNAL, EVAL_NET, EVAL_ROLLOUT, GAME_IDS, NOISE_OFF, NOISE_PHILOX, TIE_RANDOM, SelfPlayEngine)
         from .evaluators import make_evaluator, route
-        from .symmetry import members
+        from .symmetry import members, parse
         H, W = first.grid.shape
         if self._engine is not None and self._engine_board != (first.game, H, W):
             self._engine.close()  # built for another board: rebuild rather than search with the wrong rules
@@ -198,8 +198,9 @@ class BatchedMCTSPlayer(Player):
         sym = members(first.game, H, W, check_symmetry(self.symmetry, self.nn if neural else None))
         lb = check_leaf_batch(self.leaf_batch, self.nn if neural else None, self.symmetry, neural)
         if neural and not external:
-            # every slot's leaf in each of its twins, or every slot's leaf_batch walkers
-            self._hipnet = self.nn.to_hip(max_batch=max(1, len(sym), lb) * self.n_slots)
+            # every slot's leaf in each of its twins, or every slot's leaf_batch walkers (a random spec evaluates one twin per leaf)
+            rnd = parse(self.symmetry)[1]
+            self._hipnet = self.nn.to_hip(max_batch=max(1, 1 if rnd else len(sym), lb) * self.n_slots)
         noisy = self.dirichlet_alpha is not None and self.dirichlet_epsilon is not None
         self._engine = SelfPlayEngine(GAME_IDS[first.game], H, W, n_slots=self.n_slots, n_sim=self.n_sim,
                                       net=self._hipnet if neural and not external else None,
@@ -212,7 +213,7 @@ class BatchedMCTSPlayer(Player):
             self._evaluator = make_evaluator(self.nn, first.game, H, W)
             self._engine.set_evaluator(self._evaluator)
         if sym:
-            self._engine.set_symmetry(sym)
+            self._engine.set_symmetry(("random", sym) if parse(self.symmetry)[1] else sym)
         if lb > 1:
             self._engine.set_leaf_batch(lb)
         self._engine_board = (first.game, H, W)
@@ -305,7 +306,8 @@ class BatchedMCTSPlayer(Player):
 class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
     """AlphaZeroPlayer (players.py:194-247) for up to n_slots games at once: PUCT with the network `nn` (the HIP network for a shipped
     architecture, else the network's own evaluate / predict through an external evaluator), optional root Dirichlet noise and an
-    optional ensemble over the board's symmetries (`symmetry`: "all", a mask or transform codes; HIP network only)"""
+    optional ensemble over the board's symmetries (`symmetry`: "all", a mask or transform codes; HIP network only) or one symmetry
+    drawn per evaluation (`symmetry`: "random" or ("random", members); combines with `leaf_batch`)"""
     _eval_method = "neural"
 
     def __init__(self, n_sim=None, nn=None, n_slots=1, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, verbose=False,

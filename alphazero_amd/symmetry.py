@@ -6,6 +6,10 @@ to the reflected board.  A symmetry *mask* is a set of codes, bit t = code t; it
 Square Othello and TicTacToe boards have all eight codes; Connect4 has the identity and the reflection only (gravity rules the
 rotations out, on a square board too).
 
+A *random* spec -- "random" (every code the board has) or ("random", members), members anything resolve() takes -- evaluates
+every leaf in ONE member drawn per evaluation instead of averaging over all of them (az_engine_set_symmetry_random): parse() tells
+the two kinds apart, random_code() restates the draw on the host.
+
 The helpers work on numpy arrays and torch tensors alike and never touch the library: the device kernels (csrc/az_symmetry.hip)
 are tested against them.
 """
@@ -38,6 +42,54 @@ def resolve(symmetry):
             raise ValueError(f"symmetry code {code!r}: transform codes are the integers 0..7")
         mask |= 1 << int(code)
     return mask
+
+
+def parse(symmetry):
+    """(mask, is_random) of a symmetry spec: everything resolve() takes is an ensemble (or off) -> (resolve(symmetry), False);
+    "random" -> (SYM_ALL, True); ("random", members) -> (resolve(members), True).  ValueError for anything else."""
+    if isinstance(symmetry, str) and symmetry == "random":
+        return SYM_ALL, True
+    if isinstance(symmetry, (tuple, list)) and len(symmetry) >= 1 and isinstance(symmetry[0], str):
+        if symmetry[0] != "random" or len(symmetry) != 2:
+            raise ValueError(f"symmetry {symmetry!r}: a random spec is 'random' or ('random', members)")
+        if isinstance(symmetry[1], str) and symmetry[1] == "random":
+            raise ValueError(f"symmetry {symmetry!r}: the members of a random spec are 'all', a mask or transform codes 0..7")
+        return resolve(symmetry[1]), True
+    if isinstance(symmetry, str) and symmetry != "all":
+        raise ValueError(f"symmetry {symmetry!r}: expected 'all', 'random', ('random', members), None, a mask or an iterable of "
+                         f"transform codes 0..7")
+    return resolve(symmetry), False
+
+
+ROOT_PASS = 0xFFFFFFFF  # the `s` of the root-prior pass in random_code (a leaf's is its simulation index)
+
+
+def _closed_form():
+    try:
+        from tools import closed_form
+        return closed_form
+    except ImportError:  # the package used from outside its tree: tools/ lies beside it
+        import importlib.util
+        import os
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "closed_form.py")
+        spec = importlib.util.spec_from_file_location("_az_closed_form", path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+
+
+def random_code(seed, game_id, ply, s, members):
+    """the transform code a random-mode engine evaluates a pending row in (k_sym_pick, csrc/az_engine.hip): `members` the
+    candidate codes in ascending order, n of them;  r = philox4x32(seed, game_id, ply, s, P_SYMMETRY, 0),
+    m = (r[0] * n) >> 32, code = members[m].  s: the simulation index of the leaf (counted from the first search on this root;
+    leaf_batch K: t * K + j for walker j of lock-step t), ROOT_PASS for the root-prior pass; ply: the root's."""
+    cf = _closed_form()
+    members = [int(t) for t in members]
+    if not members or sorted(set(members)) != members:
+        raise ValueError(f"members {members!r}: the candidate codes in ascending order, at least one")
+    m32 = 0xFFFFFFFF
+    r = cf.philox4x32(int(seed) & m32, int(game_id) & m32, int(ply) & m32, int(s) & m32, cf.P_SYMMETRY, 0)
+    return members[(r[0] * len(members)) >> 32]
 
 
 def _game_id(game):

@@ -61,7 +61,7 @@ def augment(memory, nn, strategy):
 class AlphaZeroTrainer:
     DEFAULT_EXP_NAME = "alphazero-undefined"
 
-    def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True):
+    def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -81,6 +81,24 @@ class AlphaZeroTrainer:
         self.sgd_backend = "hip"
         self.sgd_backend_used = None
         self._hip_step = None
+        # self-play leaves evaluated in one board symmetry drawn per evaluation: None (off), "random" or ("random", members)
+        # (alphazero_amd.symmetry); the ensemble is for play and analysis, not for the self-play wave, and is refused
+        self.selfplay_symmetry = selfplay_symmetry
+        self._check_selfplay_symmetry()
+
+    def _check_selfplay_symmetry(self):
+        from .symmetry import parse
+        spec = self.selfplay_symmetry
+        if spec is None:
+            return None
+        try:
+            mask, rnd = parse(spec)
+        except (ValueError, TypeError) as exc:
+            raise ValueError(f"selfplay_symmetry={spec!r}: expected None, 'random' or ('random', members) ({exc})") from None
+        if not rnd:
+            raise ValueError(f"selfplay_symmetry={spec!r}: expected None, 'random' or ('random', members); the self-play wave takes "
+                             f"one random symmetry per evaluation, not the ensemble")
+        return spec
 
     def __str__(self):
         return f"{type(self).__name__}{self.game.capitalize()}" if self.game is not None else type(self).__name__
@@ -143,6 +161,12 @@ class AlphaZeroTrainer:
         if c.simulations is None:
             raise ValueError("the batched engine needs config.simulations (compute_time-bounded search is host-only)")
         slots = max(1, min(self.engine_slots, c.episodes))
+        sym = self._check_selfplay_symmetry()
+        if sym is not None:
+            from .mcts import check_symmetry
+            from .symmetry import members, parse
+            check_symmetry(sym, self.nn)  # ValueError for a network routed to the external evaluator
+            sym = ("random", members(self.game, H, W, parse(sym)[0]))  # ValueError for a code the board does not have
         # a network the HIP net does not serve evaluates the leaves itself (external evaluator, evaluators.route)
         external = route(self.nn) != "hip"
         if self._engine is not None and (self._engine.cfg.evaluator == EVAL_EXTERNAL) != external:
@@ -166,6 +190,8 @@ class AlphaZeroTrainer:
                                           sample_capacity=c.episodes * plies, evaluator=EVAL_EXTERNAL if external else EVAL_NET)
         if external:  # a fresh evaluator for the network of this wave (update_network replaces self.nn)
             self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
+        elif sym is not None or self._engine._sym_mode is not None:
+            self._engine.set_symmetry(sym)
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

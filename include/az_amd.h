@@ -106,6 +106,14 @@ int az_net_forward_dyn(az_net *net, const float *d_input, const int32_t *d_count
  * Needs n * B <= max_batch (AZ_EINVAL otherwise); the scratch rows belong to the net and are allocated at the first call. */
 #define AZ_SYM_ALL (-1)
 int az_net_forward_sym(az_net *net, const float *d_input, int B, int32_t mask, float *d_probs, float *d_value, void *stream);
+/* One symmetry per row instead of the average: row r is evaluated in the single orientation d_codes[r] (a transform code as above,
+ * one byte per row, DEVICE memory).  The row's input plane is replaced by its twin under that code, the ordinary forward runs on the
+ * B rows, d_probs[r][a] is the twin's entry for the cell that holds original action a (Othello's pass entry stays in place, Connect4
+ * flips its columns) and d_value[r] the twin's value: copies only, no sum and no division.  Every code 0 is az_net_forward bit for
+ * bit, every code c is az_net_forward_sym with mask 1 << c bit for bit.  The codes are not copied to the host and so are trusted:
+ * a code the board does not have is read as the identity (the Python wrapper validates them).  AZ_EINVAL: a null argument,
+ * B <= 0, B > max_batch.  This is the evaluation of az_engine_set_symmetry_random below with the codes given, not drawn. */
+int az_net_forward_sym_codes(az_net *net, const float *d_input, int B, const uint8_t *d_codes, float *d_probs, float *d_value, void *stream);
 int az_net_action_size(const az_net *net);
 /* algorithmic FLOPs of one forward per board (2*MAC) */
 int64_t az_net_flops_per_board(const az_net *net);
@@ -240,6 +248,24 @@ int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h_over, int8
  * times the network rows.  The engine's cached search graphs are dropped.  AZ_EINVAL: a code the game or board does not have,
  * an engine whose evaluator is not AZ_EVAL_NET, a net with max_batch < n * n_slots; AZ_ESTATE while a search is open. */
 int az_engine_set_symmetry(az_engine *e, int32_t mask);
+
+/* Every leaf evaluation of this engine in ONE randomly drawn member of `mask` (the form AlphaGo Zero used in self-play and in match
+ * play): the orientation bias of the network averages out over a search at the row count of the plain search.  The mask, its codes
+ * and their validity are those of az_engine_set_symmetry; AZ_SYM_ALL = every valid code; 0 = off (the default), when the launch
+ * sequence and every bit are the plain ones.  Contract -- members = the mask's codes in ascending order, n of them; every pending
+ * network row (the fresh root of the root-prior pass or a leaf selected for evaluation) is evaluated in exactly one member:
+ *   r = Philox4x32-10 keyed (seed, game_id[slot]) at counter (ply[slot], s, AZ_P_SYMMETRY = 8, 0)
+ *   m = (uint32)(((uint64)r.x * n) >> 32),   code = members[m]
+ * with s = (uint32)(sim + the simulations already run on this root) for the leaf of simulation sim (leaf_batch K: walker j of
+ * lock-step t has sim = t * K + j) and s = 0xFFFFFFFF for the root-prior pass; ply is the root's ply.  The draw is a function of
+ * the game alone, never of the slot, the row, the batch shape or the GPU.  The row is then evaluated as az_net_forward_sym_codes
+ * evaluates a row with that code; the renormalisation over the legal moves that follows is untouched.  A mask that holds the
+ * identity alone reproduces the plain search bit for bit.  Costs two small launches per lock-step and no extra network rows: it
+ * needs max_batch >= leaf_batch * n_slots only, and composes with az_engine_set_leaf_batch in either order of the two calls.
+ * Mutually exclusive with a non-zero ensemble mask: each of the two setters refuses while the other mode is in force.  The engine's
+ * cached search graphs are dropped.  AZ_EINVAL: a code the game or board does not have, an engine whose evaluator is not
+ * AZ_EVAL_NET, an ensemble mask in force, a net with max_batch < leaf_batch * n_slots; AZ_ESTATE while a search is open. */
+int az_engine_set_symmetry_random(az_engine *e, int32_t mask);
 
 /* Several leaves per slot and lock-step, kept apart by virtual loss.  The reference searches strictly one simulation after the
  * other (mcts.py:127-171 select_node, 197-223 back_propagate, 254-262 the loop of MCT.search); with leaf_batch = K > 1 a search of

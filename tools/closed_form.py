@@ -69,6 +69,7 @@ def philox4x32(k0, k1, c0, c1, c2, c3):
 
 
 P_TIE_SELECT, P_NOISE_NORMAL, P_NOISE_BOOST, P_MOVE_SAMPLE, P_TIE_MOVE, P_ROLLOUT_EXPAND, P_PLAYOUT = 1, 2, 3, 4, 5, 6, 7
+P_SYMMETRY = 8  # the symmetry a leaf is evaluated in (random mode, az_engine_set_symmetry_random)
 
 
 def u53(a, b):
