@@ -102,6 +102,13 @@ struct EngDev {
 // ---------------------------------------------------------------------------------------------
 // node access (two 16-byte transactions) and 16-lane group primitives
 // ---------------------------------------------------------------------------------------------
+// a node's last word: n_children | action << 8 | flags << 16 | winner << 24
+AZ_D u32 node_tail(const Node &n) { return (u32)n.nch | ((u32)n.act << 8) | ((u32)n.flags << 16) | ((u32)(uint8_t)n.win << 24); }
+AZ_D void set_node_tail(Node &n, u32 w) {
+    n.nch = (uint8_t)(w & 0xff); n.act = (uint8_t)((w >> 8) & 0xff); n.flags = (uint8_t)((w >> 16) & 0xff);
+    n.win = (int8_t)(w >> 24);
+}
+
 AZ_D Node load_node(const Node *p) {
     const uint4 *q = reinterpret_cast<const uint4 *>(p);
     uint4 a = q[0], b = q[1];
@@ -109,16 +116,14 @@ AZ_D Node load_node(const Node *p) {
     n.Q = __longlong_as_double((long long)(((u64)a.y << 32) | a.x));
     n.P = __longlong_as_double((long long)(((u64)a.w << 32) | a.z));
     n.N = (int)b.x; n.parent = (int)b.y; n.first = (int)b.z;
-    n.nch = (uint8_t)(b.w & 0xff); n.act = (uint8_t)((b.w >> 8) & 0xff); n.flags = (uint8_t)((b.w >> 16) & 0xff);
-    n.win = (int8_t)(b.w >> 24);
+    set_node_tail(n, b.w);
     return n;
 }
 
 AZ_D void store_node(Node *p, const Node &n) {
     u64 q = (u64)__double_as_longlong(n.Q), pp = (u64)__double_as_longlong(n.P);
     uint4 a = make_uint4((u32)q, (u32)(q >> 32), (u32)pp, (u32)(pp >> 32));
-    uint4 b = make_uint4((u32)n.N, (u32)n.parent, (u32)n.first,
-                         (u32)n.nch | ((u32)n.act << 8) | ((u32)n.flags << 16) | ((u32)(uint8_t)n.win << 24));
+    uint4 b = make_uint4((u32)n.N, (u32)n.parent, (u32)n.first, node_tail(n));
     uint4 *d = reinterpret_cast<uint4 *>(p);
     d[0] = a; d[1] = b;
 }
@@ -225,36 +230,42 @@ AZ_D int create_children_grp(const EngDev &E, int g, Node *pool, int fc, int nod
     return k;
 }
 
-// fair_max over PUCT (mcts.py:44-46, 137; utils.py:28-34): one lane per child, 16 children per round.
-// The chosen child's node is handed back by shuffle from the lane that scored it (no second memory trip).
-AZ_D int pick_child_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int ply, int sim, int depth, int sub,
-                        Node &chosen) {
-    const int fc = parent.first, nc = parent.nch;
-    const double sq = sqrt((double)parent.N);
+// The children one lane scores, one per round of 16: [r] is child r * LPG + sub of the parent, its score and what the walk needs of
+// its header (N, first child, last word).
+struct Scored {
     double key[4];
-    int cN[4], cfirst[4];
-    u32 cpack[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        key[r] = -__builtin_inf();
-        cN[r] = 0; cfirst[r] = -1; cpack[r] = 0;
-        int i = r * LPG + sub;
-        if (i < nc) {
-            Node c = load_node(pool + fc + i);
-            key[r] = c.Q + (c.P * sq) / (double)(1 + c.N);
-            cN[r] = c.N; cfirst[r] = c.first;
-            cpack[r] = (u32)c.nch | ((u32)c.act << 8) | ((u32)c.flags << 16) | ((u32)(uint8_t)c.win << 24);
-        }
-    }
-    double best = grp_max(fmax(fmax(key[0], key[1]), fmax(key[2], key[3])));
+    int N[4], first[4];
+    u32 tail[4];
+};
+
+// Round r of a scorer: marks the lane's child absent (key -inf), or loads it into c and keeps its header (the scorer then sets key[r]).
+AZ_D bool load_child_grp(const Node *pool, const Node &parent, int r, int sub, Scored &s, Node &c) {
+    s.key[r] = -__builtin_inf();
+    s.N[r] = 0; s.first[r] = -1; s.tail[r] = 0;
+    const int i = r * LPG + sub;
+    if (i >= parent.nch) return false;
+    c = load_node(pool + parent.first + i);
+    s.N[r] = c.N; s.first[r] = c.first; s.tail[r] = node_tail(c);
+    return true;
+}
+
+AZ_D int pick4(int v0, int v1, int v2, int v3, int r) { return r == 0 ? v0 : (r == 1 ? v1 : (r == 2 ? v2 : v3)); }
+
+// fair_max (utils.py:28-34) among the children a group has scored: one lane per child, 16 children per round.  Children [0, nvote)
+// take part in the ballot; when none of them holds the maximum, `none_err` (0: nothing) is raised.  `gid` is read only where a tie is
+// drawn.  The chosen child's header is handed back by shuffle from the lane that scored it (no second memory trip); returns the
+// child's index among the parent's children.
+AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int depth, const Scored &s, int nvote, int none_err,
+                        int sub, Node &chosen) {
+    double best = grp_max(fmax(fmax(s.key[0], s.key[1]), fmax(s.key[2], s.key[3])));
     u32 mask[4];
     int cnt = 0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { mask[r] = grp_ballot(key[r] == best); cnt += __popc(mask[r]); }
-    if (cnt == 0 && sub == 0) atomicOr(E.err, ERR_INTERNAL);  // NaN scores (a diverged network): no key equals the maximum
+    for (int r = 0; r < 4; ++r) { mask[r] = grp_ballot((r * LPG + sub) < nvote && s.key[r] == best); cnt += __popc(mask[r]); }
+    if (none_err && cnt == 0 && sub == 0) atomicOr(E.err, none_err);
     int k = 0;
     if (E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {  // with a single maximum the draw cannot change the result
-        Philox4 rr = az_philox(E.seed, E.game_id[g], (u32)ply, (u32)sim + E.sim_base, AZ_P_TIE_SELECT, (u32)depth);
+        Philox4 rr = az_philox(E.seed, gid, (u32)ply, (u32)sim + E.sim_base, AZ_P_TIE_SELECT, (u32)depth);
         k = (int)(((u64)rr.x * (u64)cnt) >> 32);
     }
     int rsel = 0, lsel = 0;
@@ -267,16 +278,114 @@ AZ_D int pick_child_grp(const EngDev &E, int g, const Node *pool, const Node &pa
             else k -= pc;
         }
     }
-    const int vN = rsel == 0 ? cN[0] : (rsel == 1 ? cN[1] : (rsel == 2 ? cN[2] : cN[3]));
-    const int vF = rsel == 0 ? cfirst[0] : (rsel == 1 ? cfirst[1] : (rsel == 2 ? cfirst[2] : cfirst[3]));
-    const u32 vP = rsel == 0 ? cpack[0] : (rsel == 1 ? cpack[1] : (rsel == 2 ? cpack[2] : cpack[3]));
-    chosen.N = __shfl(vN, lsel, LPG);
-    chosen.first = __shfl(vF, lsel, LPG);
-    const u32 pk = (u32)__shfl((int)vP, lsel, LPG);
-    chosen.nch = (uint8_t)(pk & 0xff); chosen.act = (uint8_t)((pk >> 8) & 0xff); chosen.flags = (uint8_t)((pk >> 16) & 0xff);
-    chosen.win = (int8_t)(pk >> 24);
+    // by value: picked as lvalues, the compiler selects the ADDRESS, indexes s dynamically and moves it to scratch
+    chosen.N = __shfl(pick4(s.N[0], s.N[1], s.N[2], s.N[3], rsel), lsel, LPG);
+    chosen.first = __shfl(pick4(s.first[0], s.first[1], s.first[2], s.first[3], rsel), lsel, LPG);
+    set_node_tail(chosen, (u32)__shfl(pick4((int)s.tail[0], (int)s.tail[1], (int)s.tail[2], (int)s.tail[3], rsel), lsel, LPG));
     chosen.Q = 0.0; chosen.P = 0.0; chosen.parent = 0;  // not needed by the walk
-    return fc + rsel * LPG + lsel;
+    return rsel * LPG + lsel;
+}
+
+// ---------------------------------------------------------------------------------------------
+// PUCT selection (mcts.py:44-46, 137) for k_step and k_step_multi.  k_step is walker j = 0 of a lock-step of one: no virtual count.
+// leaf_batch = K > 1 (az_engine_set_leaf_batch): K simulations per slot and lock-step, kept apart by virtual loss.
+// The reference searches strictly one simulation after the other (mcts.py:127-171 select_node, 197-223 back_propagate,
+// 254-262 the loop of search): this is a different search, opt-in.  Contract (DESIGN section 14):
+//   lock-step t runs the walkers j = 0 .. k_t - 1 of every searching slot, simulation index t * K + j, one after the other;
+//   walker j scores a child c of parent p with v(x) = the number of walkers i < j of this lock-step whose recorded path holds x:
+//     Q term   v(c) == 0 ? c.Q : ((double)c.N * c.Q - (double)v(c)) / (double)(c.N + v(c))
+//     U term   (c.P * sqrt((double)(p.N + v(p)))) / (double)(1 + c.N + v(c))
+//   (every v = 0: the reference's PUCT, bit for bit); break tests and flags use the real N; a path position at depth >= LPG
+//   is not recorded and counts 0.  A walker that lands on the pending leaf of an earlier walker i is a duplicate of i: no network
+//   row, and at backup it propagates i's outcome.  Backup runs in ascending j (the bump allocator advances in that order).
+// Virtual counts are never stored in a node: lane d of the group keeps the d-th node of every earlier walker's path (vpath), and a
+// child at depth d + 1 is compared with path_i[d + 1] fetched from lane d + 1 by shuffle.
+// ---------------------------------------------------------------------------------------------
+AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
+                           int ply, int sim, int depth, int sub, Node &chosen) {
+    const int fc = parent.first;
+    int vp = 0, vc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < MLB; ++i) {
+        if (i < j) {  // uniform over the group
+            const int pd = depth < LPG ? __shfl(vpath[i], depth & (LPG - 1), LPG) : -1;
+            const int cd = depth + 1 < LPG ? __shfl(vpath[i], (depth + 1) & (LPG - 1), LPG) : -1;
+            vp += pd == pnode ? 1 : 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vc[r] += cd == fc + r * LPG + sub ? 1 : 0;
+        }
+    }
+    const double sq = sqrt((double)(parent.N + vp));
+    Scored s;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        Node c;
+        if (load_child_grp(pool, parent, r, sub, s, c)) {
+            const double q = vc[r] == 0 ? c.Q : ((double)c.N * c.Q - (double)vc[r]) / (double)(c.N + vc[r]);
+            s.key[r] = q + (c.P * sq) / (double)(1 + c.N + vc[r]);
+        }
+    }
+    // every lane votes, and NaN scores (a diverged network) are an error: no key equals the maximum
+    return fc + choose_max_grp(E, E.game_id[g], ply, sim, depth, s, 4 * LPG, ERR_INTERNAL, sub, chosen);
+}
+
+// One walker on its way from the root to its leaf: the board, the node it stands on, and the path so far.
+struct Walk {
+    BB b;
+    Node cur;
+    int node, plen, my_path;  // lane i keeps the i-th node of the root..leaf path in my_path (-1: none); depth = plen - 1
+    bool bad;
+};
+
+// select_node's descent (mcts.py:127-171) of walker j, from wk (the root, or wherever wk stands) to its leaf.
+AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], int j, int ply, int sim, int sub, Walk &wk) {
+    for (;;) {
+        bool fresh = false;
+        if (!(wk.cur.flags & F_EXPANDED)) {
+            if (wk.cur.flags & F_TERMINAL) break;  // mcts.py:146-147
+            if (!(wk.cur.flags & F_EVALUATED)) { wk.bad = true; break; }
+            wk.cur.flags |= F_EXPANDED;  // mcts.py:151-160 : children become visible now, also to the walkers that follow
+            if (sub == 0) pool[wk.node].flags = wk.cur.flags;
+            fresh = true;
+        }
+        Node ch;
+        const int c = pick_child_vl_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch);
+        wk.node = c; wk.cur = ch;
+        if (sub == wk.plen) wk.my_path = c;
+        ++wk.plen;
+        az_play_grp(E.gd, wk.b, wk.cur.act, sub);
+        if (fresh || wk.cur.N == 0) break;  // mcts.py:143-144
+    }
+}
+
+// What the walk ended on: LS_NONE (an internal error, reported), LS_TERM (w = the winner; a node found terminal now is marked)
+// or LS_EVAL (the leaf wants a row of the network batch).
+AZ_D int classify_leaf_grp(const EngDev &E, Node *pool, const Walk &wk, int &w, int sub) {
+    if (wk.bad) {
+        if (sub == 0) atomicOr(E.err, ERR_INTERNAL);
+        return LS_NONE;
+    }
+    if (wk.cur.flags & F_TERMINAL) { w = wk.cur.win; return LS_TERM; }
+    if (az_status_grp(E.gd, wk.b, &w, sub)) {  // mcts.py:185-186
+        if (sub == 0) { pool[wk.node].flags = wk.cur.flags | F_TERMINAL; pool[wk.node].win = (int8_t)w; }
+        return LS_TERM;
+    }
+    return LS_EVAL;
+}
+
+// Rows of the network batch are handed out per BLOCK: one LDS count of the lanes that want one and one global atomic per 16 games,
+// instead of one per game on a single hot address.  Three workgroup barriers: EVERY wave of the block calls this, the same number
+// of times, whether its lanes want a row or not.  Returns the lane's row (meaningless for a lane that wanted none).
+AZ_D int alloc_rows_block(int *counter, bool want) {
+    __shared__ int s_need, s_base;
+    if (threadIdx.x == 0) s_need = 0;
+    __syncthreads();
+    int rank = 0;
+    if (want) rank = atomicAdd(&s_need, 1);  // LDS atomic
+    __syncthreads();
+    if (threadIdx.x == 0) s_base = s_need > 0 ? atomicAdd(counter, s_need) : 0;
+    __syncthreads();
+    return s_base + rank;
 }
 
 AZ_D double log_gamma_draw(const EngDev &E, u32 gid, int ply, int sim, double alpha, u32 j) {
@@ -509,9 +618,7 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
             if (fast && SELECT) {  // lane 0 holds the root (path[0]) with its new visit count: forward it
                 fwd.N = __shfl(mine.N, 0, LPG);
                 fwd.first = __shfl(mine.first, 0, LPG);
-                const u32 pk = (u32)__shfl((int)((u32)mine.nch | ((u32)mine.act << 8) | ((u32)mine.flags << 16) | ((u32)(uint8_t)mine.win << 24)), 0, LPG);
-                fwd.nch = (uint8_t)(pk & 0xff); fwd.act = (uint8_t)((pk >> 8) & 0xff); fwd.flags = (uint8_t)((pk >> 16) & 0xff);
-                fwd.win = (int8_t)(pk >> 24);
+                set_node_tail(fwd, (u32)__shfl((int)node_tail(mine), 0, LPG));
                 fwd.Q = 0.0; fwd.P = 0.0; fwd.parent = -1;
                 // the root itself may be the leaf that just got its children (first visit of an unexpanded root)
                 have_root = (leaf != node) || st != LS_EVAL;
@@ -524,71 +631,34 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
     PSTAMP(3)
     if (BACKUP && sub == 0 && in_range) E.evals[g] = evals;
     if (!SELECT) return;
-    // From here on no group may leave early: the leaf rows are handed out per BLOCK (one global atomic per
-    // 16 games instead of one per game on a single hot address) behind two workgroup barriers.
-    __shared__ int s_need, s_base;
-    if (threadIdx.x == 0) s_need = 0;
-    int status = LS_NONE, w = 0, depth = 0, plen = 1;
-    int my_path = -1;
-    bool bad = false;
-    Node cur;
+    // From here on no group may leave early: the leaf rows are handed out per block (alloc_rows_block) behind workgroup barriers.
+    int status = LS_NONE, w = 0;
+    Walk wk = {b, Node(), node, 1, sub == 0 ? node : -1, false};
     if (active) {
-        if (have_root) cur = fwd; else cur = load_node(pool + node);
-        if (E.noise_mode != AZ_NOISE_OFF && E.alpha >= 0.0 && E.eps >= 0.0 && (cur.flags & F_EXPANDED) && !(cur.flags & F_NOISED)) {
-            apply_root_noise_grp(E, g, pool, node, cur, b, ply, sim, sub);
-            cur.flags |= F_NOISED;
+        if (have_root) wk.cur = fwd; else wk.cur = load_node(pool + node);
+        if (E.noise_mode != AZ_NOISE_OFF && E.alpha >= 0.0 && E.eps >= 0.0 && (wk.cur.flags & F_EXPANDED) && !(wk.cur.flags & F_NOISED)) {
+            apply_root_noise_grp(E, g, pool, node, wk.cur, b, ply, sim, sub);
+            wk.cur.flags |= F_NOISED;
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
         PSTAMP(4)
-        my_path = sub == 0 ? node : -1;  // lane i keeps the i-th node of the root..leaf path
-        for (;;) {
-            if (cur.flags & F_EXPANDED) {
-                Node ch;
-                int c = pick_child_grp(E, g, pool, cur, ply, sim, depth++, sub, ch);
-                node = c; cur = ch;
-                if (sub == plen) my_path = c;
-                ++plen;
-                az_play_grp(E.gd, b, cur.act, sub);
-                if (cur.N == 0) break;  // mcts.py:143-144
-                continue;
-            }
-            if (cur.flags & F_TERMINAL) break;  // mcts.py:146-147
-            if (!(cur.flags & F_EVALUATED)) { bad = true; break; }
-            cur.flags |= F_EXPANDED;  // mcts.py:151-160 : children become visible now
-            if (sub == 0) pool[node].flags = cur.flags;
-            Node ch;
-            int c = pick_child_grp(E, g, pool, cur, ply, sim, depth, sub, ch);
-            node = c; cur = ch;
-            if (sub == plen) my_path = c;
-            ++plen;
-            az_play_grp(E.gd, b, cur.act, sub);
-            break;
-        }
+        const int no_walkers[MLB] = {};  // walker j = 0: nobody walked before it in this lock-step, every virtual count is 0
+        walk_grp(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
         PSTAMP(5)
-        E.path[(size_t)g * LPG + sub] = my_path;
-        if (sub == 0) { E.path_len[g] = plen; if (plen > LPG) atomicMax(E.max_path, plen); }
-        if (bad) { if (sub == 0) atomicOr(E.err, ERR_INTERNAL); }
-        else if (cur.flags & F_TERMINAL) { status = LS_TERM; w = cur.win; }
-        else if (az_status_grp(E.gd, b, &w, sub)) {  // mcts.py:185-186
-            status = LS_TERM;
-            if (sub == 0) { pool[node].flags = cur.flags | F_TERMINAL; pool[node].win = (int8_t)w; }
-        } else {
-            status = LS_EVAL;
-        }
+        E.path[(size_t)g * LPG + sub] = wk.my_path;
+        if (sub == 0) { E.path_len[g] = wk.plen; if (wk.plen > LPG) atomicMax(E.max_path, wk.plen); }
+        status = classify_leaf_grp(E, pool, wk, w, sub);
     }
-    __syncthreads();
-    int rank = 0;
-    if (status == LS_EVAL && sub == 0) rank = atomicAdd(&s_need, 1);  // LDS atomic
-    __syncthreads();
-    if (threadIdx.x == 0) s_base = s_need > 0 ? atomicAdd(E.batch_cnt + (sim & 1), s_need) : 0;
-    __syncthreads();
+    const int row = __shfl(alloc_rows_block(E.batch_cnt + (sim & 1), status == LS_EVAL && sub == 0), 0, LPG);
     if (status == LS_EVAL) {
-        const int row = s_base + __shfl(rank, 0, LPG);
-        write_nn_input_grp(E, row, b, sub);
+        write_nn_input_grp(E, row, wk.b, sub);
         if (sub == 0) E.row_of_slot[g] = row;
     }
     if (sub == 0 && in_range) {
-        if (active) { E.leaf[g] = node; E.leaf_p1[g] = b.p1; E.leaf_m1[g] = b.m1; E.leaf_player[g] = (int8_t)b.player; E.leaf_winner[g] = (int8_t)w; }
+        if (active) {
+            E.leaf[g] = wk.node; E.leaf_p1[g] = wk.b.p1; E.leaf_m1[g] = wk.b.m1; E.leaf_player[g] = (int8_t)wk.b.player;
+            E.leaf_winner[g] = (int8_t)w;
+        }
         E.leaf_status[g] = (int8_t)status;
     }
     PSTAMP(6)
@@ -596,87 +666,9 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
     if (BACKUP && SELECT && sim == 50 && (threadIdx.x & 63) == 0 && blockIdx.x < 1024) {  // az_step_probe holds 1024 blocks x 4 waves
         unsigned long long *o = az_step_probe + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
         for (int i = 0; i < 7; ++i) o[i] = pt[i];
-        o[7] = (unsigned long long)depth;
+        o[7] = (unsigned long long)(wk.plen - 1);
     }
 #endif
-}
-
-// ---------------------------------------------------------------------------------------------
-// leaf_batch = K > 1 (az_engine_set_leaf_batch): K simulations per slot and lock-step, kept apart by virtual loss.
-// The reference searches strictly one simulation after the other (mcts.py:127-171 select_node, 197-223 back_propagate,
-// 254-262 the loop of search): this is a different search, opt-in.  Contract (DESIGN section 14):
-//   lock-step t runs the walkers j = 0 .. k_t - 1 of every searching slot, simulation index t * K + j, one after the other;
-//   walker j scores a child c of parent p with v(x) = the number of walkers i < j of this lock-step whose recorded path holds x:
-//     Q term   v(c) == 0 ? c.Q : ((double)c.N * c.Q - (double)v(c)) / (double)(c.N + v(c))
-//     U term   (c.P * sqrt((double)(p.N + v(p)))) / (double)(1 + c.N + v(c))
-//   (every v = 0: pick_child_grp's expression, bit for bit); break tests and flags use the real N; a path position at depth >= LPG
-//   is not recorded and counts 0.  A walker that lands on the pending leaf of an earlier walker i is a duplicate of i: no network
-//   row, and at backup it propagates i's outcome.  Backup runs in ascending j (the bump allocator advances in that order).
-// Virtual counts are never stored in a node: lane d of the group keeps the d-th node of every earlier walker's path (vpath), and a
-// child at depth d + 1 is compared with path_i[d + 1] fetched from lane d + 1 by shuffle.
-// ---------------------------------------------------------------------------------------------
-AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
-                           int ply, int sim, int depth, int sub, Node &chosen) {
-    const int fc = parent.first, nc = parent.nch;
-    int vp = 0, vc[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < MLB; ++i) {
-        if (i < j) {  // uniform over the group
-            const int pd = depth < LPG ? __shfl(vpath[i], depth & (LPG - 1), LPG) : -1;
-            const int cd = depth + 1 < LPG ? __shfl(vpath[i], (depth + 1) & (LPG - 1), LPG) : -1;
-            vp += pd == pnode ? 1 : 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) vc[r] += cd == fc + r * LPG + sub ? 1 : 0;
-        }
-    }
-    const double sq = sqrt((double)(parent.N + vp));
-    double key[4];
-    int cN[4], cfirst[4];
-    u32 cpack[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        key[r] = -__builtin_inf();
-        cN[r] = 0; cfirst[r] = -1; cpack[r] = 0;
-        int i = r * LPG + sub;
-        if (i < nc) {
-            Node c = load_node(pool + fc + i);
-            const double q = vc[r] == 0 ? c.Q : ((double)c.N * c.Q - (double)vc[r]) / (double)(c.N + vc[r]);
-            key[r] = q + (c.P * sq) / (double)(1 + c.N + vc[r]);
-            cN[r] = c.N; cfirst[r] = c.first;
-            cpack[r] = (u32)c.nch | ((u32)c.act << 8) | ((u32)c.flags << 16) | ((u32)(uint8_t)c.win << 24);
-        }
-    }
-    double best = grp_max(fmax(fmax(key[0], key[1]), fmax(key[2], key[3])));
-    u32 mask[4];
-    int cnt = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { mask[r] = grp_ballot(key[r] == best); cnt += __popc(mask[r]); }
-    if (cnt == 0 && sub == 0) atomicOr(E.err, ERR_INTERNAL);  // NaN scores (a diverged network): no key equals the maximum
-    int k = 0;
-    if (E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {
-        Philox4 rr = az_philox(E.seed, E.game_id[g], (u32)ply, (u32)sim + E.sim_base, AZ_P_TIE_SELECT, (u32)depth);
-        k = (int)(((u64)rr.x * (u64)cnt) >> 32);
-    }
-    int rsel = 0, lsel = 0;
-    bool found = false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        int pc = __popc(mask[r]);
-        if (!found) {
-            if (k < pc) { rsel = r; lsel = kth_set_bit(mask[r], k); found = true; }
-            else k -= pc;
-        }
-    }
-    const int vN = rsel == 0 ? cN[0] : (rsel == 1 ? cN[1] : (rsel == 2 ? cN[2] : cN[3]));
-    const int vF = rsel == 0 ? cfirst[0] : (rsel == 1 ? cfirst[1] : (rsel == 2 ? cfirst[2] : cfirst[3]));
-    const u32 vP = rsel == 0 ? cpack[0] : (rsel == 1 ? cpack[1] : (rsel == 2 ? cpack[2] : cpack[3]));
-    chosen.N = __shfl(vN, lsel, LPG);
-    chosen.first = __shfl(vF, lsel, LPG);
-    const u32 pk = (u32)__shfl((int)vP, lsel, LPG);
-    chosen.nch = (uint8_t)(pk & 0xff); chosen.act = (uint8_t)((pk >> 8) & 0xff); chosen.flags = (uint8_t)((pk >> 16) & 0xff);
-    chosen.win = (int8_t)(pk >> 24);
-    chosen.Q = 0.0; chosen.P = 0.0; chosen.parent = 0;  // not needed by the walk
-    return fc + rsel * LPG + lsel;
 }
 
 // One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
@@ -744,10 +736,8 @@ __global__ __launch_bounds__(256) void k_step_multi(EngDev E, int t, int kb, int
         if (!SELECT && in_range) E.m_leaf_status[wj] = LS_NONE;
     }
     if (!SELECT) return;
-    // From here on no group may leave early: all walks first, then the rows of the whole block behind two barriers (one LDS count
-    // of the LS_EVAL walkers, one global atomic).  No barrier inside the walker loop.
-    __shared__ int s_need, s_base;
-    if (threadIdx.x == 0) s_need = 0;
+    // From here on no group may leave early: all walks first, then the rows of the whole block (alloc_rows_block: one LDS count of the
+    // LS_EVAL walkers, one global atomic).  No barrier inside the walker loop.
     int k_st = LS_NONE, k_leaf = 0, k_pl = 1, k_w = 0, k_plen = 0;  // lane j: walker j's pending leaf
     u64 k_p1 = 0, k_m1 = 0;
     int vpath[MLB];  // vpath[i]: the sub-th node of walker i's path (-1: none)
@@ -758,64 +748,32 @@ __global__ __launch_bounds__(256) void k_step_multi(EngDev E, int t, int kb, int
         int ndup = 0;
         for (int j = 0; j < kt; ++j) {
             const int sim = t * E.K + j;
-            BB b = rb;
-            int node = root, depth = 0, plen = 1, w = 0;
-            bool bad = false;
-            Node cur = rootn;
-            if (E.noise_mode != AZ_NOISE_OFF && E.alpha >= 0.0 && E.eps >= 0.0 && (cur.flags & F_EXPANDED) && !(cur.flags & F_NOISED)) {
-                apply_root_noise_grp(E, g, pool, node, cur, b, ply, sim, sub);
-                cur.flags |= F_NOISED;
-                rootn.flags = cur.flags;
+            Walk wk = {rb, rootn, root, 1, sub == 0 ? root : -1, false};
+            if (E.noise_mode != AZ_NOISE_OFF && E.alpha >= 0.0 && E.eps >= 0.0 && (wk.cur.flags & F_EXPANDED) && !(wk.cur.flags & F_NOISED)) {
+                apply_root_noise_grp(E, g, pool, root, wk.cur, rb, ply, sim, sub);
+                wk.cur.flags |= F_NOISED;
+                rootn.flags = wk.cur.flags;
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             }
-            int my_path = sub == 0 ? node : -1;  // lane i keeps the i-th node of the root..leaf path
-            for (;;) {
-                bool fresh = false;
-                if (!(cur.flags & F_EXPANDED)) {
-                    if (cur.flags & F_TERMINAL) break;  // mcts.py:146-147
-                    if (!(cur.flags & F_EVALUATED)) { bad = true; break; }
-                    cur.flags |= F_EXPANDED;  // mcts.py:151-160 : children become visible now, also to the walkers that follow
-                    if (sub == 0) pool[node].flags = cur.flags;
-                    if (depth == 0) rootn.flags = cur.flags;
-                    fresh = true;
-                }
-                Node ch;
-                const int c = pick_child_vl_grp(E, g, pool, cur, node, vpath, j, ply, sim, depth, sub, ch);
-                ++depth;
-                node = c; cur = ch;
-                if (sub == plen) my_path = c;
-                ++plen;
-                az_play_grp(E.gd, b, cur.act, sub);
-                if (fresh || cur.N == 0) break;  // mcts.py:143-144
-            }
-            E.m_path[((size_t)g * MLB + j) * LPG + sub] = my_path;
+            walk_grp(E, g, pool, vpath, j, ply, sim, sub, wk);
+            if (wk.plen > 1) rootn.flags |= F_EXPANDED;  // a walk that left the root found or made its children visible
+            E.m_path[((size_t)g * MLB + j) * LPG + sub] = wk.my_path;
 #pragma unroll
-            for (int i = 0; i < MLB; ++i) vpath[i] = i == j ? my_path : vpath[i];
-            if (plen > LPG && sub == 0) atomicMax(E.max_path, plen);
-            int status = LS_NONE;
-            if (bad) { if (sub == 0) atomicOr(E.err, ERR_INTERNAL); }
-            else if (cur.flags & F_TERMINAL) { status = LS_TERM; w = cur.win; }
-            else if (az_status_grp(E.gd, b, &w, sub)) {  // mcts.py:185-186
-                status = LS_TERM;
-                if (sub == 0) { pool[node].flags = cur.flags | F_TERMINAL; pool[node].win = (int8_t)w; }
-            } else {
-                const u32 m = grp_ballot(sub < j && k_st == LS_EVAL && k_leaf == node);  // pending leaf of an earlier walker?
-                status = m ? LS_DUP + (__ffs((int)m) - 1) : LS_EVAL;
-                ndup += m ? 1 : 0;
+            for (int i = 0; i < MLB; ++i) vpath[i] = i == j ? wk.my_path : vpath[i];
+            if (wk.plen > LPG && sub == 0) atomicMax(E.max_path, wk.plen);
+            int w = 0;
+            int status = classify_leaf_grp(E, pool, wk, w, sub);
+            if (status == LS_EVAL) {
+                const u32 m = grp_ballot(sub < j && k_st == LS_EVAL && k_leaf == wk.node);  // pending leaf of an earlier walker?
+                if (m) { status = LS_DUP + (__ffs((int)m) - 1); ++ndup; }
             }
-            if (sub == j) { k_st = status; k_leaf = node; k_p1 = b.p1; k_m1 = b.m1; k_pl = b.player; k_w = w; k_plen = plen; }
+            if (sub == j) { k_st = status; k_leaf = wk.node; k_p1 = wk.b.p1; k_m1 = wk.b.m1; k_pl = wk.b.player; k_w = w; k_plen = wk.plen; }
             // flag stores of this walker (F_EXPANDED, F_TERMINAL, the noised priors) must be visible to the next walker's loads
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
         if (ndup > 0 && sub == 0) atomicAdd(&E.ctr[CTR_COLLISIONS], (unsigned long long)ndup);
     }
-    __syncthreads();
-    int rank = 0;
-    if (k_st == LS_EVAL) rank = atomicAdd(&s_need, 1);  // LDS atomic, one per LS_EVAL walker
-    __syncthreads();
-    if (threadIdx.x == 0) s_base = s_need > 0 ? atomicAdd(E.batch_cnt + (t & 1), s_need) : 0;
-    __syncthreads();
-    const int k_row = s_base + rank;  // < K * G: at most one row per walker
+    const int k_row = alloc_rows_block(E.batch_cnt + (t & 1), k_st == LS_EVAL);  // < K * G: at most one row per walker
     for (int j = 0; j < kt; ++j) {
         if (__shfl(k_st, j, LPG) == LS_EVAL) {
             const BB bj = {(u64)__shfl((long long)k_p1, j, LPG), (u64)__shfl((long long)k_m1, j, LPG), __shfl(k_pl, j, LPG)};
@@ -841,50 +799,15 @@ __global__ __launch_bounds__(256) void k_step_multi(EngDev E, int t, int kb, int
 #define AZ_P_PLAYOUT 7
 
 AZ_D int pick_child_uct_grp(const EngDev &E, u32 gid, const Node *pool, const Node &parent, int ply, int sim, int depth, int sub, Node &chosen) {
-    const int fc = parent.first, nc = parent.nch;
     const double lg = az_det_log((double)parent.N);
-    double key[4];
-    int cN[4], cfirst[4];
-    u32 cpack[4];
+    Scored s;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        key[r] = -__builtin_inf();
-        cN[r] = 0; cfirst[r] = -1; cpack[r] = 0;
-        int i = r * LPG + sub;
-        if (i < nc) {
-            Node c = load_node(pool + fc + i);
-            key[r] = c.N == 0 ? __builtin_inf() : c.Q + 1.4142135623730951 * sqrt(lg / (double)c.N);
-            cN[r] = c.N; cfirst[r] = c.first;
-            cpack[r] = (u32)c.nch | ((u32)c.act << 8) | ((u32)c.flags << 16) | ((u32)(uint8_t)c.win << 24);
-        }
+        Node c;
+        if (load_child_grp(pool, parent, r, sub, s, c))
+            s.key[r] = c.N == 0 ? __builtin_inf() : c.Q + 1.4142135623730951 * sqrt(lg / (double)c.N);
     }
-    double best = grp_max(fmax(fmax(key[0], key[1]), fmax(key[2], key[3])));
-    u32 mask[4];
-    int cnt = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { mask[r] = grp_ballot((r * LPG + sub) < nc && key[r] == best); cnt += __popc(mask[r]); }
-    int k = 0;
-    if (E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {
-        Philox4 rr = az_philox(E.seed, gid, (u32)ply, (u32)sim + E.sim_base, AZ_P_TIE_SELECT, (u32)depth);
-        k = (int)(((u64)rr.x * (u64)cnt) >> 32);
-    }
-    int rsel = 0, lsel = 0;
-    bool found = false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        int pc = __popc(mask[r]);
-        if (!found) { if (k < pc) { rsel = r; lsel = kth_set_bit(mask[r], k); found = true; } else k -= pc; }
-    }
-    const int vN = rsel == 0 ? cN[0] : (rsel == 1 ? cN[1] : (rsel == 2 ? cN[2] : cN[3]));
-    const int vF = rsel == 0 ? cfirst[0] : (rsel == 1 ? cfirst[1] : (rsel == 2 ? cfirst[2] : cfirst[3]));
-    const u32 vP = rsel == 0 ? cpack[0] : (rsel == 1 ? cpack[1] : (rsel == 2 ? cpack[2] : cpack[3]));
-    chosen.N = __shfl(vN, lsel, LPG);
-    chosen.first = __shfl(vF, lsel, LPG);
-    const u32 pk = (u32)__shfl((int)vP, lsel, LPG);
-    chosen.nch = (uint8_t)(pk & 0xff); chosen.act = (uint8_t)((pk >> 8) & 0xff); chosen.flags = (uint8_t)((pk >> 16) & 0xff);
-    chosen.win = (int8_t)(pk >> 24);
-    chosen.Q = 0.0; chosen.P = 0.0; chosen.parent = 0;
-    return fc + rsel * LPG + lsel;
+    return parent.first + choose_max_grp(E, gid, ply, sim, depth, s, parent.nch, 0, sub, chosen);
 }
 
 __global__ __launch_bounds__(256) void k_rollout_step(EngDev E, int sim) {
@@ -956,29 +879,11 @@ __global__ __launch_bounds__(256) void k_rollout_step(EngDev E, int sim) {
         over = az_status_grp(gd, b, &w, sub);
     }
     // back_propagate along the recorded path
-    const double outcome = (double)w;
-    double reward;
-    if (fabs(outcome) < 1e-4) reward = 0.0;
-    else reward = ((double)player_to_play * outcome > 0.0) ? -fabs(outcome) : fabs(outcome);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (plen > LPG && sub == 0) atomicMax(E.max_path, plen);
-    if (plen <= LPG) {
-        if (sub < plen) {
-            Node n = load_node(pool + my_path);
-            const int up = plen - 1 - sub;
-            const double r = (reward == 0.0) ? 0.0 : ((up & 1) ? -reward : reward);
-            pool[my_path].Q = ((double)n.N * n.Q + r) / (double)(n.N + 1);
-            pool[my_path].N = n.N + 1;
-        }
-    } else {
-        int nd = node;
-        while (nd >= 0) {
-            Node n = load_node(pool + nd);
-            if (sub == 0) { pool[nd].Q = ((double)n.N * n.Q + reward) / (double)(n.N + 1); pool[nd].N = n.N + 1; }
-            nd = n.parent;
-            reward = (reward == 0.0) ? 0.0 : -reward;
-        }
-    }
+    Node mine;
+    if (plen <= LPG && sub < plen) mine = load_node(pool + my_path);
+    back_propagate_grp(pool, plen, my_path, mine, node, player_to_play, (double)w, sub);
 }
 
 AZ_D double linear_temp(int step, int tmax, int tmin) {  // schedulers.py:33-40
