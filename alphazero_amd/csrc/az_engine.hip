@@ -4,6 +4,8 @@
 // batch for the policy-value network.  Every tree still sees strictly sequential simulations, so
 // per-game semantics equal the reference's MCT.search (mcts.py:226-269) exactly -- no virtual loss.  (Opt-in, default off:
 // az_engine_set_leaf_batch walks K simulations per game and lock-step with virtual loss -- k_step_multi below, another search.)
+// (Opt-in, default off: az_engine_set_gumbel replaces the root's PUCT pick by Sequential Halving over actions sampled with Gumbel
+// noise and reads the root out by the completed Q-values -- k_step_gumbel below, another search again.)
 //
 // HBM layout
 //   boards   : 2 x u64 bitboards + int8 side-to-move per slot (root and current leaf), SoA over slots
@@ -97,6 +99,11 @@ struct EngDev {
     int K;
     int *m_leaf; u64 *m_leaf_p1, *m_leaf_m1; int8_t *m_leaf_player, *m_leaf_status, *m_leaf_winner;
     int *m_row, *m_path, *m_path_len;
+    // az_engine_set_gumbel (k_step_gumbel): gm = the actions sampled at the root (0: off, the PUCT search), the constants of sigma
+    // and the scale of the Gumbel draw; gmask [G] = the root children the slot's Sequential Halving still considers (0: all).
+    int gm;
+    double g_cvisit, g_cscale, g_scale;
+    u64 *gmask;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -496,7 +503,7 @@ AZ_D void reset_slot(const EngDev &E, int g, u32 game_id) {
     start_position(E.gd, b);
     E.root_p1[g] = b.p1; E.root_m1[g] = b.m1; E.root_player[g] = (int8_t)b.player;
     E.root[g] = 0; E.n_nodes[g] = 1; E.ply[g] = 0; E.game_id[g] = game_id; E.active[g] = 1;
-    E.leaf_status[g] = LS_NONE; E.evals[g] = 0; E.side[g] = 0;
+    E.leaf_status[g] = LS_NONE; E.evals[g] = 0; E.side[g] = 0; E.gmask[g] = 0;
     store_node(pool_of(E, g), fresh_node(0, -1, 0.0, 0));
 }
 
@@ -790,6 +797,240 @@ __global__ __launch_bounds__(256) void k_step_multi(EngDev E, int t, int kb, int
 }
 
 // ---------------------------------------------------------------------------------------------
+// Gumbel root search (az_engine_set_gumbel; "Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022): the root
+// samples gm actions without replacement by Gumbel noise, deals the simulations of a search over them by Sequential Halving and
+// is read out as the policy improved by the completed Q-values.  A different search from the reference's: opt-in, default off.
+// Contract.  The root has children 0 .. nch - 1; float64, one operation at a time:
+//   logit(a) = az_det_log(P(a))                                                  (-inf for P = 0)
+//   g(a)     = gumbel_scale == 0 ? 0.0 (no draw) : gumbel_scale * (-az_det_log(-az_det_log(u))),
+//              r = az_philox(seed, game_id, ply, 0xFFFF, AZ_P_GUMBEL, action(a)), u = az_u53(r.x, r.y), 2^-53 where that is 0:
+//              one draw per (game, ply, action), the same in every phase and search call, no function of slot, row or batch
+//   vmix     = (sum over N(b) > 0 of P(b) Q(b)) / (sum over N(b) > 0 of P(b)), child-index order; 0.0 when the divisor is 0
+//   cq(a)    = N(a) > 0 ? Q(a) : vmix            maxN = max N(b)
+//   sigma(a) = ((c_visit + (double)maxN) * c_scale) * cq(a)
+//   score(a) = (g(a) + logit(a)) + sigma(a)
+// Schedule of a search call of n simulations, m0 = min(gm, nch): m0 = 1 sends all to child 0; otherwise L = ceil(log2 m0), phase p
+// considers m_p candidates (m_0 = m0, m_{p+1} = max(2, m_p / 2)) for v_p = max(1, n / (L m_p)) rounds, phases follow each other
+// until n simulations are dealt (the phase of 2 repeats, the last one is cut).  At the first simulation of a phase the candidates
+// become the m_p best by score of the previous set (phase 0: of all children), ties to the lowest index whatever tie_mode says;
+// simulation i of a phase takes the (i mod m_p)-th candidate in ascending child index.  Below the root: the plain PUCT walk.
+// No root noise.  Move = the best score among the slot's candidates on the final statistics; policy target = softmax(logit + sigma).
+// ---------------------------------------------------------------------------------------------
+#define AZ_P_GUMBEL 9
+
+AZ_D double gumbel_g(const EngDev &E, u32 gid, int ply, int action) {
+    if (E.g_scale == 0.0) return 0.0;
+    const Philox4 r = az_philox(E.seed, gid, (u32)ply, 0xFFFFu, AZ_P_GUMBEL, (u32)action);
+    double u = az_u53(r.x, r.y);
+    if (u == 0.0) u = 1.0 / 9007199254740992.0;
+    return E.g_scale * (-az_det_log(-az_det_log(u)));
+}
+
+// where simulation s of a search of n stands in the schedule: phase p of m_p candidates, i = its index inside the phase
+AZ_D void gumbel_phase(int s, int n, int m0, int &p, int &mp, int &i) {
+    p = 0; mp = m0; i = s;
+    if (m0 <= 1) return;
+    const int L = 32 - __clz(m0 - 1);  // ceil(log2 m0)
+    int start = 0;
+    for (;;) {
+        int v = n / (L * mp);
+        v = v < 1 ? 1 : v;
+        if (s < start + mp * v) break;
+        start += mp * v;
+        mp = mp / 2 < 2 ? 2 : mp / 2;
+        ++p;
+    }
+    i = s - start;
+}
+
+AZ_D int kth_set_bit64(u64 mask, int k) {
+    for (int i = 0; i < k; ++i) mask &= mask - 1;
+    return mask ? __ffsll((long long)mask) - 1 : -1;
+}
+AZ_D u64 first_bits64(int n) { return n >= 64 ? ~0ULL : (1ULL << n) - 1ULL; }
+
+// The mp best by score among the children `prev` of the root, one lane per child and round: N / Q / P [r] are child r * LPG + sub
+// (absent: N = 0, P = 0).  At most 16 rounds of one group maximum each; a NaN score is an error (it equals no maximum).
+AZ_D u64 gumbel_rerank_grp(const EngDev &E, const int (&N)[4], const double (&Q)[4], const double (&P)[4], const uint8_t (&act)[4],
+                           int nch, u64 prev, int mp, u32 gid, int ply, int sub) {
+    double pq[4], pp[4];
+    int mx = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const bool vis = N[r] > 0;
+        pq[r] = vis ? P[r] * Q[r] : 0.0;
+        pp[r] = vis ? P[r] : 0.0;
+        mx = N[r] > mx ? N[r] : mx;
+    }
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) { const int o = __shfl_xor(mx, m, LPG); mx = o > mx ? o : mx; }
+    double num = 0.0, den = 0.0;  // sequential sums in child-index order (an unvisited child adds an exact 0.0)
+    for (int i = 0; i < nch; ++i) {
+        num += __shfl(sel4(pq, i >> 4), i & 15, LPG);
+        den += __shfl(sel4(pp, i >> 4), i & 15, LPG);
+    }
+    const double vmix = den > 0.0 ? num / den : 0.0;
+    const double k = (E.g_cvisit + (double)mx) * E.g_cscale;
+    double sc[4];
+    bool nan = false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        sc[r] = -__builtin_inf();
+        if ((prev >> (r * LPG + sub)) & 1ULL) {
+            sc[r] = (gumbel_g(E, gid, ply, act[r]) + az_det_log(P[r])) + k * (N[r] > 0 ? Q[r] : vmix);
+            nan |= sc[r] != sc[r];
+        }
+    }
+    if (grp_ballot(nan) != 0 && sub == 0) atomicOr(E.err, ERR_INTERNAL);
+    u64 avail = prev, sel = 0;
+    for (int t = 0; t < mp; ++t) {
+        double mine = -__builtin_inf();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if ((avail >> (r * LPG + sub)) & 1ULL) mine = fmax(mine, sc[r]);
+        const double best = grp_max(mine);
+        int idx = -1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const u32 b = grp_ballot(((avail >> (r * LPG + sub)) & 1ULL) && sc[r] == best);
+            if (idx < 0 && b) idx = r * LPG + __ffs((int)b) - 1;
+        }
+        if (idx < 0) break;  // nothing left that compares: NaN scores, reported above
+        sel |= 1ULL << idx;
+        avail &= ~(1ULL << idx);
+    }
+    return sel;
+}
+
+// One lock-step of the search in the Gumbel mode: k_step with the root's child taken from the Sequential Halving schedule instead
+// of pick_child_vl_grp and without root noise.  BACKUP and everything from the root's child downwards are k_step's.
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_gumbel(EngDev E, int sim, int n_sim, int g0, int g1) {
+    const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && g0 == 0) { E.batch_cnt[(sim + 1) & 1] = 0; if (!SELECT) E.batch_cnt[2] = 0; }
+    // inert groups beyond the last slot stay in the kernel: every barrier below is reached once by every wave (see k_step)
+    const bool in_range = g < g1;
+    const int gs = in_range ? g : g1 - 1;
+    Node *pool = pool_of(E, gs);
+    const int st = (BACKUP && in_range) ? E.leaf_status[gs] : LS_NONE;
+    const int leaf = BACKUP ? E.leaf[gs] : 0;
+    const BB lb = {BACKUP ? E.leaf_p1[gs] : 0, BACKUP ? E.leaf_m1[gs] : 0, BACKUP ? E.leaf_player[gs] : 1};
+    const int row_prev = BACKUP ? E.row_of_slot[gs] : 0;
+    const int plen_prev = BACKUP ? E.path_len[gs] : 0;
+    const int path_prev = BACKUP ? E.path[(size_t)gs * LPG + sub] : 0;
+    const int lwin = BACKUP ? E.leaf_winner[gs] : 0;
+    int n_nodes = E.n_nodes[gs];
+    int evals = E.evals[gs];
+    bool active = in_range && searches(E, gs);
+    const int ply = E.ply[gs];
+    BB b = {E.root_p1[gs], E.root_m1[gs], E.root_player[gs]};
+    int node = E.root[gs];
+    u64 mask = SELECT ? E.gmask[gs] : 0;
+    const u32 gid = E.game_id[gs];
+    Node fwd;
+    bool have_root = false;
+    if (BACKUP && st != LS_NONE) {
+        Node mine;
+        const bool on_path = plen_prev <= LPG && sub < plen_prev;
+        if (on_path) mine = load_node(pool + path_prev);
+        double outcome;
+        bool ok = true;
+        if (st == LS_EVAL) {
+            const float v = E.value[row_prev];
+            int k = create_children_grp(E, g, pool, n_nodes, leaf, lb, E.probs + (size_t)row_prev * E.A, sub);
+            ok = k > 0;
+            n_nodes += ok ? k : 0;
+            outcome = (double)lb.player * (double)v;  // base.py:366
+            if (ok) evals += 1;
+            else { active = false; if (sub == 0) E.active[g] = 0; }
+        } else {
+            outcome = (double)lwin;
+        }
+        if (ok) {
+            bool fast = back_propagate_grp(pool, plen_prev, path_prev, mine, leaf, lb.player, outcome, sub);
+            if (fast && SELECT) {  // lane 0 holds the root (path[0]) with its new visit count: forward it
+                fwd.N = __shfl(mine.N, 0, LPG);
+                fwd.first = __shfl(mine.first, 0, LPG);
+                set_node_tail(fwd, (u32)__shfl((int)node_tail(mine), 0, LPG));
+                fwd.Q = 0.0; fwd.P = 0.0; fwd.parent = -1;
+                have_root = (leaf != node) || st != LS_EVAL;
+            }
+        }
+        if (sub == 0) E.leaf_status[g] = LS_NONE;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    if (BACKUP && sub == 0 && in_range) E.evals[g] = evals;
+    if (!SELECT) return;
+    // From here on no group may leave early: the leaf rows are handed out per block (alloc_rows_block) behind workgroup barriers.
+    int status = LS_NONE, w = 0;
+    Walk wk = {b, Node(), node, 1, sub == 0 ? node : -1, false};
+    if (active) {
+        if (have_root) wk.cur = fwd; else wk.cur = load_node(pool + node);
+        // the root's step of select_node (walk_grp's first turn) with the scheduled child
+        bool fresh = false, stop = false;
+        if (!(wk.cur.flags & F_EXPANDED)) {
+            if (wk.cur.flags & F_TERMINAL) stop = true;
+            else if (!(wk.cur.flags & F_EVALUATED)) { wk.bad = true; stop = true; }
+            else {
+                wk.cur.flags |= F_EXPANDED;
+                if (sub == 0) pool[wk.node].flags = wk.cur.flags;
+                fresh = true;
+            }
+        }
+        if (!stop && wk.cur.nch == 0) { wk.bad = true; stop = true; }  // an expanded node always has children
+        if (!stop) {
+            const int nch = wk.cur.nch;
+            int p, mp, i;
+            gumbel_phase(sim, n_sim, nch < E.gm ? nch : E.gm, p, mp, i);
+            Scored s;
+            double cQ[4], cP[4];
+            uint8_t cact[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                Node c;
+                cQ[r] = 0.0; cP[r] = 0.0; cact[r] = 0;
+                if (load_child_grp(pool, wk.cur, r, sub, s, c)) { cQ[r] = c.Q; cP[r] = c.P; cact[r] = c.act; }
+            }
+            const u64 all = first_bits64(nch);
+            if (i == 0) {  // a phase starts: the candidates are ranked again
+                mask = mp == 1 ? 1ULL : gumbel_rerank_grp(E, s.N, cQ, cP, cact, nch, p == 0 ? all : (mask & all), mp, gid, ply, sub);
+                if (sub == 0) E.gmask[g] = mask;
+            }
+            int c = kth_set_bit64(mask & all, i % mp);
+            if (c < 0) { c = 0; if (sub == 0) atomicOr(E.err, ERR_INTERNAL); }
+            const int rsel = c >> 4, lsel = c & (LPG - 1);
+            Node ch;  // the chosen child's header, from the lane that loaded it
+            ch.N = __shfl(pick4(s.N[0], s.N[1], s.N[2], s.N[3], rsel), lsel, LPG);
+            ch.first = __shfl(pick4(s.first[0], s.first[1], s.first[2], s.first[3], rsel), lsel, LPG);
+            set_node_tail(ch, (u32)__shfl(pick4((int)s.tail[0], (int)s.tail[1], (int)s.tail[2], (int)s.tail[3], rsel), lsel, LPG));
+            ch.Q = 0.0; ch.P = 0.0; ch.parent = 0;
+            wk.node = wk.cur.first + c; wk.cur = ch;
+            if (sub == wk.plen) wk.my_path = wk.node;
+            ++wk.plen;
+            az_play_grp(E.gd, wk.b, wk.cur.act, sub);
+            if (!(fresh || wk.cur.N == 0)) {
+                const int no_walkers[MLB] = {};
+                walk_grp(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
+            }
+        }
+        E.path[(size_t)g * LPG + sub] = wk.my_path;
+        if (sub == 0) { E.path_len[g] = wk.plen; if (wk.plen > LPG) atomicMax(E.max_path, wk.plen); }
+        status = classify_leaf_grp(E, pool, wk, w, sub);
+    }
+    const int row = __shfl(alloc_rows_block(E.batch_cnt + (sim & 1), status == LS_EVAL && sub == 0), 0, LPG);
+    if (status == LS_EVAL) {
+        write_nn_input_grp(E, row, wk.b, sub);
+        if (sub == 0) E.row_of_slot[g] = row;
+    }
+    if (sub == 0 && in_range) {
+        if (active) {
+            E.leaf[g] = wk.node; E.leaf_p1[g] = wk.b.p1; E.leaf_m1[g] = wk.b.m1; E.leaf_player[g] = (int8_t)wk.b.player;
+            E.leaf_winner[g] = (int8_t)w;
+        }
+        E.leaf_status[g] = (int8_t)status;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // TreeEval.ROLLOUT (BASELINE config 1, the reference's default evaluation opponent): one whole simulation per
 // launch -- UCT selection (mcts.py:38-42, 134-135), expansion with a uniformly random child (mcts.py:152-154,
 // 163-165), random playout to the end of the game (mcts.py:173-180), back-propagation (mcts.py:197-223).
@@ -894,9 +1135,51 @@ AZ_D double linear_temp(int step, int tmax, int tmin) {  // schedulers.py:33-40
 
 // get_action_probs (mcts.py:95-116) + the move choice (players.py:184-189) over the root's children pool[fc .. fc + nc): writes
 // pi[action] of every child into the (already zeroed) row `pi` when one is given and returns the index of the chosen child.
-// One lane; sum and running total in child-index order in float64.  k_move (which then plays the move) and k_root_readout (which
+// One lane; sum and running total in child-index order in float64.  In the Gumbel mode (az_engine_set_gumbel) move and policy are
+// gumbel_move_policy's, whatever the temperature.  k_move (which then plays the move) and k_root_readout (which
 // only reports it) both call this, so what a readout shows is what an advance would record and play.
-AZ_D int move_policy(const EngDev &E, const Node *pool, int fc, int nc, double temp, u32 gid, int ply, float *pi) {
+// Gumbel mode (the contract above k_step_gumbel): the move is the best score among the candidates `gmask` (0: all children) on the
+// statistics as they stand, pi the softmax of logit + sigma over all children; the temperature plays no part.
+AZ_D int gumbel_move_policy(const EngDev &E, const Node *pool, int fc, int nc, u64 gmask, u32 gid, int ply, float *pi) {
+    double num = 0.0, den = 0.0;
+    int maxN = 0;
+    for (int i = 0; i < nc; ++i) {
+        const int n = pool[fc + i].N;
+        if (n > 0) { const double P = pool[fc + i].P; num += P * pool[fc + i].Q; den += P; }
+        maxN = n > maxN ? n : maxN;
+    }
+    const double vmix = den > 0.0 ? num / den : 0.0;
+    const double k = (E.g_cvisit + (double)maxN) * E.g_cscale;
+    gmask &= first_bits64(nc);
+    if (gmask == 0) gmask = first_bits64(nc);
+    double xmax = -__builtin_inf(), best = -__builtin_inf();
+    int pick = -1;
+    bool nan = false;
+    for (int i = 0; i < nc; ++i) {
+        const double logit = az_det_log(pool[fc + i].P);
+        const double sigma = k * (pool[fc + i].N > 0 ? pool[fc + i].Q : vmix);
+        const double x = logit + sigma;
+        nan |= x != x;
+        xmax = fmax(xmax, x);
+        if ((gmask >> i) & 1ULL) {
+            const double sc = (gumbel_g(E, gid, ply, pool[fc + i].act) + logit) + sigma;
+            if (sc != sc) nan = true;
+            else if (pick < 0 || sc > best) { best = sc; pick = i; }
+        }
+    }
+    if (nan || pick < 0) { atomicOr(E.err, ERR_INTERNAL); pick = pick < 0 ? 0 : pick; }
+    if (pi) {
+        double sum = 0.0;
+        for (int i = 0; i < nc; ++i)
+            sum += az_det_exp((az_det_log(pool[fc + i].P) + k * (pool[fc + i].N > 0 ? pool[fc + i].Q : vmix)) - xmax);
+        for (int i = 0; i < nc; ++i)
+            pi[pool[fc + i].act] = (float)(az_det_exp((az_det_log(pool[fc + i].P) + k * (pool[fc + i].N > 0 ? pool[fc + i].Q : vmix)) - xmax) / sum);
+    }
+    return pick;
+}
+
+AZ_D int move_policy(const EngDev &E, const Node *pool, int fc, int nc, double temp, u32 gid, int ply, u64 gmask, float *pi) {
+    if (E.gm > 0) return gumbel_move_policy(E, pool, fc, nc, gmask, gid, ply, pi);
     if (temp == 0.0) {  // fair_max by N
         int best = -1, cnt = 0, first = 0;
         for (int i = 0; i < nc; ++i) {
@@ -960,7 +1243,8 @@ __global__ void k_move(EngDev E) {
     int *vis = si >= 0 ? E.o_visits + (size_t)si * E.A : nullptr;
     if (si >= 0) for (int a = 0; a < E.A; ++a) { pi[a] = 0.0f; vis[a] = 0; }
 
-    const int chosen = fc + move_policy(E, pool, fc, nc, temp, gid, ply, pi);
+    const int chosen = fc + move_policy(E, pool, fc, nc, temp, gid, ply, E.gmask[g], pi);
+    E.gmask[g] = 0;  // the candidates belong to the root that is left here
     int action = pool[chosen].act;
     if (si >= 0) {
         for (int i = 0; i < nc; ++i) vis[pool[fc + i].act] = pool[fc + i].N;
@@ -1077,6 +1361,7 @@ __global__ void k_apply_moves(EngDev E, const int *actions, int n, int *status) 
     E.root[g] = chosen;
     E.ply[g] = E.ply[g] + 1;
     E.leaf_status[g] = LS_NONE;
+    E.gmask[g] = 0;
     int w = 0;
     if (az_status(gd, b, &w)) E.active[g] = 0;  // finished: the board stays readable, the slot is no longer searched
     status[g] = AZ_OK;
@@ -1171,7 +1456,7 @@ __global__ __launch_bounds__(256) void k_root_readout(EngDev E, int n, const dou
         if (served && (o.pi || o.action)) {
             const int ply = E.ply[g];
             const double temp = temps ? temps[g] : linear_temp(ply, E.tmax, E.tmin);
-            act = pool[fc + move_policy(E, pool, fc, nc, temp, E.game_id[g], ply, o.pi ? o.pi + (size_t)g * A : nullptr)].act;
+            act = pool[fc + move_policy(E, pool, fc, nc, temp, E.game_id[g], ply, E.gmask[g], o.pi ? o.pi + (size_t)g * A : nullptr)].act;
         }
         if (o.action) o.action[g] = act;
         if (o.root_N) o.root_N[g] = served ? rn.N : 0;
@@ -1492,6 +1777,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.noise_mode = cfg->noise_mode; d.tmax = cfg->temp_max_step; d.tmin = cfg->temp_min_step; d.seed = cfg->seed;
     d.sample_cap = cfg->sample_capacity;
     d.K = 1; e->net_rows = d.G;
+    d.gm = 0; d.g_cvisit = 0.0; d.g_cscale = 0.0; d.g_scale = 0.0;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -1503,6 +1789,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     A_(samp_idx, G * (size_t)d.max_plies);
     A_(o_state, S * gd.cells); A_(o_pi, S * gd.A); A_(o_z, S); A_(o_meta, S * 4); A_(o_visits, S * gd.A);
     A_(ctr, CTR_ALLOC); A_(err, 1); A_(max_nodes, 1); A_(max_path, 1);
+    A_(gmask, G);
 #undef A_
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_a, G);
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_b, G);
@@ -1616,6 +1903,16 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
         AZ_HIP(hipGetLastError());
         return AZ_OK;
     }
+    if (d.gm > 0) {  // the Gumbel root search: k_step's launch sequence with k_step_gumbel
+        for (int s = 0; s < n_sim; ++s) {
+            if (s == 0) hipLaunchKernelGGL((k_step_gumbel<false, true>), gg, gb, 0, e->stream, d, s, n_sim, 0, d.G);
+            else hipLaunchKernelGGL((k_step_gumbel<true, true>), gg, gb, 0, e->stream, d, s, n_sim, 0, d.G);
+            AZ_TRY(forward(e, d.batch_cnt + (s & 1), cap, s));
+        }
+        hipLaunchKernelGGL((k_step_gumbel<true, false>), gg, gb, 0, e->stream, d, n_sim, n_sim, 0, d.G);
+        AZ_HIP(hipGetLastError());
+        return AZ_OK;
+    }
     for (int s = 0; s < n_sim; ++s) {
         if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
         else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
@@ -1644,7 +1941,8 @@ static int do_search(az_engine *e, int n_sim) {
     const int cap_q = (R >= 4096 && cap < 4096) ? (cap + 511) / 512 * 512 : R;  // below 4096 rows the network picks other kernels
     if (!graphable) return enqueue_search(e, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
     cap = cap_q;
-    const unsigned long long key = ((unsigned long long)n_sim << 32) | (unsigned)cap;
+    // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31)
+    const unsigned long long key = ((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)n_sim << 32) | (unsigned)cap;
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) {
         AZ_HIP(hipGraphLaunch(it->second, e->stream));
@@ -2147,6 +2445,7 @@ extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_leaf_batch: an AZ_EVAL_EXTERNAL engine searches one leaf per lock-step (external evaluator)");
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_ROLLOUT, AZ_EINVAL, "az_engine_set_leaf_batch: a rollout engine (AZ_EVAL_ROLLOUT) evaluates no leaf with a network");
     AZ_REQUIRE(e->sym_mask == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the engine evaluates over a symmetry mask (0x%x); the ensemble does not combine with leaf_batch", e->sym_mask);
+    AZ_REQUIRE(k == 1 || d.gm == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the Gumbel root search is on (az_engine_set_gumbel, m = %d) and searches one leaf per lock-step; switch it off first", d.gm);
     const long long rows = (long long)k * d.G;
     if (e->cfg.evaluator == AZ_EVAL_NET)
         AZ_REQUIRE(rows <= az_net_max_batch(e->net), AZ_EINVAL, "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", k, d.G,
@@ -2180,5 +2479,42 @@ extern "C" int az_engine_collisions(az_engine *e, int64_t *n) {
     AZ_TRY(enter(e));
     AZ_TRY(fetch_counters(e));
     *n = (int64_t)e->h_ctr[CTR_COLLISIONS];
+    return AZ_OK;
+}
+
+// ---- Gumbel root search (k_step_gumbel, gumbel_move_policy) -------------------------------------------------------------
+extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, double c_scale, double gumbel_scale) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_gumbel");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_gumbel");
+    EngDev &d = e->d;
+    AZ_REQUIRE(m >= 0 && m <= AZ_MAX_GUMBEL, AZ_EINVAL, "az_engine_set_gumbel: m must be in [0, %d], got %d", AZ_MAX_GUMBEL, m);
+    if (m == 0 && d.gm == 0) return AZ_OK;
+    if (m > 0) {
+        AZ_REQUIRE(c_visit >= 0.0 && c_visit <= 1.79769313486231570815e308 && c_scale >= 0.0 && c_scale <= 1.79769313486231570815e308 &&
+                   gumbel_scale >= 0.0 && gumbel_scale <= 1.79769313486231570815e308, AZ_EINVAL,
+                   "az_engine_set_gumbel: c_visit, c_scale and gumbel_scale must be finite and >= 0, got %g, %g, %g", c_visit, c_scale, gumbel_scale);
+        AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_ROLLOUT, AZ_EINVAL, "az_engine_set_gumbel: a rollout engine (AZ_EVAL_ROLLOUT) has no priors to sample the root's actions from");
+        AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_gumbel: an AZ_EVAL_EXTERNAL engine searches with the PUCT root only");
+        AZ_REQUIRE(e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_gumbel: leaf_batch %d > 1 is in force (az_engine_set_leaf_batch); the Gumbel root search takes one leaf per lock-step", e->leaf_batch);
+    }
+    AZ_TRY(enter(e));
+    AZ_HIP(hipMemsetAsync(d.gmask, 0, sizeof(u64) * (size_t)d.G, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    d.gm = m;
+    d.g_cvisit = m > 0 ? c_visit : 0.0; d.g_cscale = m > 0 ? c_scale : 0.0; d.g_scale = m > 0 ? gumbel_scale : 0.0;
+    // the launch sequence of a search changes: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_gumbel_considered(az_engine *e, int32_t slot, uint64_t *mask) {
+    AZ_REQUIRE(e && mask, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_gumbel_considered");
+    AZ_USABLE(e, "az_engine_gumbel_considered");
+    AZ_REQUIRE(slot >= 0 && slot < e->d.G, AZ_EINVAL, "slot %d outside [0, %d)", slot, e->d.G);
+    AZ_TRY(enter(e));
+    AZ_HIP(hipMemcpyAsync(mask, e->d.gmask + slot, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
     return AZ_OK;
 }

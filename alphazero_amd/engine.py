@@ -364,6 +364,22 @@ class SelfPlayEngine:
         check(lib().az_engine_collisions(self.h, C.byref(n)))
         return n.value
 
+    def set_gumbel(self, gumbel):
+        """the Gumbel root search (az_engine_set_gumbel; alphazero_amd.gumbel.parse: None = off, an int m or a dict of m, c_visit,
+        c_scale, gumbel_scale): Sequential Halving over m root actions sampled with Gumbel noise, the move and the policy target
+        from the completed Q-values.  EVAL_NET / EVAL_FAKE engines at leaf_batch 1; combines with the symmetry modes."""
+        from .gumbel import parse
+        g = parse(gumbel)
+        m, cv, cs, gs = (0, 0.0, 0.0, 0.0) if g is None else g
+        check(lib().az_engine_set_gumbel(self.h, m, cv, cs, gs))
+
+    def considered(self, slot=0):
+        """the root children the slot's Sequential Halving considers now, as ascending child indices ([]: none chosen yet, which
+        reads as all children)"""
+        mask = C.c_uint64()
+        check(lib().az_engine_gumbel_considered(self.h, int(slot), C.byref(mask)))
+        return [i for i in range(64) if (mask.value >> i) & 1]
+
     def run(self, n_games, first_game_id=0):
         """plays n_games to completion; returns the samples as a dict of CUDA tensors (copies)."""
         self._evaluated(lib().az_engine_run(self.h, first_game_id, n_games))

@@ -55,6 +55,8 @@ def check_symmetry(symmetry, nn):
 
 MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
 
+from .gumbel import check_gumbel  # noqa: E402  (the Gumbel root search's spec and refusals)
+
 
 def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
     """the walkers per lock-step of `leaf_batch` (None: 1); ValueError -- before any device work -- for a bool, a non-integer or a
@@ -85,7 +87,7 @@ def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
 
 class MCT:
     def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None,
-                 leaf_batch=None):
+                 leaf_batch=None, gumbel=None):
         self.n_rollouts = 0
         self.simulation_time = 0
         self.eval_method = TreeEval.to_dict()["rollout" if eval_method is None else eval_method]
@@ -111,6 +113,11 @@ class MCT:
         # simulations per lock-step, kept apart by virtual loss (None / 1: the reference's sequential search); HIP-routed networks only
         self.leaf_batch = leaf_batch
         check_leaf_batch(leaf_batch, self._nn, symmetry, self.eval_method == TreeEval.NEURAL)
+        # the Gumbel root search (alphazero_amd.gumbel: None = off, an int m or a dict): Sequential Halving at the root, move and
+        # action probabilities from the completed Q-values; n_sim searches on HIP-routed networks at leaf_batch 1 only
+        self.gumbel = gumbel
+        self._engine_gumbel = None    # the spec the engine is set to
+        check_gumbel(gumbel, self._nn, leaf_batch, self.eval_method == TreeEval.NEURAL)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -123,6 +130,7 @@ class MCT:
             raise ValueError(f"Trying to set a neural network for the MCT but the evaluation method is {self.eval_method}")
         check_symmetry(self.symmetry, nn)
         check_leaf_batch(self.leaf_batch, nn, self.symmetry)
+        check_gumbel(self.gumbel, nn, self.leaf_batch)
         self._nn = nn
         self._hipnet = None
         self._evaluator = None
@@ -137,6 +145,7 @@ class MCT:
         start = time()
         if n_sim is None and compute_time is None:
             raise ValueError("MCT.search needs to have either n_sim or compute_time specified.")
+        check_gumbel(self.gumbel, self._nn, self.leaf_batch, self.eval_method == TreeEval.NEURAL, compute_time)
         self._sync_device_root(board, n_sim)
         if n_sim is not None:
             self._ensure_room(n_sim)
@@ -162,6 +171,15 @@ class MCT:
         counts = {_move_of(board, int(ai)): int(ni) for ai, ni in zip(a, n)}
         if len(counts) == 0:
             return {board.pass_move: 1.}
+        if self.gumbel is not None:
+            # the move and the improved policy of the Gumbel root search, as the engine would record and play them (a one-row
+            # readout); a temperature other than 0 returns the policy, renormalised in float64 for the caller's draw
+            r = self._engine.root_readout(temps=0, n=1)
+            if temp == 0:
+                return {_move_of(board, int(r["action"][0])): 1}, counts
+            pi = r["pi"][0].cpu().numpy().astype(np.float64)
+            total = float(sum(pi[int(ai)] for ai in a))
+            return {_move_of(board, int(ai)): float(pi[int(ai)]) / total for ai in a}, counts
         if temp == 0:
             best, _ = fair_max(counts.items(), key=lambda kv: kv[1])
             return {best: 1}, counts
@@ -237,10 +255,15 @@ class MCT:
             self._engine_board = (board.game, H, W)
             self._plies = 0
             self._engine_lb = 1
+            self._engine_gumbel = None
         lb = check_leaf_batch(self.leaf_batch, self._nn if neural else None, self.symmetry, neural)
         if self._engine_lb != lb:
             self._engine.set_leaf_batch(lb)
             self._engine_lb = lb
+        gum = check_gumbel(self.gumbel, self._nn if neural else None, self.leaf_batch, neural)
+        if self._engine_gumbel != gum:
+            self._engine.set_gumbel(self.gumbel)
+            self._engine_gumbel = gum
         key = (board.grid.astype(np.int8).tobytes(), int(board.player))
         if key != self._root_key:  # tree restarted from an unexplored state (mcts.py:124-125, 231-233)
             self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8),

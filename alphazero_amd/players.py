@@ -7,6 +7,7 @@ from time import sleep
 import numpy as np
 
 from .base import Player
+from .gumbel import check_gumbel
 from .mcts import MCT, _action_of, _move_of, check_leaf_batch, check_symmetry
 from .utils import fair_max
 
@@ -81,10 +82,16 @@ class MCTSPlayer(Player):
 
 class AlphaZeroPlayer(MCTSPlayer):
     def __init__(self, n_sim=None, compute_time=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, verbose=False,
-                 symmetry=None, leaf_batch=None):
+                 symmetry=None, leaf_batch=None, gumbel=None):
         super().__init__(n_sim=n_sim, compute_time=compute_time, verbose=verbose)
+        check_gumbel(gumbel, nn, leaf_batch, True, compute_time)
         self.mct = MCT(eval_method="neural", nn=nn, dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
-                       symmetry=symmetry, leaf_batch=leaf_batch)
+                       symmetry=symmetry, leaf_batch=leaf_batch, gumbel=gumbel)
+
+    @property
+    def gumbel(self):
+        """the Gumbel root search's spec (alphazero_amd.gumbel; None: the PUCT root)"""
+        return self.mct.gumbel
 
     @property
     def symmetry(self):
@@ -100,15 +107,16 @@ class AlphaZeroPlayer(MCTSPlayer):
         return AlphaZeroPlayer(n_sim=self.n_sim, compute_time=self.compute_time,
                                nn=self.mct.nn.clone() if self.mct.nn is not None else None,
                                dirichlet_alpha=self.mct.dirichlet_alpha, dirichlet_epsilon=self.mct.dirichlet_epsilon,
-                               verbose=self.verbose, symmetry=self.mct.symmetry, leaf_batch=self.mct.leaf_batch)
+                               verbose=self.verbose, symmetry=self.mct.symmetry, leaf_batch=self.mct.leaf_batch,
+                               gumbel=self.mct.gumbel)
 
     def reset(self):
         old = self.mct
         self.mct = MCT(eval_method="neural", nn=old.nn, dirichlet_alpha=old.dirichlet_alpha,
-                       dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry, leaf_batch=old.leaf_batch)
+                       dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry, leaf_batch=old.leaf_batch, gumbel=old.gumbel)
         # keep the uploaded weights and the device tree storage: a reset only drops the tree
         self.mct._hipnet, self.mct._engine, self.mct._engine_board = old._hipnet, old._engine, old._engine_board
-        self.mct._engine_lb = old._engine_lb
+        self.mct._engine_lb, self.mct._engine_gumbel = old._engine_lb, old._engine_gumbel
         self.mct._evaluator = old._evaluator  # the carried engine calls it (external evaluation, evaluators.route)
         if self.mct._engine is not None:
             self.mct._plies = 0
@@ -135,6 +143,7 @@ class BatchedMCTSPlayer(Player):
             raise ValueError("n_slots must be a positive integer")
         self.n_sim, self.n_slots = int(n_sim), int(n_slots)
         self.nn, self.dirichlet_alpha, self.dirichlet_epsilon, self.symmetry, self.leaf_batch = None, None, None, None, None
+        self.gumbel = None
         self._seed = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         self._engine = None           # n_slots device trees
         self._engine_board = None     # (game, H, W) the engine was built for
@@ -216,6 +225,9 @@ class BatchedMCTSPlayer(Player):
             self._engine.set_symmetry(("random", sym) if parse(self.symmetry)[1] else sym)
         if lb > 1:
             self._engine.set_leaf_batch(lb)
+        if neural and self.gumbel is not None:
+            check_gumbel(self.gumbel, self.nn, self.leaf_batch)
+            self._engine.set_gumbel(self.gumbel)
         self._engine_board = (first.game, H, W)
 
     def _sync(self, boards, first):
@@ -311,7 +323,7 @@ class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
     _eval_method = "neural"
 
     def __init__(self, n_sim=None, nn=None, n_slots=1, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, verbose=False,
-                 symmetry=None, leaf_batch=None):
+                 symmetry=None, leaf_batch=None, gumbel=None):
         super().__init__(n_sim=n_sim, n_slots=n_slots, seed=seed, verbose=verbose)
         self.nn, self.dirichlet_alpha, self.dirichlet_epsilon = nn, dirichlet_alpha, dirichlet_epsilon
         # leaf evaluations averaged over the board's symmetries (alphazero_amd.symmetry; None: off); HIP-routed networks only
@@ -320,6 +332,10 @@ class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
         # simulations per lock-step and game, kept apart by virtual loss (None / 1: the sequential search); HIP-routed networks only
         self.leaf_batch = leaf_batch
         check_leaf_batch(leaf_batch, nn, symmetry)
+        # the Gumbel root search (alphazero_amd.gumbel: None = off, an int m or a dict): get_moves then returns its move and, at a
+        # temperature other than 0, its improved policy; HIP-routed networks at leaf_batch 1 only
+        self.gumbel = gumbel
+        check_gumbel(gumbel, nn, leaf_batch)
 
 
 PLAYERS_SET = {"human", "random", "greedy", "mcts", "alphazero"}

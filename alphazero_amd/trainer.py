@@ -61,7 +61,8 @@ def augment(memory, nn, strategy):
 class AlphaZeroTrainer:
     DEFAULT_EXP_NAME = "alphazero-undefined"
 
-    def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None):
+    def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
+                 selfplay_gumbel=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -85,6 +86,11 @@ class AlphaZeroTrainer:
         # (alphazero_amd.symmetry); the ensemble is for play and analysis, not for the self-play wave, and is refused
         self.selfplay_symmetry = selfplay_symmetry
         self._check_selfplay_symmetry()
+        # the self-play wave searched with the Gumbel root search: None (off), an int m or a dict (alphazero_amd.gumbel); the samples'
+        # pi is then the policy improved by the completed Q-values.  Config stays pinned to the reference.
+        self.selfplay_gumbel = selfplay_gumbel
+        from .gumbel import parse as parse_gumbel
+        parse_gumbel(selfplay_gumbel)
 
     def _check_selfplay_symmetry(self):
         from .symmetry import parse
@@ -192,6 +198,11 @@ class AlphaZeroTrainer:
             self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
         elif sym is not None or self._engine._sym_mode is not None:
             self._engine.set_symmetry(sym)
+        from .gumbel import check_gumbel
+        gum = check_gumbel(self.selfplay_gumbel, self.nn)  # ValueError for a network routed to the external evaluator
+        if gum != getattr(self._engine, "_gumbel_spec", None):
+            self._engine.set_gumbel(self.selfplay_gumbel)
+            self._engine._gumbel_spec = gum
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

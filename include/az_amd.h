@@ -286,6 +286,47 @@ int az_engine_set_symmetry_random(az_engine *e, int32_t mask);
 int az_engine_set_leaf_batch(az_engine *e, int32_t k);
 int az_engine_collisions(az_engine *e, int64_t *n);
 
+/* Gumbel root search ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022): the root samples m actions
+ * without replacement with Gumbel noise, spends the simulations of a search on them by Sequential Halving, and is read out as the
+ * policy improved by the completed Q-values instead of the visit counts -- the form that still improves the policy at 8 to 32
+ * simulations.  A different search from the reference's: opt-in, m = 0 (the default) is off, when every launch and every bit are
+ * the plain ones; 1 <= m <= AZ_MAX_GUMBEL switches it on.  Python's defaults: m 16, c_visit 50, c_scale 0.5 (Q is in [-1, 1] here:
+ * the paper's c_scale 1 on values in [0, 1]), gumbel_scale 1; gumbel_scale 0 is a deterministic search for evaluation play.
+ * While it is on no root noise is applied (F_NOISED stays clear), the move ignores the temperature schedule, and the walk below
+ * the root is the plain PUCT walk.  Contract -- the root's children 0 .. nch - 1 in child-index order, float64, one operation at
+ * a time:
+ *   logit(a) = az_det_log of P(a)                   (the engine's deterministic log; -inf for P = 0)
+ *   g(a)     = 0.0 when gumbel_scale == 0 (no draw); else gumbel_scale * (-L(-L(u))) with L = az_det_log,
+ *              r = Philox4x32-10 keyed (seed, game_id) at counter (ply, 0xFFFF, AZ_P_GUMBEL = 9, action(a)),
+ *              u = the 53-bit uniform az_u53 of (r.x, r.y), replaced by 2^-53 when 0: one draw per (game, ply, action), the same in every phase and
+ *              every search call on that root, never a function of slot, row or batch shape
+ *   vmix     = (sum over N(b) > 0 of P(b) Q(b)) / (sum over N(b) > 0 of P(b)), both in child-index order; 0.0 when no child is
+ *              visited (or the divisor is 0).  The root's own network value is discarded, as the reference discards it: this is
+ *              the visited-children term of the paper's v_mix alone
+ *   cq(a)    = N(a) > 0 ? Q(a) : vmix               (Q is in the root mover's frame)
+ *   maxN     = max N(b), the real counts, visits kept by a re-rooting included
+ *   sigma(a) = ((c_visit + (double)maxN) * c_scale) * cq(a)
+ *   score(a) = (g(a) + logit(a)) + sigma(a)
+ * Schedule, a pure function of (n, m0) with n the n_sim of the search call and m0 = min(m, nch); every search call runs a whole
+ * schedule over the root's statistics as they stand.  m0 = 1: all simulations to child 0.  Otherwise L = ceil(log2 m0); phase p
+ * considers m_p candidates, m_0 = m0, m_{p+1} = max(2, m_p / 2), for v_p = max(1, n / (L m_p)) rounds (integer divisions) of one
+ * visit per candidate; phases follow each other until n simulations are dealt: the phase of two repeats, the last phase is cut.
+ * At the first simulation of a phase the candidates become the m_p best by score of the previous set (phase 0: of all children),
+ * ties -- among -inf too -- to the lowest child index whatever the tie mode; simulation i of a phase goes to candidate i mod m_p in
+ * ascending child index.  The root is expanded as ever (first visit, then the walk stops at the child).
+ * Move (az_engine_advance, az_engine_root_readout): the candidate of the slot's current set with the highest score on the final
+ * statistics, lowest index among equals; an empty set (after this setter, after a move) means all children.  Policy target:
+ * pi'(a) = E(x(a) - max x) / sum with E = az_det_exp, x(a) = logit(a) + sigma(a) (no g), the sum in child-index order, stored as float32 where
+ * the visit-count policy is stored (the samples' pi, d_pi of the readout); the visits stay the visit counts.  A NaN score is
+ * reported like a NaN PUCT score.  az_engine_best_moves stays visit-based.
+ * AZ_EINVAL: m outside [0, AZ_MAX_GUMBEL]; with m > 0 a constant that is negative or not finite, an AZ_EVAL_ROLLOUT or
+ * AZ_EVAL_EXTERNAL engine, leaf_batch > 1 in force (az_engine_set_leaf_batch(k > 1) in turn refuses while this mode is on);
+ * AZ_ESTATE while a search is open.  The cached search graphs are dropped and the slots' candidate sets cleared; the symmetry
+ * modes act on network rows and combine.  az_engine_gumbel_considered reads a slot's candidate set (bit i = child i). */
+#define AZ_MAX_GUMBEL 16
+int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, double c_scale, double gumbel_scale);
+int az_engine_gumbel_considered(az_engine *e, int32_t slot, uint64_t *mask);
+
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
  * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves
