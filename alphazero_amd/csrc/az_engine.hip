@@ -5,7 +5,8 @@
 // per-game semantics equal the reference's MCT.search (mcts.py:226-269) exactly -- no virtual loss.  (Opt-in, default off:
 // az_engine_set_leaf_batch walks K simulations per game and lock-step with virtual loss -- k_step_multi below, another search.)
 // (Opt-in, default off: az_engine_set_gumbel replaces the root's PUCT pick by Sequential Halving over actions sampled with Gumbel
-// noise and reads the root out by the completed Q-values -- k_step_gumbel below, another search again.)
+// noise and reads the root out by the completed Q-values -- k_step_gumbel below, another search again; az_engine_set_gumbel_batch
+// walks up to K simulations of a Sequential Halving phase per game and lock-step -- k_step_gumbel_multi.)
 //
 // HBM layout
 //   boards   : 2 x u64 bitboards + int8 side-to-move per slot (root and current leaf), SoA over slots
@@ -104,6 +105,9 @@ struct EngDev {
     int gm;
     double g_cvisit, g_cscale, g_scale;
     u64 *gmask;
+    // az_engine_set_gumbel_batch (k_step_gumbel_multi; then K above = its walkers): the slot's cursor = the simulations of the search
+    // call already dealt, and the cursor at the start of the slot's current lock-step, [G] each
+    int *gcur, *gstart;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1030,6 +1034,206 @@ __global__ __launch_bounds__(256) void k_step_gumbel(EngDev E, int sim, int n_si
     }
 }
 
+// where the phase that holds simulation s of a search of n ends (first simulation of the next phase, at most n): gumbel_phase's walk
+AZ_D int gumbel_phase_end(int s, int n, int m0) {
+    if (m0 <= 1) return n;
+    const int L = 32 - __clz(m0 - 1);
+    int start = 0, mp = m0;
+    for (;;) {
+        int v = n / (L * mp);
+        v = v < 1 ? 1 : v;
+        start += mp * v;
+        if (s < start) break;
+        mp = mp / 2 < 2 ? 2 : mp / 2;
+    }
+    return start < n ? start : n;
+}
+
+// Several Sequential Halving leaves per network call (az_engine_set_gumbel_batch(K > 1) while the Gumbel mode is on; DESIGN
+// section 17).  Everything not named here is the contract above k_step_gumbel.  The schedule depends on m0 = min(gm, nch) and that
+// differs from slot to slot, so every searching slot keeps a cursor s = the simulations of this search call already dealt:
+//   the search's first launch sets s = 0; a lock-step of the slot runs kt = min(K, end of the current phase - s, n - s) walkers
+//   j = 0 .. kt - 1, walker j is simulation s + j (+ sim_base in every Philox counter), then s += kt.  No lock-step crosses a
+//   phase boundary: a re-ranking (i == 0) can only fall on walker 0 and sees real statistics only, every earlier walker being
+//   backed up.  A root without children, and m0 = 1, take the one phase of n: child 0, ceil(n / K) lock-steps.
+//   The host enqueues Lmax(n, gm, K) = the longest plan of any m0 in 1 .. gm lock-steps (+ the backup-only launch); a slot whose
+//   plan is shorter idles in the rest: kt = 0, LS_NONE for every walker, no rows.
+//   The walkers of a lock-step run in ascending j, one after the other, as k_step_multi's.  Walker j makes k_step_gumbel's root
+//   step -- first-visit expansion with the `fresh` break, child = the (i mod m_p)-th candidate, stop when fresh or the child's
+//   real N == 0 -- with no virtual count (the pick is forced), then descends from depth 1 with pick_child_vl_grp's virtual counts
+//   over the earlier walkers' recorded paths (the root's child is node 1 of a path).  Leaf status, duplicates (LS_DUP + i, counted
+//   in collisions: with K > m_p several walkers share a root child and, while its real N is 0, its pending leaf), backup order,
+//   the bump allocator's order and the fences are k_step_multi's.
+// Every root grows by exactly n visits per search call; the result is a function of (seed, game id, gm, constants, K, n), never of
+// the slot, the slot count or the block; K = 1 never comes here (k_step_gumbel).
+// gcur [G] = the cursor, gstart [G] = its value at the start of the slot's current lock-step (k_sym_pick's simulation index and the
+// number of walkers the next launch backs up: gcur - gstart).  Lane j of the group owns walker j's pending words, as in k_step_multi.
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_gumbel_multi(EngDev E, int t, int n_sim) {
+    const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { E.batch_cnt[(t + 1) & 1] = 0; if (!SELECT) E.batch_cnt[2] = 0; }
+    // groups beyond the last slot stay as inert groups: every __syncthreads() below is reached by every wave once (see k_step)
+    const bool in_range = g < E.G;
+    const int gs = in_range ? g : E.G - 1;
+    Node *pool = pool_of(E, gs);
+    const size_t wj = (size_t)gs * MLB + sub;  // this lane's walker
+    // ---- every per-slot and per-walker word in one batch of independent loads
+    const int cur = BACKUP ? E.gcur[gs] : 0;  // the search's first launch (no BACKUP) starts the cursor at 0
+    int kb = BACKUP ? cur - E.gstart[gs] : 0;  // walkers the slot's previous lock-step selected
+    kb = kb < 0 ? 0 : (kb > MLB ? MLB : kb);
+    const int p_st = (BACKUP && in_range && sub < kb) ? E.m_leaf_status[wj] : LS_NONE;
+    const int p_leaf = BACKUP ? E.m_leaf[wj] : 0;
+    const u64 p_p1 = BACKUP ? E.m_leaf_p1[wj] : 0, p_m1 = BACKUP ? E.m_leaf_m1[wj] : 0;
+    const int p_pl = BACKUP ? E.m_leaf_player[wj] : 1, p_win = BACKUP ? E.m_leaf_winner[wj] : 0;
+    const int p_row = BACKUP ? E.m_row[wj] : 0, p_plen = BACKUP ? E.m_path_len[wj] : 0;
+    int path_cur = (BACKUP && kb > 0) ? E.m_path[(size_t)gs * MLB * LPG + sub] : 0;
+    int n_nodes = E.n_nodes[gs];
+    int evals = E.evals[gs];
+    bool active = in_range && searches(E, gs);
+    const int ply = E.ply[gs];
+    const BB rb = {E.root_p1[gs], E.root_m1[gs], E.root_player[gs]};
+    const int root = E.root[gs];
+    u64 mask = SELECT ? E.gmask[gs] : 0;
+    const u32 gid = E.game_id[gs];
+    if (BACKUP) {  // k_step_multi's, over the slot's own kb
+        double p_out = 0.0;  // lane j: the outcome walker j propagated (a duplicate of j propagates it again)
+        bool dead = false;
+        for (int j = 0; j < kb; ++j) {
+            const int path_next = (j + 1 < kb) ? E.m_path[((size_t)gs * MLB + j + 1) * LPG + sub] : 0;
+            const int st = __shfl(p_st, j, LPG);
+            if (st != LS_NONE && !dead) {
+                const int leaf = __shfl(p_leaf, j, LPG), plen = __shfl(p_plen, j, LPG);
+                const BB lb = {(u64)__shfl((long long)p_p1, j, LPG), (u64)__shfl((long long)p_m1, j, LPG), __shfl(p_pl, j, LPG)};
+                Node mine;
+                const bool on_path = plen <= LPG && sub < plen;
+                if (on_path) mine = load_node(pool + path_cur);
+                double outcome;
+                bool ok = true;
+                if (st == LS_EVAL) {
+                    const int row = __shfl(p_row, j, LPG);
+                    const float v = E.value[row];
+                    int k = create_children_grp(E, g, pool, n_nodes, leaf, lb, E.probs + (size_t)row * E.A, sub);
+                    ok = k > 0;
+                    n_nodes += ok ? k : 0;
+                    outcome = (double)lb.player * (double)v;  // base.py:366
+                    if (ok) evals += 1;
+                    if (sub == j) p_out = outcome;
+                } else if (st >= LS_DUP) {
+                    outcome = __shfl(p_out, st - LS_DUP, LPG);
+                } else {
+                    outcome = (double)__shfl(p_win, j, LPG);
+                }
+                if (ok) back_propagate_grp(pool, plen, path_cur, mine, leaf, lb.player, outcome, sub);
+                else { dead = true; active = false; if (sub == 0) E.active[g] = 0; }
+                // this walker's stores (other lanes) must be visible to the next walker's loads
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            }
+            path_cur = path_next;
+        }
+        if (sub == 0 && in_range) E.evals[g] = evals;
+        if (!SELECT && in_range) E.m_leaf_status[wj] = LS_NONE;
+    }
+    if (!SELECT) return;
+    // From here on no group may leave early: all walks first, then the rows of the whole block (alloc_rows_block).  No barrier inside
+    // the walker loop, whose length differs from group to group.
+    int k_st = LS_NONE, k_leaf = 0, k_pl = 1, k_w = 0, k_plen = 0;  // lane j: walker j's pending leaf
+    u64 k_p1 = 0, k_m1 = 0;
+    int vpath[MLB];  // vpath[i]: the sub-th node of walker i's path (-1: none)
+#pragma unroll
+    for (int i = 0; i < MLB; ++i) vpath[i] = -1;
+    int kt = 0;
+    if (active && cur < n_sim) {
+        Node rootn = load_node(pool + root);
+        // k_step_gumbel's tests at the root: the same for every walker of the lock-step but `fresh`, which only walker 0 can see
+        const bool unexp = !(rootn.flags & F_EXPANDED);
+        const bool root_term = unexp && (rootn.flags & F_TERMINAL);
+        const bool root_bad = (unexp && !root_term && !(rootn.flags & F_EVALUATED)) || (!root_term && rootn.nch == 0);
+        const bool stop = root_term || root_bad;
+        const int nch = stop ? 0 : rootn.nch;
+        const int m0 = nch < E.gm ? nch : E.gm;
+        const int end = gumbel_phase_end(cur, n_sim, m0);
+        kt = end - cur < E.K ? end - cur : E.K;
+        int p = 0, mp = 1, i0 = 0;
+        Scored s;
+        if (!stop) {
+            gumbel_phase(cur, n_sim, m0, p, mp, i0);
+            double cQ[4], cP[4];
+            uint8_t cact[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                Node c;
+                cQ[r] = 0.0; cP[r] = 0.0; cact[r] = 0;
+                if (load_child_grp(pool, rootn, r, sub, s, c)) { cQ[r] = c.Q; cP[r] = c.P; cact[r] = c.act; }
+            }
+            if (i0 == 0) {  // a phase starts with walker 0: the candidates are ranked again, on real statistics
+                const u64 all = first_bits64(nch);
+                mask = mp == 1 ? 1ULL : gumbel_rerank_grp(E, s.N, cQ, cP, cact, nch, p == 0 ? all : (mask & all), mp, gid, ply, sub);
+                if (sub == 0) E.gmask[g] = mask;
+            }
+            mask &= first_bits64(nch);
+        }
+        int ndup = 0;
+        for (int j = 0; j < kt; ++j) {
+            const int sim = cur + j;
+            Walk wk = {rb, rootn, root, 1, sub == 0 ? root : -1, false};
+            wk.bad = root_bad;
+            if (!stop) {
+                bool fresh = false;
+                if (!(rootn.flags & F_EXPANDED)) {  // walker 0 of the root's first visit
+                    rootn.flags |= F_EXPANDED;
+                    if (sub == 0) pool[root].flags = rootn.flags;
+                    fresh = true;
+                }
+                int c = kth_set_bit64(mask, (i0 + j) % mp);
+                if (c < 0) { c = 0; if (sub == 0) atomicOr(E.err, ERR_INTERNAL); }
+                const int rsel = c >> 4, lsel = c & (LPG - 1);
+                Node ch;  // the chosen child's header, from the lane that loaded it
+                ch.N = __shfl(pick4(s.N[0], s.N[1], s.N[2], s.N[3], rsel), lsel, LPG);
+                ch.first = __shfl(pick4(s.first[0], s.first[1], s.first[2], s.first[3], rsel), lsel, LPG);
+                set_node_tail(ch, (u32)__shfl(pick4((int)s.tail[0], (int)s.tail[1], (int)s.tail[2], (int)s.tail[3], rsel), lsel, LPG));
+                ch.Q = 0.0; ch.P = 0.0; ch.parent = 0;
+                wk.node = rootn.first + c;
+                // an earlier walker of this lock-step went through the same child (K > m_p): its flag stores count, N is still the real one
+                if (j >= mp) set_node_tail(ch, node_tail(load_node(pool + wk.node)));
+                wk.cur = ch;
+                if (sub == wk.plen) wk.my_path = wk.node;
+                ++wk.plen;
+                az_play_grp(E.gd, wk.b, wk.cur.act, sub);
+                if (!(fresh || wk.cur.N == 0)) walk_grp(E, g, pool, vpath, j, ply, sim, sub, wk);
+            }
+            E.m_path[((size_t)g * MLB + j) * LPG + sub] = wk.my_path;
+#pragma unroll
+            for (int i = 0; i < MLB; ++i) vpath[i] = i == j ? wk.my_path : vpath[i];
+            if (wk.plen > LPG && sub == 0) atomicMax(E.max_path, wk.plen);
+            int w = 0;
+            int status = classify_leaf_grp(E, pool, wk, w, sub);
+            if (status == LS_EVAL) {
+                const u32 m = grp_ballot(sub < j && k_st == LS_EVAL && k_leaf == wk.node);  // pending leaf of an earlier walker?
+                if (m) { status = LS_DUP + (__ffs((int)m) - 1); ++ndup; }
+            }
+            if (sub == j) { k_st = status; k_leaf = wk.node; k_p1 = wk.b.p1; k_m1 = wk.b.m1; k_pl = wk.b.player; k_w = w; k_plen = wk.plen; }
+            // flag stores of this walker (F_EXPANDED, F_TERMINAL) must be visible to the next walker's loads
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+        if (ndup > 0 && sub == 0) atomicAdd(&E.ctr[CTR_COLLISIONS], (unsigned long long)ndup);
+    }
+    const int k_row = alloc_rows_block(E.batch_cnt + (t & 1), k_st == LS_EVAL);  // < K * G: at most one row per walker
+    for (int j = 0; j < kt; ++j) {
+        if (__shfl(k_st, j, LPG) == LS_EVAL) {
+            const BB bj = {(u64)__shfl((long long)k_p1, j, LPG), (u64)__shfl((long long)k_m1, j, LPG), __shfl(k_pl, j, LPG)};
+            write_nn_input_grp(E, __shfl(k_row, j, LPG), bj, sub);
+        }
+    }
+    if (in_range) {
+        E.m_leaf_status[wj] = (int8_t)k_st;
+        if (k_st != LS_NONE) {
+            E.m_leaf[wj] = k_leaf; E.m_leaf_p1[wj] = k_p1; E.m_leaf_m1[wj] = k_m1; E.m_leaf_player[wj] = (int8_t)k_pl;
+            E.m_leaf_winner[wj] = (int8_t)k_w; E.m_row[wj] = k_row; E.m_path_len[wj] = k_plen;
+        }
+        if (sub == 0) { E.gstart[g] = cur; E.gcur[g] = cur + kt; }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // TreeEval.ROLLOUT (BASELINE config 1, the reference's default evaluation opponent): one whole simulation per
 // launch -- UCT selection (mcts.py:38-42, 134-135), expansion with a uniformly random child (mcts.py:152-154,
@@ -1635,7 +1839,8 @@ AZ_D void sym_pick_row_grp(const EngDev &E, int row, int code, float *sym_in, ui
     if (sub == 0) sym_code[row] = (uint8_t)code;
 }
 
-// step: -1 the root-prior pass; K == 1: the simulation index k_step was launched with; K > 1: the lock-step t of k_step_multi and its kt
+// step: -1 the root-prior pass; K == 1: the simulation index k_step was launched with; K > 1: the lock-step t of k_step_multi and its kt;
+// Gumbel mode with K > 1 (k_step_gumbel_multi): kt = K, walker j of a slot is simulation gstart[slot] + j, walkers the slot did not run hold LS_NONE
 __global__ __launch_bounds__(256) void k_sym_pick(EngDev E, int mask, int n, int step, int kt, float *sym_in, uint8_t *sym_code) {
     const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     if (g >= E.G) return;
@@ -1649,7 +1854,8 @@ __global__ __launch_bounds__(256) void k_sym_pick(EngDev E, int mask, int n, int
     const size_t wj = (size_t)g * MLB + sub;
     const bool mine = sub < kt && E.m_leaf_status[wj] == LS_EVAL;
     const int my_row = mine ? E.m_row[wj] : -1;
-    const int my_code = mine ? sym_draw(E, g, (u32)E.ply[g], (u32)(step * E.K + sub) + E.sim_base, mask, n) : 0;
+    const int sim0 = E.gm > 0 ? E.gstart[g] : step * E.K;
+    const int my_code = mine ? sym_draw(E, g, (u32)E.ply[g], (u32)(sim0 + sub) + E.sim_base, mask, n) : 0;
     for (int j = 0; j < kt; ++j) {
         const int row = __shfl(my_row, j, LPG), code = __shfl(my_code, j, LPG);
         if (row >= 0) sym_pick_row_grp(E, row, code, sym_in, sym_code, sub);
@@ -1700,6 +1906,8 @@ struct az_engine {
     uint8_t *sym_code = nullptr;
     // az_engine_set_leaf_batch: walkers per slot and lock-step (1: k_step) and the rows nn_in / probs / value hold
     int leaf_batch = 1, net_rows = 0;
+    // az_engine_set_gumbel_batch: the walkers of the Gumbel mode, in force (d.K) only while d.gm > 0
+    int gumbel_batch = 1;
 };
 
 int az_make_game_desc(int game, int H, int W, GameDesc *gd) {
@@ -1789,7 +1997,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     A_(samp_idx, G * (size_t)d.max_plies);
     A_(o_state, S * gd.cells); A_(o_pi, S * gd.A); A_(o_z, S); A_(o_meta, S * 4); A_(o_visits, S * gd.A);
     A_(ctr, CTR_ALLOC); A_(err, 1); A_(max_nodes, 1); A_(max_path, 1);
-    A_(gmask, G);
+    A_(gmask, G); A_(gcur, G); A_(gstart, G);
 #undef A_
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_a, G);
     if (rc == AZ_OK) rc = dev_alloc(e, &e->scr_b, G);
@@ -1877,6 +2085,29 @@ static int forward(az_engine *e, const int *cnt, int cap, int step, int kt = 0) 
     return az_sym_reduce(&d.gd, e->sym_mask, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
 }
 
+// Lmax(n, m, K) of the Gumbel mode with K walkers (the contract above k_step_gumbel_multi; gumbel.locksteps in Python): the longest
+// per-slot plan of any m0 in 1 .. m.  A pure function of its arguments: the launch sequence of a search captures as a graph.
+static int gumbel_locksteps(int n, int m, int K) {
+    int best = 0;
+    for (int m0 = 1; m0 <= m; ++m0) {
+        int L = 0, mp = m0, end = 0, steps = 0;
+        for (int b = m0 - 1; b > 0; b >>= 1) ++L;  // ceil(log2 m0)
+        for (int s = 0; s < n;) {
+            while (end <= s) {  // the phase that holds s
+                if (m0 == 1) { end = n; break; }
+                int v = n / (L * mp);
+                end += mp * (v < 1 ? 1 : v);
+                mp = mp / 2 < 2 ? 2 : mp / 2;
+            }
+            const int stop = end < n ? end : n;
+            s += stop - s < K ? stop - s : K;
+            ++steps;
+        }
+        best = steps > best ? steps : best;
+    }
+    return best;
+}
+
 // MCT.search for every active slot: one root-prior pass (mcts.py:231-233; empty unless a slot holds a
 // fresh root), then n_sim lock-steps of [backup+select -> network].
 // the raw launch sequence of one search; `cap` bounds the network batch (leaf rows are compact: count <= searching slots)
@@ -1891,6 +2122,17 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
     hipLaunchKernelGGL(k_root_prep, gg, gb, 0, e->stream, d, 0, d.G);
     AZ_TRY(forward(e, d.batch_cnt + 2, cap, -1));
     hipLaunchKernelGGL(k_root_init, gg, gb, 0, e->stream, d, 0, d.G);
+    if (d.gm > 0 && d.K > 1) {  // Sequential Halving with K walkers: Lmax lock-steps, cut per slot by its own cursor, then the last backup
+        const int L = gumbel_locksteps(n_sim, d.gm, d.K);
+        for (int t = 0; t < L; ++t) {
+            if (t == 0) hipLaunchKernelGGL((k_step_gumbel_multi<false, true>), gg, gb, 0, e->stream, d, t, n_sim);
+            else hipLaunchKernelGGL((k_step_gumbel_multi<true, true>), gg, gb, 0, e->stream, d, t, n_sim);
+            AZ_TRY(forward(e, d.batch_cnt + (t & 1), cap, t, d.K));
+        }
+        hipLaunchKernelGGL((k_step_gumbel_multi<true, false>), gg, gb, 0, e->stream, d, L, n_sim);
+        AZ_HIP(hipGetLastError());
+        return AZ_OK;
+    }
     if (d.K > 1) {  // ceil(n_sim / K) lock-steps of up to K walkers per slot (k_step_multi), then the backup of the last ones
         const int K = d.K, L = (n_sim + K - 1) / K;
         for (int t = 0; t < L; ++t) {
@@ -1928,8 +2170,8 @@ static int do_search(az_engine *e, int n_sim) {
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL || e->ext_fn, AZ_ESTATE, "AZ_EVAL_EXTERNAL engine without an evaluator (az_engine_set_evaluator)");
     d.sim_base = e->sim_base;
     e->sim_base += (u32)n_sim;
-    e->lockstep_iters += d.rollout ? n_sim : (n_sim + d.K - 1) / d.K + 1;
-    // network rows: every searching slot brings up to K leaves per lock-step (K = 1 unless az_engine_set_leaf_batch)
+    e->lockstep_iters += d.rollout ? n_sim : ((d.gm > 0 && d.K > 1) ? gumbel_locksteps(n_sim, d.gm, d.K) : (n_sim + d.K - 1) / d.K) + 1;
+    // network rows: every searching slot brings up to K leaves per lock-step (K = 1 unless az_engine_set_leaf_batch / _set_gumbel_batch)
     const int R = d.G * d.K;
     int cap = (e->active_bound > 0 && e->active_bound < d.G ? e->active_bound : d.G) * d.K;
     // graph replay needs launch parameters that do not change from search to search: the Philox counter base must be 0
@@ -1941,7 +2183,8 @@ static int do_search(az_engine *e, int n_sim) {
     const int cap_q = (R >= 4096 && cap < 4096) ? (cap + 511) / 512 * 512 : R;  // below 4096 rows the network picks other kernels
     if (!graphable) return enqueue_search(e, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
     cap = cap_q;
-    // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31)
+    // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31).  A change
+    // of K (either setter) drops every graph.
     const unsigned long long key = ((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)n_sim << 32) | (unsigned)cap;
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) {
@@ -2392,6 +2635,7 @@ extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
     AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
     AZ_REQUIRE(mask == 0 || e->symr_mask == 0, AZ_EINVAL, "az_engine_set_symmetry: the engine draws one symmetry per evaluation (az_engine_set_symmetry_random, mask 0x%x); switch that mode off first", (unsigned)e->symr_mask);
     AZ_REQUIRE(mask == 0 || e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with leaf_batch %d > 1 (az_engine_set_leaf_batch)", e->leaf_batch);
+    AZ_REQUIRE(mask == 0 || e->gumbel_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with gumbel_batch %d > 1 (az_engine_set_gumbel_batch)", e->gumbel_batch);
     AZ_REQUIRE((long long)n * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "%d symmetries of %d slots are %lld rows, the network's max_batch is %d", n, d.G, (long long)n * d.G, az_net_max_batch(e->net));
     if (mask == e->sym_mask) return AZ_OK;
@@ -2414,11 +2658,11 @@ extern "C" int az_engine_set_symmetry_random(az_engine *e, int32_t mask) {
     int n = 0;
     AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
     AZ_REQUIRE(mask == 0 || e->sym_mask == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the engine averages over a symmetry mask (az_engine_set_symmetry, mask 0x%x); switch the ensemble off first", (unsigned)e->sym_mask);
-    AZ_REQUIRE((long long)e->leaf_batch * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
-               "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", e->leaf_batch, d.G, (long long)e->leaf_batch * d.G, az_net_max_batch(e->net));
+    AZ_REQUIRE((long long)d.K * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
+               "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", d.K, d.G, (long long)d.K * d.G, az_net_max_batch(e->net));
     if (mask == e->symr_mask) return AZ_OK;
     AZ_TRY(enter(e));
-    if (mask != 0) AZ_TRY(sym_reserve(e, e->leaf_batch * d.G));
+    if (mask != 0) AZ_TRY(sym_reserve(e, d.K * d.G));  // d.K: the walkers in force (leaf_batch, or gumbel_batch while the Gumbel mode is on)
     e->symr_mask = mask; e->symr_n = n;
     drop_graphs(e);
     return AZ_OK;
@@ -2436,6 +2680,32 @@ extern "C" int az_engine_set_evaluator(az_engine *e, az_eval_fn fn, void *user) 
 }
 
 // ---- several leaves per slot and lock-step, kept apart by virtual loss (k_step_multi) --------------------------------
+// K walkers per slot and lock-step come into force (az_engine_set_leaf_batch; az_engine_set_gumbel_batch while the Gumbel mode is on):
+// the walkers' pending words at the first K > 1, K * G network rows, the twins of the random symmetry mode.  The caller has entered.
+static int set_walkers(az_engine *e, int k) {
+    EngDev &d = e->d;
+    if (k == d.K) return AZ_OK;
+    const long long rows = (long long)k * d.G;
+    if (k > 1 && !d.m_leaf) {  // the walkers' pending leaves, at the first k > 1
+        const size_t W = (size_t)d.G * MLB;
+        AZ_TRY(dev_alloc(e, &d.m_leaf, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_p1, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_m1, W));
+        AZ_TRY(dev_alloc(e, &d.m_leaf_player, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_status, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_winner, W));
+        AZ_TRY(dev_alloc(e, &d.m_row, W)); AZ_TRY(dev_alloc(e, &d.m_path, W * LPG)); AZ_TRY(dev_alloc(e, &d.m_path_len, W));
+    }
+    if (rows > e->net_rows) {  // K * G rows for the network (the smaller buffers stay allocated until the engine goes: e->allocs)
+        AZ_TRY(dev_alloc(e, &d.nn_in, (size_t)rows * d.gd.cells));
+        AZ_TRY(dev_alloc(e, &d.probs, (size_t)rows * d.A));
+        AZ_TRY(dev_alloc(e, &d.value, (size_t)rows));
+        e->net_rows = (int)rows;
+    }
+    if (e->symr_mask != 0) AZ_TRY(sym_reserve(e, (int)rows));  // the twins of the random symmetry mode follow K * G
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    d.K = k;
+    // the launch sequence of a search changes: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
 extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
     AZ_REQUIRE(e, AZ_EINVAL, "null engine");
     AZ_NO_OPEN_SEARCH(e, "az_engine_set_leaf_batch");
@@ -2452,23 +2722,8 @@ extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
                    rows, az_net_max_batch(e->net));
     if (k == e->leaf_batch) return AZ_OK;
     AZ_TRY(enter(e));
-    if (k > 1 && !d.m_leaf) {  // the walkers' pending leaves, at the first k > 1
-        const size_t W = (size_t)d.G * MLB;
-        AZ_TRY(dev_alloc(e, &d.m_leaf, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_p1, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_m1, W));
-        AZ_TRY(dev_alloc(e, &d.m_leaf_player, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_status, W)); AZ_TRY(dev_alloc(e, &d.m_leaf_winner, W));
-        AZ_TRY(dev_alloc(e, &d.m_row, W)); AZ_TRY(dev_alloc(e, &d.m_path, W * LPG)); AZ_TRY(dev_alloc(e, &d.m_path_len, W));
-    }
-    if (rows > e->net_rows) {  // K * G rows for the network (the smaller buffers stay allocated until the engine goes: e->allocs)
-        AZ_TRY(dev_alloc(e, &d.nn_in, (size_t)rows * d.gd.cells));
-        AZ_TRY(dev_alloc(e, &d.probs, (size_t)rows * d.A));
-        AZ_TRY(dev_alloc(e, &d.value, (size_t)rows));
-        e->net_rows = (int)rows;
-    }
-    if (e->symr_mask != 0) AZ_TRY(sym_reserve(e, (int)rows));  // the twins of the random symmetry mode follow K * G
-    AZ_HIP(hipStreamSynchronize(e->stream));
-    e->leaf_batch = k; d.K = k;
-    // the launch sequence of a search changes: nothing captured before may be replayed
-    drop_graphs(e);
+    AZ_TRY(set_walkers(e, k));
+    e->leaf_batch = k;
     return AZ_OK;
 }
 
@@ -2498,14 +2753,43 @@ extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, dou
         AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_gumbel: an AZ_EVAL_EXTERNAL engine searches with the PUCT root only");
         AZ_REQUIRE(e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_gumbel: leaf_batch %d > 1 is in force (az_engine_set_leaf_batch); the Gumbel root search takes one leaf per lock-step", e->leaf_batch);
     }
+    if (m > 0 && e->gumbel_batch > 1 && e->cfg.evaluator == AZ_EVAL_NET)
+        AZ_REQUIRE((long long)e->gumbel_batch * d.G <= az_net_max_batch(e->net), AZ_EINVAL, "az_engine_set_gumbel: gumbel_batch %d of %d slots are %lld rows, the network's max_batch is %d",
+                   e->gumbel_batch, d.G, (long long)e->gumbel_batch * d.G, az_net_max_batch(e->net));
     AZ_TRY(enter(e));
     AZ_HIP(hipMemsetAsync(d.gmask, 0, sizeof(u64) * (size_t)d.G, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
+    AZ_TRY(set_walkers(e, m > 0 ? e->gumbel_batch : e->leaf_batch));  // gumbel_batch is in force only while the mode is on
     d.gm = m;
     d.g_cvisit = m > 0 ? c_visit : 0.0; d.g_cscale = m > 0 ? c_scale : 0.0; d.g_scale = m > 0 ? gumbel_scale : 0.0;
     // the launch sequence of a search changes: nothing captured before may be replayed
     drop_graphs(e);
     return AZ_OK;
+}
+
+// several Sequential Halving leaves per slot and lock-step (k_step_gumbel_multi): accepted with the mode on or off, in force while it is on
+extern "C" int az_engine_set_gumbel_batch(az_engine *e, int32_t k) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_gumbel_batch");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_gumbel_batch");
+    EngDev &d = e->d;
+    AZ_REQUIRE(k >= 1 && k <= AZ_MAX_LEAF_BATCH, AZ_EINVAL, "gumbel_batch must be in [1, %d], got %d", AZ_MAX_LEAF_BATCH, k);
+    AZ_REQUIRE(k == 1 || e->sym_mask == 0, AZ_EINVAL, "az_engine_set_gumbel_batch: the engine evaluates over a symmetry mask (az_engine_set_symmetry, 0x%x); the ensemble does not combine with gumbel_batch", (unsigned)e->sym_mask);
+    if (d.gm > 0 && e->cfg.evaluator == AZ_EVAL_NET)
+        AZ_REQUIRE((long long)k * d.G <= az_net_max_batch(e->net), AZ_EINVAL, "gumbel_batch %d of %d slots are %lld rows, the network's max_batch is %d", k, d.G,
+                   (long long)k * d.G, az_net_max_batch(e->net));
+    if (k == e->gumbel_batch) return AZ_OK;
+    if (d.gm > 0) {
+        AZ_TRY(enter(e));
+        AZ_TRY(set_walkers(e, k));
+    }
+    e->gumbel_batch = k;
+    return AZ_OK;
+}
+
+extern "C" int az_gumbel_locksteps(int32_t n_sim, int32_t m, int32_t k) {
+    if (n_sim < 0 || m < 1 || m > AZ_MAX_GUMBEL || k < 1 || k > AZ_MAX_LEAF_BATCH) return -1;
+    return gumbel_locksteps(n_sim, m, k);
 }
 
 extern "C" int az_engine_gumbel_considered(az_engine *e, int32_t slot, uint64_t *mask) {

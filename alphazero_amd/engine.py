@@ -373,6 +373,13 @@ class SelfPlayEngine:
         m, cv, cs, gs = (0, 0.0, 0.0, 0.0) if g is None else g
         check(lib().az_engine_set_gumbel(self.h, m, cv, cs, gs))
 
+    def set_gumbel_batch(self, k):
+        """k Sequential Halving leaves per slot and lock-step of the Gumbel root search (az_engine_set_gumbel_batch; DESIGN section
+        17; 1: one, the default).  Accepted with the mode on or off, in force while it is on; not with a symmetry ensemble; the
+        network needs max_batch >= k * n_slots."""
+        from .gumbel import check_gumbel_batch
+        check(lib().az_engine_set_gumbel_batch(self.h, check_gumbel_batch(k, gumbel=True)))
+
     def considered(self, slot=0):
         """the root children the slot's Sequential Halving considers now, as ascending child indices ([]: none chosen yet, which
         reads as all children)"""

@@ -93,6 +93,52 @@ def locate(s, n, m0):
     raise ValueError(f"simulation {s} is beyond the {n} of the search")
 
 
+MAX_GUMBEL_BATCH = 16  # AZ_MAX_LEAF_BATCH: walkers per slot and lock-step
+
+
+def check_gumbel_batch(gumbel_batch, gumbel=None, symmetry=None):
+    """int(gumbel_batch) (az_engine_set_gumbel_batch); ValueError -- before any device work -- for a bool or a
+    non-integer, a value outside 1..16, and for a value > 1 without the Gumbel mode or together with the symmetry ensemble "all"."""
+    k = gumbel_batch
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"gumbel_batch must be an integer in 1..{MAX_GUMBEL_BATCH}, got {k!r}")
+    k = int(k)
+    if not 1 <= k <= MAX_GUMBEL_BATCH:
+        raise ValueError(f"gumbel_batch must be in 1..{MAX_GUMBEL_BATCH}, got {k}")
+    if k > 1 and gumbel is None:
+        raise ValueError(f"gumbel_batch={k} needs the Gumbel root search (gumbel=...): it batches the simulations of Sequential Halving")
+    if k > 1 and isinstance(symmetry, str) and symmetry == "all":
+        raise ValueError(f"gumbel_batch={k} does not combine with symmetry='all' (the ensemble evaluates one leaf per slot and lock-step)")
+    return k
+
+
+def lockstep_plan(n, m0, K):
+    """the lock-steps [(s, kt)] of a search call of n simulations over m0 sampled actions with gumbel_batch = K: s is the slot's
+    cursor at the start of the lock-step, kt = min(K, end of the current phase - s, n - s) its walkers.  No lock-step crosses a
+    phase boundary of schedule(n, m0); m0 <= 1 (also a root without children) is the one phase of n."""
+    n, m0, K = int(n), max(1, int(m0)), int(K)
+    if K < 1:
+        raise ValueError(f"K must be >= 1, got {K}")
+    ends, e = [], 0
+    for mp, v in schedule(n, m0):
+        e = min(n, e + mp * v)
+        ends.append(e)
+    out, s, p = [], 0, 0
+    while s < n:
+        while ends[p] <= s:
+            p += 1
+        kt = min(K, ends[p] - s)
+        out.append((s, kt))
+        s += kt
+    return out
+
+
+def locksteps(n, m, K):
+    """Lmax(n, m, K): the lock-steps the host enqueues per search call (plus the final backup-only launch) -- the longest plan of
+    any m0 in 1..m, a pure function, so the launch sequence is the same for every slot count and captures as a graph"""
+    return max((len(lockstep_plan(n, m0, K)) for m0 in range(1, int(m) + 1)), default=0)
+
+
 _INF = float("inf")
 
 

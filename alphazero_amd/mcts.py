@@ -55,7 +55,7 @@ def check_symmetry(symmetry, nn):
 
 MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
 
-from .gumbel import check_gumbel  # noqa: E402  (the Gumbel root search's spec and refusals)
+from .gumbel import check_gumbel, check_gumbel_batch  # noqa: E402  (the Gumbel root search's spec and refusals)
 
 
 def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
@@ -87,7 +87,7 @@ def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
 
 class MCT:
     def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None,
-                 leaf_batch=None, gumbel=None):
+                 leaf_batch=None, gumbel=None, gumbel_batch=1):
         self.n_rollouts = 0
         self.simulation_time = 0
         self.eval_method = TreeEval.to_dict()["rollout" if eval_method is None else eval_method]
@@ -118,6 +118,10 @@ class MCT:
         self.gumbel = gumbel
         self._engine_gumbel = None    # the spec the engine is set to
         check_gumbel(gumbel, self._nn, leaf_batch, self.eval_method == TreeEval.NEURAL)
+        # Sequential Halving leaves per lock-step of the Gumbel root search (1: one); needs `gumbel`, not symmetry "all"
+        self.gumbel_batch = gumbel_batch
+        self._engine_gb = 1           # the gumbel_batch the engine is set to
+        check_gumbel_batch(gumbel_batch, gumbel, symmetry)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -146,6 +150,7 @@ class MCT:
         if n_sim is None and compute_time is None:
             raise ValueError("MCT.search needs to have either n_sim or compute_time specified.")
         check_gumbel(self.gumbel, self._nn, self.leaf_batch, self.eval_method == TreeEval.NEURAL, compute_time)
+        check_gumbel_batch(self.gumbel_batch, self.gumbel, self.symmetry)
         self._sync_device_root(board, n_sim)
         if n_sim is not None:
             self._ensure_room(n_sim)
@@ -256,6 +261,7 @@ class MCT:
             self._plies = 0
             self._engine_lb = 1
             self._engine_gumbel = None
+            self._engine_gb = 1
         lb = check_leaf_batch(self.leaf_batch, self._nn if neural else None, self.symmetry, neural)
         if self._engine_lb != lb:
             self._engine.set_leaf_batch(lb)
@@ -264,6 +270,10 @@ class MCT:
         if self._engine_gumbel != gum:
             self._engine.set_gumbel(self.gumbel)
             self._engine_gumbel = gum
+        gb = check_gumbel_batch(self.gumbel_batch, self.gumbel, self.symmetry)
+        if self._engine_gb != gb:
+            self._engine.set_gumbel_batch(gb)
+            self._engine_gb = gb
         key = (board.grid.astype(np.int8).tobytes(), int(board.player))
         if key != self._root_key:  # tree restarted from an unexplored state (mcts.py:124-125, 231-233)
             self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8),

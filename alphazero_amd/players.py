@@ -7,7 +7,7 @@ from time import sleep
 import numpy as np
 
 from .base import Player
-from .gumbel import check_gumbel
+from .gumbel import check_gumbel, check_gumbel_batch
 from .mcts import MCT, _action_of, _move_of, check_leaf_batch, check_symmetry
 from .utils import fair_max
 
@@ -82,16 +82,22 @@ class MCTSPlayer(Player):
 
 class AlphaZeroPlayer(MCTSPlayer):
     def __init__(self, n_sim=None, compute_time=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, verbose=False,
-                 symmetry=None, leaf_batch=None, gumbel=None):
+                 symmetry=None, leaf_batch=None, gumbel=None, gumbel_batch=1):
         super().__init__(n_sim=n_sim, compute_time=compute_time, verbose=verbose)
         check_gumbel(gumbel, nn, leaf_batch, True, compute_time)
+        check_gumbel_batch(gumbel_batch, gumbel, symmetry)
         self.mct = MCT(eval_method="neural", nn=nn, dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
-                       symmetry=symmetry, leaf_batch=leaf_batch, gumbel=gumbel)
+                       symmetry=symmetry, leaf_batch=leaf_batch, gumbel=gumbel, gumbel_batch=gumbel_batch)
 
     @property
     def gumbel(self):
         """the Gumbel root search's spec (alphazero_amd.gumbel; None: the PUCT root)"""
         return self.mct.gumbel
+
+    @property
+    def gumbel_batch(self):
+        """Sequential Halving leaves per lock-step of the Gumbel root search (1: one)"""
+        return self.mct.gumbel_batch
 
     @property
     def symmetry(self):
@@ -108,15 +114,16 @@ class AlphaZeroPlayer(MCTSPlayer):
                                nn=self.mct.nn.clone() if self.mct.nn is not None else None,
                                dirichlet_alpha=self.mct.dirichlet_alpha, dirichlet_epsilon=self.mct.dirichlet_epsilon,
                                verbose=self.verbose, symmetry=self.mct.symmetry, leaf_batch=self.mct.leaf_batch,
-                               gumbel=self.mct.gumbel)
+                               gumbel=self.mct.gumbel, gumbel_batch=self.mct.gumbel_batch)
 
     def reset(self):
         old = self.mct
         self.mct = MCT(eval_method="neural", nn=old.nn, dirichlet_alpha=old.dirichlet_alpha,
-                       dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry, leaf_batch=old.leaf_batch, gumbel=old.gumbel)
+                       dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry, leaf_batch=old.leaf_batch, gumbel=old.gumbel,
+                       gumbel_batch=old.gumbel_batch)
         # keep the uploaded weights and the device tree storage: a reset only drops the tree
         self.mct._hipnet, self.mct._engine, self.mct._engine_board = old._hipnet, old._engine, old._engine_board
-        self.mct._engine_lb, self.mct._engine_gumbel = old._engine_lb, old._engine_gumbel
+        self.mct._engine_lb, self.mct._engine_gumbel, self.mct._engine_gb = old._engine_lb, old._engine_gumbel, old._engine_gb
         self.mct._evaluator = old._evaluator  # the carried engine calls it (external evaluation, evaluators.route)
         if self.mct._engine is not None:
             self.mct._plies = 0
@@ -143,7 +150,7 @@ class BatchedMCTSPlayer(Player):
             raise ValueError("n_slots must be a positive integer")
         self.n_sim, self.n_slots = int(n_sim), int(n_slots)
         self.nn, self.dirichlet_alpha, self.dirichlet_epsilon, self.symmetry, self.leaf_batch = None, None, None, None, None
-        self.gumbel = None
+        self.gumbel, self.gumbel_batch = None, 1
         self._seed = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         self._engine = None           # n_slots device trees
         self._engine_board = None     # (game, H, W) the engine was built for
@@ -206,10 +213,12 @@ class BatchedMCTSPlayer(Player):
         external = neural and route(self.nn) != "hip"  # evaluates the leaves itself, as in BatchedArena._engine
         sym = members(first.game, H, W, check_symmetry(self.symmetry, self.nn if neural else None))
         lb = check_leaf_batch(self.leaf_batch, self.nn if neural else None, self.symmetry, neural)
+        gb = check_gumbel_batch(self.gumbel_batch, self.gumbel if neural else None, self.symmetry)
         if neural and not external:
-            # every slot's leaf in each of its twins, or every slot's leaf_batch walkers (a random spec evaluates one twin per leaf)
+            # every slot's leaf in each of its twins, or every slot's leaf_batch / gumbel_batch walkers (a random spec evaluates one
+            # twin per leaf)
             rnd = parse(self.symmetry)[1]
-            self._hipnet = self.nn.to_hip(max_batch=max(1, 1 if rnd else len(sym), lb) * self.n_slots)
+            self._hipnet = self.nn.to_hip(max_batch=max(1, 1 if rnd else len(sym), lb, gb) * self.n_slots)
         noisy = self.dirichlet_alpha is not None and self.dirichlet_epsilon is not None
         self._engine = SelfPlayEngine(GAME_IDS[first.game], H, W, n_slots=self.n_slots, n_sim=self.n_sim,
                                       net=self._hipnet if neural and not external else None,
@@ -228,6 +237,8 @@ class BatchedMCTSPlayer(Player):
         if neural and self.gumbel is not None:
             check_gumbel(self.gumbel, self.nn, self.leaf_batch)
             self._engine.set_gumbel(self.gumbel)
+            if gb > 1:
+                self._engine.set_gumbel_batch(gb)
         self._engine_board = (first.game, H, W)
 
     def _sync(self, boards, first):
@@ -323,7 +334,7 @@ class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
     _eval_method = "neural"
 
     def __init__(self, n_sim=None, nn=None, n_slots=1, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, verbose=False,
-                 symmetry=None, leaf_batch=None, gumbel=None):
+                 symmetry=None, leaf_batch=None, gumbel=None, gumbel_batch=1):
         super().__init__(n_sim=n_sim, n_slots=n_slots, seed=seed, verbose=verbose)
         self.nn, self.dirichlet_alpha, self.dirichlet_epsilon = nn, dirichlet_alpha, dirichlet_epsilon
         # leaf evaluations averaged over the board's symmetries (alphazero_amd.symmetry; None: off); HIP-routed networks only
@@ -336,6 +347,9 @@ class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
         # temperature other than 0, its improved policy; HIP-routed networks at leaf_batch 1 only
         self.gumbel = gumbel
         check_gumbel(gumbel, nn, leaf_batch)
+        # Sequential Halving leaves per lock-step and game of the Gumbel root search (1: one); needs `gumbel`, not symmetry "all"
+        self.gumbel_batch = gumbel_batch
+        check_gumbel_batch(gumbel_batch, gumbel, symmetry)
 
 
 PLAYERS_SET = {"human", "random", "greedy", "mcts", "alphazero"}

@@ -62,7 +62,7 @@ class AlphaZeroTrainer:
     DEFAULT_EXP_NAME = "alphazero-undefined"
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
-                 selfplay_gumbel=None):
+                 selfplay_gumbel=None, selfplay_gumbel_batch=1):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -91,6 +91,11 @@ class AlphaZeroTrainer:
         self.selfplay_gumbel = selfplay_gumbel
         from .gumbel import parse as parse_gumbel
         parse_gumbel(selfplay_gumbel)
+        # Sequential Halving leaves per lock-step and game of that wave (1: one): the network runs on up to
+        # selfplay_gumbel_batch * engine_slots rows per call
+        self.selfplay_gumbel_batch = selfplay_gumbel_batch
+        from .gumbel import check_gumbel_batch
+        check_gumbel_batch(selfplay_gumbel_batch, selfplay_gumbel)
 
     def _check_selfplay_symmetry(self):
         from .symmetry import parse
@@ -168,6 +173,8 @@ class AlphaZeroTrainer:
             raise ValueError("the batched engine needs config.simulations (compute_time-bounded search is host-only)")
         slots = max(1, min(self.engine_slots, c.episodes))
         sym = self._check_selfplay_symmetry()
+        from .gumbel import check_gumbel, check_gumbel_batch
+        gb = check_gumbel_batch(self.selfplay_gumbel_batch, self.selfplay_gumbel)
         if sym is not None:
             from .mcts import check_symmetry
             from .symmetry import members, parse
@@ -180,8 +187,11 @@ class AlphaZeroTrainer:
             self._engine = None
         if external:
             check_normalizer(self.nn)
-        elif self._hipnet is None:
-            self._hipnet = self.nn.to_hip(max_batch=slots)
+        elif self._hipnet is None or self._hipnet.max_batch < slots * gb:
+            if self._engine is not None:  # the engine holds the smaller network
+                self._engine.close()
+                self._engine = None
+            self._hipnet = self.nn.to_hip(max_batch=slots * gb)  # every slot's gumbel_batch walkers
         else:
             self._hipnet.load_state_dict(self.nn.state_dict())
         if self._engine is None:
@@ -198,11 +208,13 @@ class AlphaZeroTrainer:
             self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
         elif sym is not None or self._engine._sym_mode is not None:
             self._engine.set_symmetry(sym)
-        from .gumbel import check_gumbel
         gum = check_gumbel(self.selfplay_gumbel, self.nn)  # ValueError for a network routed to the external evaluator
         if gum != getattr(self._engine, "_gumbel_spec", None):
             self._engine.set_gumbel(self.selfplay_gumbel)
             self._engine._gumbel_spec = gum
+        if gb != getattr(self._engine, "_gumbel_batch", 1):
+            self._engine.set_gumbel_batch(gb)
+            self._engine._gumbel_batch = gb
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

@@ -327,6 +327,34 @@ int az_engine_collisions(az_engine *e, int64_t *n);
 int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, double c_scale, double gumbel_scale);
 int az_engine_gumbel_considered(az_engine *e, int32_t slot, uint64_t *mask);
 
+/* Several Sequential Halving leaves per network call: gumbel_batch = K walkers per slot and lock-step for the Gumbel mode only
+ * (az_engine_set_leaf_batch and az_engine_set_gumbel keep refusing each other).  Opt-in, default 1; accepted with the mode on or off
+ * and in force only while m > 0: with the mode off, or at K = 1, every launch and every bit are unchanged.  Everything not named
+ * here is the contract of az_engine_set_gumbel.  Sequential Halving fixes the root child of every simulation of a phase before the
+ * phase starts, so the walks of a round run in disjoint subtrees.  The schedule depends on m0 = min(m, nch), which differs from
+ * slot to slot, so each searching slot keeps a cursor s = the simulations of this search call already dealt:
+ *   the search's first launch sets s = 0; a lock-step of the slot runs kt = min(K, end of the current phase - s, n - s) walkers
+ *   j = 0 .. kt - 1; walker j is simulation s + j (plus the simulations already run on this root in every Philox counter, the
+ *   symmetry draw of az_engine_set_symmetry_random included); then s += kt.  No lock-step crosses a phase boundary: a re-ranking
+ *   can only fall on walker 0 and sees real statistics only, every earlier walker being backed up.  A root without children, and
+ *   m0 = 1, take the one phase of n: all simulations to child 0, ceil(n / K) lock-steps.
+ *   The host enqueues Lmax(n, m, K) = max over m0 in 1 .. m of the length of that plan (az_gumbel_locksteps; -1 for arguments out
+ *   of range) lock-steps and the final backup-only launch -- a pure function, so the sequence captures as a graph; a slot whose
+ *   plan is shorter idles in the rest (no walker, no row).  lockstep_iters grows by Lmax + 1 per search.
+ *   The walkers of a lock-step run in ascending j, strictly one after the other.  Walker j takes the root step of the Gumbel mode
+ *   -- the expansion on the first visit, child = candidate (i mod m_p), stop when the root was fresh or the child's real N is 0 --
+ *   with no virtual count (the pick is forced), then descends from depth 1 with az_engine_set_leaf_batch's virtual-count scores over
+ *   the earlier walkers' recorded paths (the root's child is node 1 of a path).  Leaf status, collisions (az_engine_collisions:
+ *   with K > m_p several walkers share a root child and, while its N is 0, its pending leaf), backup order and node allocation
+ *   order are az_engine_set_leaf_batch's.
+ * Every root grows by exactly n visits per search call; the result is a function of (seed, game id, m, constants, K, n), never of
+ * the slot, the slot count or the block.  AZ_EINVAL: k outside [1, AZ_MAX_LEAF_BATCH]; k > 1 while an ensemble mask is in force
+ * (and az_engine_set_symmetry refuses a mask while k > 1); k * n_slots beyond the network's max_batch while the mode is on (with it
+ * off az_engine_set_gumbel refuses then); AZ_ESTATE while a search is open.  A change of the walkers in force drops the cached
+ * search graphs. */
+int az_engine_set_gumbel_batch(az_engine *e, int32_t k);
+int az_gumbel_locksteps(int32_t n_sim, int32_t m, int32_t k);
+
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
  * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves

@@ -6,7 +6,11 @@ gumbel = 16 at n_sim 16, 32 and 100:
 At equal n_sim the two searches launch the same sequence (k_step_gumbel for k_step); the mode exists for c. at n_sim 16 and 32
 against plain at 100: fewer simulations per move, not a faster kernel.  Wall-clock medians of repeats after a warm-up; every timed
 call blocks until its results are there.  --trace runs the one-game leg at n_sim 100 alone (for rocprofv3 --kernel-trace --stats).
-usage: python tools/gumbel_bench.py [--out profiles/r13_gumbel.txt] [--repeats 9] [--wave-repeats 2] [--trace]"""
+--batch 1,4,16 adds a column per gumbel_batch K (K Sequential Halving leaves per network call; 1 is the leg
+above): every K > 1 leg is set against K = 1, with the share of simulations that collided on a pending leaf, and for the wave the
+network rows per enqueued lock-step against the K * slots the call could carry (what the idle tail of Lmax costs).
+usage: python tools/gumbel_bench.py [--out profiles/r13_gumbel.txt] [--repeats 9] [--wave-repeats 2] [--trace] [--sims 16,32,100]
+       [--batch 1,4,16]"""
 import argparse
 import os
 import statistics
@@ -18,6 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from alphazero_amd import engine as E  # noqa: E402
+from alphazero_amd import gumbel as G  # noqa: E402
 from alphazero_amd.games.othello import OthelloBoard, OthelloNet  # noqa: E402
 from alphazero_amd.mcts import MCT  # noqa: E402
 from alphazero_amd.players import BatchedAlphaZeroPlayer  # noqa: E402
@@ -36,7 +41,15 @@ def spread(xs, scale, unit):
 
 
 def opt(gumbel):
-    return {"gumbel": M} if gumbel else {}
+    """gumbel: False (the plain search) or the gumbel_batch K of the Gumbel leg"""
+    return {"gumbel": M, "gumbel_batch": int(gumbel)} if gumbel else {}
+
+
+def name(gumbel):
+    return "plain     " if not gumbel else f"gumbel K{int(gumbel):2d}"
+
+
+COLL = {}  # (leg, gumbel, n_sim) -> collisions / simulations of the timed calls
 
 
 def one_game(net, gumbel, n_sim, repeats):
@@ -50,6 +63,7 @@ def one_game(net, gumbel, n_sim, repeats):
         if i >= 3:
             ts.append(time.perf_counter() - t)
     assert mct._engine.stats()["graph_replays"] > 0
+    COLL["a", gumbel, n_sim] = mct._engine.collisions() / float((repeats + 3) * n_sim)
     mct._engine.close()
     return ts
 
@@ -69,6 +83,7 @@ def batched_player(net, gumbel, n_sim, repeats, games=64):
         player.get_moves(boards, temps=0)
         if i >= 3:
             ts.append(time.perf_counter() - t)
+    COLL["b", gumbel, n_sim] = player._engine.collisions() / float((repeats + 3) * n_sim * games)
     player.close()
     return ts
 
@@ -78,6 +93,7 @@ def wave(hip, gumbel, n_sim, repeats, games=4096):
     eng = E.SelfPlayEngine(0, 8, 8, n_slots=games, n_sim=n_sim, net=hip, seed=3)
     if gumbel:
         eng.set_gumbel(M)
+        eng.set_gumbel_batch(int(gumbel))
     out = []
     for i in range(repeats + 1):
         torch.cuda.synchronize()
@@ -89,6 +105,16 @@ def wave(hip, gumbel, n_sim, repeats, games=4096):
         assert st["games_done"] == games and st["error_flags"] == 0
         if i >= 1:
             out.append((games / dt, st["samples"] / dt))
+    # the last wave: simulations that collided, and the network rows per enqueued lock-step (root-prior passes included in the rows)
+    COLL["c", gumbel, n_sim] = eng.collisions() / float((repeats + 1) * max(1, st["samples"]) * n_sim)
+    COLL["rows", gumbel, n_sim] = st["net_evals"] / float(max(1, st["lockstep_iters"]))
+    if gumbel and int(gumbel) > 1:
+        # the searched roots' child counts (pi' has full support over the legal moves) and with them the lock-steps a slot's own plan
+        # fills of the Lmax the host enqueues: what the idle tail costs
+        nch = (eng.samples()["pi"] > 0).sum(1).cpu().numpy()
+        plan = {c: len(G.lockstep_plan(n_sim, min(M, int(c)), int(gumbel))) for c in np.unique(nch)}
+        COLL["plan", gumbel, n_sim] = (float(np.mean([plan[c] for c in nch])), G.locksteps(n_sim, M, int(gumbel)),
+                                      [int(((nch >= lo) & (nch <= hi)).sum()) for lo, hi in ((1, 1), (2, 3), (4, 7), (8, 15), (16, 64))])
     eng.close()
     return out
 
@@ -100,7 +126,11 @@ def main():
     ap.add_argument("--wave-repeats", type=int, default=2)
     ap.add_argument("--trace", action="store_true", help="one-game leg at 100 simulations only (for rocprofv3 --kernel-trace --stats)")
     ap.add_argument("--no-wave", action="store_true")
+    ap.add_argument("--sims", default="16,32,100")
+    ap.add_argument("--batch", default="1", help="gumbel_batch values of the Gumbel legs, e.g. 1,4,16")
     a = ap.parse_args()
+    Ks = [int(k) for k in a.batch.split(",")]
+    assert Ks and Ks[0] == 1 and all(1 <= k <= 16 for k in Ks), "--batch starts with 1 (the yardstick of the K > 1 legs)"
     assert torch.cuda.is_available(), "needs the GPU"
     torch.manual_seed(0)
     net = OthelloNet(8, device="cuda")
@@ -108,38 +138,53 @@ def main():
     say(f"python tools/gumbel_bench.py{' --trace' if a.trace else ''}: Othello 8x8, random-init OthelloNet, gumbel m = {M}, "
         f"{torch.cuda.get_device_name(0)}")
     med = statistics.median
-    sims = [100] if a.trace else [16, 32, 100]
+    sims = [100] if a.trace else [int(x) for x in a.sims.split(",")]
+    legs = [False] + Ks
     for n_sim in sims:
         res = {}
-        for gumbel in (False, True, False, True):  # alternated: the second pair shows the spread of a repeat
+        for gumbel in legs + legs:  # alternated: the second round shows the spread of a repeat
             ts = one_game(net, gumbel, n_sim, a.repeats)
             res.setdefault(gumbel, []).append(med(ts))
-            say(f"a. 1 game, MCT.search, n_sim {n_sim:3d}, {'gumbel' if gumbel else 'plain '} : {spread([t / n_sim for t in ts], 1e6, 'us per simulation')}  "
+            say(f"a. 1 game, MCT.search, n_sim {n_sim:3d}, {name(gumbel)} : {spread([t / n_sim for t in ts], 1e6, 'us per simulation')}  "
                 f"{med(ts) * 1e3:7.3f} ms per move")
-        say(f"   n_sim {n_sim:3d}: gumbel / plain = {med(res[True]) / med(res[False]):.3f} (plain runs {res[False][0] * 1e3:.3f} and {res[False][1] * 1e3:.3f} ms)")
+        say(f"   n_sim {n_sim:3d}: gumbel / plain = {med(res[1]) / med(res[False]):.3f} (plain runs {res[False][0] * 1e3:.3f} and {res[False][1] * 1e3:.3f} ms)")
+        for k in Ks[1:]:
+            say(f"   n_sim {n_sim:3d}: K {k:2d} / K 1 = {med(res[k]) / med(res[1]):.3f} (K 1 runs {res[1][0] * 1e3:.3f} and {res[1][1] * 1e3:.3f} ms), "
+                f"{G.locksteps(n_sim, M, k)} lock-steps for {n_sim}, collisions {COLL['a', k, n_sim]:.3f} of the simulations")
     if a.trace:
         return
     for n_sim in sims:
         res = {}
-        for gumbel in (False, True):
+        for gumbel in legs:
             ts = batched_player(net, gumbel, n_sim, a.repeats)
             res[gumbel] = med(ts)
-            say(f"b. 64-game BatchedAlphaZeroPlayer.get_moves, n_sim {n_sim:3d}, {'gumbel' if gumbel else 'plain '} : {spread(ts, 1e3, 'ms per call')}")
-        say(f"   n_sim {n_sim:3d}: gumbel / plain = {res[True] / res[False]:.3f}")
+            say(f"b. 64-game BatchedAlphaZeroPlayer.get_moves, n_sim {n_sim:3d}, {name(gumbel)} : {spread(ts, 1e3, 'ms per call')}")
+        say(f"   n_sim {n_sim:3d}: gumbel / plain = {res[1] / res[False]:.3f}")
+        for k in Ks[1:]:
+            say(f"   n_sim {n_sim:3d}: K {k:2d} / K 1 = {res[k] / res[1]:.3f}, collisions {COLL['b', k, n_sim]:.3f} of the simulations")
     if not a.no_wave:
-        hip = net.to_hip(max_batch=4096)
+        hip = net.to_hip(max_batch=4096 * max(Ks))
         got = {}
         for n_sim in sims:
-            for gumbel in (False, True):
+            for gumbel in legs:
                 r = wave(hip, gumbel, n_sim, a.wave_repeats)
                 got[gumbel, n_sim] = (med([x[0] for x in r]), med([x[1] for x in r]))
-                say(f"c. 4096-slot wave, n_sim {n_sim:3d}, {'gumbel' if gumbel else 'plain '} : " +
-                    ", ".join(f"{g:8.1f} games/s {x:10.1f} examples/s" for g, x in r))
+                say(f"c. 4096-slot wave, n_sim {n_sim:3d}, {name(gumbel)} : " +
+                    ", ".join(f"{g:8.1f} games/s {x:10.1f} examples/s" for g, x in r) +
+                    f"; {COLL['rows', gumbel, n_sim]:9.1f} network rows per enqueued lock-step of {4096 * max(1, int(gumbel))}")
+                if ("plan", gumbel, n_sim) in COLL:
+                    mean, lmax, hist = COLL["plan", gumbel, n_sim]
+                    say(f"   roots by child count 1 / 2-3 / 4-7 / 8-15 / 16+: {hist}; their own plans fill {mean:.2f} of the {lmax} lock-steps enqueued")
         for n_sim in sims:
-            say(f"   n_sim {n_sim:3d}: gumbel / plain games/s = {got[True, n_sim][0] / got[False, n_sim][0]:.3f}")
-        for n_sim in (16, 32):
-            say(f"   gumbel at n_sim {n_sim} against plain at 100: {got[True, n_sim][0] / got[False, 100][0]:.2f}x the games/s, "
-                f"{got[True, n_sim][1] / got[False, 100][1]:.2f}x the examples/s (fewer simulations per move, not a faster kernel)")
+            say(f"   n_sim {n_sim:3d}: gumbel / plain games/s = {got[1, n_sim][0] / got[False, n_sim][0]:.3f}")
+            for k in Ks[1:]:
+                say(f"   n_sim {n_sim:3d}: K {k:2d} / K 1 games/s = {got[k, n_sim][0] / got[1, n_sim][0]:.3f}, Lmax {G.locksteps(n_sim, M, k)} against "
+                    f"{n_sim} lock-steps, collisions {COLL['c', k, n_sim]:.3f} of the simulations")
+        if 100 in sims:
+            for n_sim in (x for x in sims if x < 100):
+                for k in Ks:
+                    say(f"   gumbel K {k:2d} at n_sim {n_sim} against plain at 100: {got[k, n_sim][0] / got[False, 100][0]:.2f}x the games/s, "
+                        f"{got[k, n_sim][1] / got[False, 100][1]:.2f}x the examples/s (fewer simulations per move, not a faster kernel)")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
