@@ -13,6 +13,8 @@ NOISE_OFF, NOISE_PHILOX, NOISE_HASH = 0, 1, 2
 EVAL_NET, EVAL_FAKE, EVAL_ROLLOUT, EVAL_EXTERNAL = 0, 1, 2, 3
 SYM_ALL = -1  # AZ_SYM_ALL: every transform code the board has
 MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH
+# AZ_TBUF_*: the class of a trainer's device buffer (az_trainer_buffer), by its number
+TRAINER_BUFFER_CLASSES = ("parameter", "momentum", "running_stat", "hyper", "workspace")
 
 
 class AzError(RuntimeError):
@@ -65,7 +67,7 @@ SYMBOLS = [
     "az_engine_set_sides", "az_engine_best_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator", "az_engine_set_symmetry", "az_engine_set_symmetry_random", "az_engine_set_leaf_batch", "az_engine_collisions",
     "az_engine_set_gumbel", "az_engine_gumbel_considered", "az_engine_set_gumbel_batch", "az_gumbel_locksteps",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
-    "az_trainer_steps", "az_trainer_check", "az_trainer_debug",
+    "az_trainer_steps", "az_trainer_check", "az_trainer_debug", "az_trainer_buffer",
 ]
 
 
@@ -144,6 +146,7 @@ def lib():
     L.az_trainer_steps.argtypes = [vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, vp]
     L.az_trainer_check.argtypes = [vp]
     L.az_trainer_debug.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(i64)]
+    L.az_trainer_buffer.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(i32), C.POINTER(vp), C.POINTER(i64)]
     _LIB = L
     return L
 

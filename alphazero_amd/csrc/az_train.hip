@@ -2018,16 +2018,16 @@ __global__ void k_relayout(float *dst, const float *src, long long n, int kind, 
 }
 
 struct TensorRef { float *ptr; long long numel; int kind, a; };
+struct TBuf { std::string name; int cls; void *ptr; size_t bytes; };  // cls: AZ_TBUF_* (az_amd.h)
 
 struct az_trainer {
     int game = 0, H = 0, W = 0, max_batch = 0;
     TDims d;
     TPtr q;
     TttPtr tq;  // game == AZ_TICTACTOE: the whole step is one launch (k_ttt_step)
-    std::vector<void *> allocs;
+    std::vector<TBuf> bufs;  // every device allocation of the trainer, in allocation order (az_trainer_buffer, az_trainer_debug)
     std::vector<std::pair<float *, size_t>> momenta;  // zeroed by az_trainer_begin
     std::map<std::string, TensorRef> tensors;
-    std::map<std::string, std::pair<void *, long long>> debug;  // name -> (device pointer, element count) of the workspace buffers
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     hipGraphExec_t graph = nullptr, graph_k = nullptr;  // one step / graph_steps consecutive steps
@@ -2041,20 +2041,22 @@ struct az_trainer {
 
 #define AZ_TRY(x) do { int _rc = (x); if (_rc != AZ_OK) return _rc; } while (0)
 
+// The only way to device memory: every allocation is recorded under a name and a class, zeroed once, and freed by az_trainer_destroy
 template <typename T>
-static int talloc(az_trainer *t, T **p, size_t n) {
+static int talloc(az_trainer *t, T **p, size_t n, const std::string &name, int cls) {
     void *v = nullptr;
-    AZ_HIP(hipMalloc(&v, (n ? n : 1) * sizeof(T)));
-    AZ_HIP(hipMemset(v, 0, (n ? n : 1) * sizeof(T)));
-    t->allocs.push_back(v);
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    AZ_HIP(hipMalloc(&v, bytes));
+    t->bufs.push_back(TBuf{name, cls, v, bytes});
+    AZ_HIP(hipMemset(v, 0, bytes));
     *p = (T *)v;
     return AZ_OK;
 }
 
-static int palloc(az_trainer *t, float *PSet::*field, size_t n) {  // a parameter and its momentum buffer
-    AZ_TRY(talloc(t, &(t->q.p.*field), n));
-    AZ_TRY(talloc(t, &(t->q.m.*field), n));
-    t->momenta.push_back({t->q.m.*field, n});
+static int palloc(az_trainer *t, float **p, float **m, size_t n, const std::string &name) {  // a parameter and its momentum buffer
+    AZ_TRY(talloc(t, p, n, "p." + name, AZ_TBUF_PARAMETER));
+    AZ_TRY(talloc(t, m, n, "m." + name, AZ_TBUF_MOMENTUM));
+    t->momenta.push_back({*m, n});
     return AZ_OK;
 }
 
@@ -2068,16 +2070,15 @@ extern "C" int az_trainer_create(int game, int H, int W, int max_batch, az_train
         t->game = game; t->H = H; t->W = W; t->max_batch = max_batch;
         memset(&t->d, 0, sizeof t->d); memset(&t->q, 0, sizeof t->q); memset(&t->tq, 0, sizeof t->tq);
         t->d.B = max_batch;
-        int rc = talloc(t, &t->tq.p, 320);
-        if (rc == AZ_OK) rc = talloc(t, &t->tq.m, 320);
-        if (rc == AZ_OK) rc = talloc(t, &t->tq.rs, 36);
-        if (rc == AZ_OK) rc = talloc(t, &t->tq.hp, 1);
+        // no workspace class: k_ttt_step keeps every activation and gradient in LDS
+        int rc = palloc(t, &t->tq.p, &t->tq.m, 320, "all");
+        if (rc == AZ_OK) rc = talloc(t, &t->tq.rs, 36, "rs", AZ_TBUF_RUNNING_STAT);
+        if (rc == AZ_OK) rc = talloc(t, &t->tq.hp, 1, "hyper", AZ_TBUF_HYPER);
         if (rc == AZ_OK && (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
                             hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming) != hipSuccess ||
                             hipEventCreateWithFlags(&t->ev_out, hipEventDisableTiming) != hipSuccess)) { az_set_error("could not create the trainer's stream"); rc = AZ_EHIP; }
         if (rc != AZ_OK) { az_trainer_destroy(t); return rc; }
         t->q.hp = t->tq.hp;
-        t->momenta.push_back({t->tq.m, 320});
         { const char *g = getenv("AZ_TRAIN_GRAPH"); if (g && atoi(g) == 0) t->graphs_ok = false; }
         { const char *g = getenv("AZ_TRAIN_GRAPH_STEPS"); if (g && atoi(g) >= 1 && atoi(g) <= 64) t->graph_steps = atoi(g); }
         auto reg = [&](const char *name, float *p, long long n) { t->tensors[name] = TensorRef{p, n, 0, 0}; };
@@ -2108,30 +2109,34 @@ extern "C" int az_trainer_create(int game, int H, int W, int max_batch, az_train
     memset(&t->q, 0, sizeof t->q);
     int rc = AZ_OK;
     const size_t B = (size_t)max_batch, NBmax = 256;
-#define TA(p, n) if (rc == AZ_OK) rc = talloc(t, &t->q.p, (n))
-#define PA(f, n) if (rc == AZ_OK) rc = palloc(t, &PSet::f, (n))
+    const auto nm = [](const char *s, int l) { return s + std::to_string(l + 1); };
+#define WS(p, n, name) if (rc == AZ_OK) rc = talloc(t, &t->q.p, (n), name, AZ_TBUF_WORKSPACE)
+#define RS(p, n, name) if (rc == AZ_OK) rc = talloc(t, &t->q.p, (n), name, AZ_TBUF_RUNNING_STAT)
+#define PA(f, n, name) if (rc == AZ_OK) rc = palloc(t, &t->q.p.f, &t->q.m.f, (n), name)
     for (int l = 0; l < 4 && rc == AZ_OK; ++l) {
         const size_t wn = l == 0 ? 9 * 32 : 9 * 32 * 32;
-        rc = talloc(t, &t->q.p.cw[l], wn); if (rc == AZ_OK) rc = talloc(t, &t->q.m.cw[l], wn); t->momenta.push_back({t->q.m.cw[l], wn});
-        float **pp[3] = {&t->q.p.cb[l], &t->q.p.bg[l], &t->q.p.bb[l]}, **mm[3] = {&t->q.m.cb[l], &t->q.m.bg[l], &t->q.m.bb[l]};
-        for (int k = 0; k < 3 && rc == AZ_OK; ++k) { rc = talloc(t, pp[k], 32); if (rc == AZ_OK) rc = talloc(t, mm[k], 32); t->momenta.push_back({*mm[k], 32}); }
-        TA(rm[l], 32); TA(rv[l], 32);
+        PA(cw[l], wn, nm("cw", l)); PA(cb[l], 32, nm("cb", l)); PA(bg[l], 32, nm("bg", l)); PA(bb[l], 32, nm("bb", l));
+        RS(rm[l], 32, nm("rm_c", l)); RS(rv[l], 32, nm("rv_c", l));
         const size_t P = l <= 1 ? d.P1 : (l == 2 ? d.P3 : d.P4);
-        TA(c[l], B * P * 32); TA(dy[l], B * P * 32); TA(fpart[l], NBmax * FPART); TA(fdone[l], 160); TA(bdone[l], 64);
-        TA(gw[l], NBmax * (l == 0 ? (size_t)C1P : wn + 32));
-        if (l < 3) TA(bpart[l], NBmax * 64);
+        WS(c[l], B * P * 32, nm("c", l)); WS(dy[l], B * P * 32, nm("dy", l)); WS(fpart[l], NBmax * FPART, nm("fpart", l));
+        WS(fdone[l], 160, nm("fdone", l)); WS(bdone[l], 64, nm("bdone", l));
+        WS(gw[l], NBmax * (l == 0 ? (size_t)C1P : wn + 32), nm("gw", l));
+        if (l < 3) WS(bpart[l], NBmax * 64, nm("bpart", l));
     }
-    PA(w1, (size_t)d.F1 * d.FIN); PA(b1, d.F1); PA(g1, d.F1); PA(be1, d.F1);
-    PA(w2, (size_t)d.F2 * d.F1); PA(b2, d.F2); PA(g2, d.F2); PA(be2, d.F2);
-    PA(wh, (size_t)d.NHP * d.F2); PA(bh, d.NHP);
-    TA(rm1, d.F1); TA(rv1, d.F1); TA(rm2, d.F2); TA(rv2, d.F2);
-    TA(x0, B * d.P1); TA(y1, B * d.F1); TA(h1, B * d.F1); TA(mu1, d.F1); TA(iv1, d.F1);
-    TA(y2, B * d.F2); TA(h2, B * d.F2); TA(mu2, d.F2); TA(iv2, d.F2);
-    TA(dlog, B * d.NHP); TA(losspart, (B / 16) * 2); TA(dz2, B * d.F2); TA(dz1, B * d.F1);
-    TA(colsum, (size_t)NRBMAX * d.FIN * 2); TA(hp, 1);
-    TA(hwpart, (size_t)NRBMAX * d.NHP * (d.F2 + 1));
-    TA(fstat[0], (size_t)NRBMAX * d.F1 * 3); TA(fstat[1], (size_t)NRBMAX * d.F2 * 3); TA(bstat[0], (size_t)NRBMAX * d.F1 * 3); TA(bstat[1], (size_t)NRBMAX * d.F2 * 3);
-#undef TA
+    PA(w1, (size_t)d.F1 * d.FIN, "w1"); PA(b1, d.F1, "b1"); PA(g1, d.F1, "g1"); PA(be1, d.F1, "be1");
+    PA(w2, (size_t)d.F2 * d.F1, "w2"); PA(b2, d.F2, "b2"); PA(g2, d.F2, "g2"); PA(be2, d.F2, "be2");
+    PA(wh, (size_t)d.NHP * d.F2, "wh"); PA(bh, d.NHP, "bh");
+    RS(rm1, d.F1, "rm_f1"); RS(rv1, d.F1, "rv_f1"); RS(rm2, d.F2, "rm_f2"); RS(rv2, d.F2, "rv_f2");
+    WS(x0, B * d.P1, "x0"); WS(y1, B * d.F1, "y1"); WS(h1, B * d.F1, "h1"); WS(mu1, d.F1, "mu1"); WS(iv1, d.F1, "iv1");
+    WS(y2, B * d.F2, "y2"); WS(h2, B * d.F2, "h2"); WS(mu2, d.F2, "mu2"); WS(iv2, d.F2, "iv2");
+    WS(dlog, B * d.NHP, "dlog"); WS(losspart, (B / 16) * 2, "losspart"); WS(dz2, B * d.F2, "dz2"); WS(dz1, B * d.F1, "dz1");
+    WS(colsum, (size_t)NRBMAX * d.FIN * 2, "colsum");
+    if (rc == AZ_OK) rc = talloc(t, &t->q.hp, 1, "hyper", AZ_TBUF_HYPER);
+    WS(hwpart, (size_t)NRBMAX * d.NHP * (d.F2 + 1), "hwpart");
+    WS(fstat[0], (size_t)NRBMAX * d.F1 * 3, "fstat1"); WS(fstat[1], (size_t)NRBMAX * d.F2 * 3, "fstat2");
+    WS(bstat[0], (size_t)NRBMAX * d.F1 * 3, "bstat1"); WS(bstat[1], (size_t)NRBMAX * d.F2 * 3, "bstat2");
+#undef WS
+#undef RS
 #undef PA
     if (rc == AZ_OK && (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
                         hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming) != hipSuccess ||
@@ -2157,15 +2162,6 @@ extern "C" int az_trainer_create(int game, int H, int W, int max_batch, az_train
     reg("fc_bn2.weight", t->q.p.g2, d.F2); reg("fc_bn2.bias", t->q.p.be2, d.F2); reg("fc_bn2.running_mean", t->q.rm2, d.F2); reg("fc_bn2.running_var", t->q.rv2, d.F2);
     reg("fc_probs.weight", t->q.p.wh, (long long)d.A * d.F2); reg("fc_probs.bias", t->q.p.bh, d.A);
     reg("fc_value.weight", t->q.p.wh + (size_t)d.A * d.F2, d.F2); reg("fc_value.bias", t->q.p.bh + d.A, 1);
-    auto dbg = [&](const char *name, void *p, long long n) { t->debug[name] = {p, n}; };
-    for (int l = 0; l < 4; ++l) {
-        const long long P = l <= 1 ? d.P1 : (l == 2 ? d.P3 : d.P4);
-        dbg(("c" + std::to_string(l + 1)).c_str(), t->q.c[l], (long long)B * P * 32);
-        dbg(("dy" + std::to_string(l + 1)).c_str(), t->q.dy[l], (long long)B * P * 32);
-        dbg(("fpart" + std::to_string(l + 1)).c_str(), t->q.fpart[l], (long long)NBmax * FPART);
-    }
-    dbg("x0", t->q.x0, B * d.P1); dbg("y1", t->q.y1, B * d.F1); dbg("h1", t->q.h1, B * d.F1); dbg("y2", t->q.y2, B * d.F2); dbg("h2", t->q.h2, B * d.F2);
-    dbg("dlog", t->q.dlog, B * d.NHP); dbg("dz2", t->q.dz2, B * d.F2); dbg("dz1", t->q.dz1, B * d.F1); dbg("losspart", t->q.losspart, (B / 16) * 2);
     *out = t;
     return AZ_OK;
 }
@@ -2175,7 +2171,7 @@ extern "C" void az_trainer_destroy(az_trainer *t) {
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     if (t->graph) (void)hipGraphExecDestroy(t->graph);
     if (t->graph_k) (void)hipGraphExecDestroy(t->graph_k);
-    for (void *p : t->allocs) (void)hipFree(p);
+    for (const TBuf &b : t->bufs) (void)hipFree(b.ptr);
     if (t->ev_in) (void)hipEventDestroy(t->ev_in);
     if (t->ev_out) (void)hipEventDestroy(t->ev_out);
     if (t->stream) (void)hipStreamDestroy(t->stream);
@@ -2453,8 +2449,17 @@ extern "C" int az_trainer_debug(az_trainer *t, const char *name, void **d_ptr, i
         return AZ_OK;
     }
 #endif
-    auto it = t->debug.find(name);
-    AZ_REQUIRE(it != t->debug.end(), AZ_EINVAL, "unknown workspace buffer '%s'", name);
-    *d_ptr = it->second.first; *numel = it->second.second;
+    for (const TBuf &b : t->bufs)
+        if (b.cls == AZ_TBUF_WORKSPACE && b.name == name) { *d_ptr = b.ptr; *numel = (int64_t)(b.bytes / sizeof(float)); return AZ_OK; }
+    AZ_REQUIRE(false, AZ_EINVAL, "unknown workspace buffer '%s'", name);
+    return AZ_EINVAL;
+}
+
+// test access to EVERY device allocation of the trainer, in allocation order: a buffer cannot exist without appearing here (talloc)
+extern "C" int az_trainer_buffer(az_trainer *t, int32_t index, const char **name, int32_t *cls, void **d_ptr, int64_t *n_bytes) {
+    AZ_REQUIRE(t && name && cls && d_ptr && n_bytes, AZ_EINVAL, "null argument");
+    AZ_REQUIRE(index >= 0 && (size_t)index < t->bufs.size(), AZ_EINVAL, "buffer index %d outside [0, %d)", (int)index, (int)t->bufs.size());
+    const TBuf &b = t->bufs[(size_t)index];
+    *name = b.name.c_str(); *cls = b.cls; *d_ptr = b.ptr; *n_bytes = (int64_t)b.bytes;
     return AZ_OK;
 }

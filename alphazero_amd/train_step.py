@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import check, lib
+from ._lib import AZ_EINVAL, TRAINER_BUFFER_CLASSES, AzError, check, lib
 
 
 def _stream():
@@ -114,6 +114,28 @@ class HipTrainStep:
         torch.cuda.synchronize()
         t = _wrap(p.value, (n.value,), torch.float32, self).clone()
         return t.view(shape) if shape is not None else t
+
+    def buffers(self):
+        """every device allocation of the trainer, in allocation order: [(name, class name, device pointer, bytes)] with the class one of
+        _lib.TRAINER_BUFFER_CLASSES (tests).  The walk ends at the first index az_trainer_buffer rejects as out of range; any other
+        failure (a closed trainer, a null argument) raises, and so does a trainer without a single buffer"""
+        if not getattr(self, "h", None):
+            raise AzError("the trainer is closed")
+        out = []
+        name, cls, p, n = C.c_char_p(), C.c_int32(), C.c_void_p(), C.c_int64()
+        while True:
+            rc = lib().az_trainer_buffer(self.h, len(out), C.byref(name), C.byref(cls), C.byref(p), C.byref(n))
+            if rc == AZ_EINVAL and out and lib().az_last_error().decode(errors="replace").startswith("buffer index"):
+                return out
+            check(rc)
+            out.append((name.value.decode(), TRAINER_BUFFER_CLASSES[cls.value], p.value, n.value))
+
+    def views(self, cls="workspace"):
+        """yields (name, uint8 CUDA tensor) for every buffer of class `cls`: the trainer's own memory, writable, not a copy (tests)"""
+        from .engine import _wrap
+        for name, c, p, n in self.buffers():
+            if c == cls:
+                yield name, _wrap(p, (n,), torch.uint8, self)
 
     def close(self):
         if getattr(self, "h", None):

@@ -421,6 +421,17 @@ int az_trainer_steps(az_trainer *t, const int8_t *d_state, const float *d_pi, co
 int az_trainer_check(az_trainer *t);
 /* test access: device pointer and element count of a workspace buffer of the last step ("c1".."c4", "y1", "h1", "dz1", ...) */
 int az_trainer_debug(az_trainer *t, const char *name, void **d_ptr, int64_t *numel);
+/* test access: EVERY device allocation of the trainer, by index in allocation order: its name, its class, its device pointer and its
+ * size in bytes (*name stays valid until az_trainer_destroy).  AZ_EINVAL past the last index.  What a class means for a step:
+ * parameters, momenta, running statistics and the Hyper block persist from step to step (az_trainer_load / az_trainer_begin set
+ * them); a workspace buffer carries nothing from one step to the next: a step writes every element of it before reading it.
+ * TicTacToeNet's single-kernel step has no workspace buffers (LDS only). */
+#define AZ_TBUF_PARAMETER 0
+#define AZ_TBUF_MOMENTUM 1
+#define AZ_TBUF_RUNNING_STAT 2
+#define AZ_TBUF_HYPER 3
+#define AZ_TBUF_WORKSPACE 4
+int az_trainer_buffer(az_trainer *t, int32_t index, const char **name, int32_t *cls, void **d_ptr, int64_t *n_bytes);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,29 @@ def test_constructor_errors_match_reference():
         _lib.check(L.az_engine_create(C.byref(cfg), None, None, C.byref(h)))
 
 
+def test_trainer_buffer_listing_is_declared_and_its_classes_match_python():
+    """az_trainer_buffer (every allocation of a trainer by index: name, class, pointer, bytes) is declared, listed and exported; the
+    AZ_TBUF_* numbers of the header are the positions of the names Python uses (_lib.TRAINER_BUFFER_CLASSES), 0 .. n - 1 without a gap;
+    HipTrainStep reaches the listing; a null trainer is a ValueError, not a crash"""
+    hdr = open(os.path.join(ROOT, "include", "az_amd.h")).read()
+    assert re.search(r"\bint\s+az_trainer_buffer\s*\(\s*az_trainer\s*\*", hdr) and "az_trainer_buffer" in _lib.SYMBOLS
+    classes = {name.lower(): int(num) for name, num in re.findall(r"#define\s+AZ_TBUF_([A-Z_]+)\s+(\d+)", hdr)}
+    assert classes == {name: i for i, name in enumerate(_lib.TRAINER_BUFFER_CLASSES)}
+    assert set(_lib.TRAINER_BUFFER_CLASSES) == {"parameter", "momentum", "running_stat", "hyper", "workspace"}
+    src = open(os.path.join(ROOT, "alphazero_amd", "csrc", "az_train.hip")).read()
+    assert set(re.findall(r"AZ_TBUF_[A-Z_]+", src)) == {"AZ_TBUF_" + n.upper() for n in _lib.TRAINER_BUFFER_CLASSES}
+    # one allocation call in the whole file, and it sits in talloc's body: an allocation anywhere else would escape the listing
+    code = re.sub(r"//[^\n]*|/\*.*?\*/", "", src, flags=re.S)
+    body = re.search(r"static int talloc\(.*?\n}\n", code, flags=re.S)
+    assert body and len(re.findall(r"\bhipMalloc\w*\s*\(", code)) == 1 == len(re.findall(r"\bhipMalloc\s*\(", body.group(0)))
+    from alphazero_amd.train_step import HipTrainStep
+    assert callable(HipTrainStep.buffers) and callable(HipTrainStep.views)
+    L = _lib.lib()
+    name, cls, p, n = C.c_char_p(), C.c_int32(), C.c_void_p(), C.c_int64()
+    with pytest.raises(ValueError, match="null argument"):
+        _lib.check(L.az_trainer_buffer(None, 0, C.byref(name), C.byref(cls), C.byref(p), C.byref(n)))
+
+
 def test_product_does_not_import_oracle():
     """the oracle is test infrastructure: nothing under alphazero_amd/ may reference it"""
     for dirpath, _, files in os.walk(os.path.join(ROOT, "alphazero_amd")):

@@ -5,7 +5,9 @@ gradient the step keeps in its workspace, the losses, and the parameters / Batch
 Prints one line per buffer (max abs error, scale); tests/test_gpu_train_step.py asserts on the same report.
     python tools/check_train_step.py --update-profile
 The parameter update at its own scale (gradients from one step at momentum 0 / weight decay 0, the hyper-parameters as identities of
-the step with itself): the helpers of tests/test_gpu_train_update.py, and the figures of profiles/r07_update_parity.txt."""
+the step with itself): the helpers of tests/test_gpu_train_update.py, and the figures of profiles/r07_update_parity.txt.
+The step as a function of nothing but its inputs (StateProblem, state_run, poison_workspace, copy_state, Banded): the helpers of
+tests/test_gpu_train_state.py."""
 import copy
 import os
 import sys
@@ -386,6 +388,172 @@ def update_profile():
         i = identity_check(tag, B, 0)
         print(f"{tag:13s}{B:4d} | {i['wd'] * IDENTITY_SLACK:6.3f} {i['mom'] * IDENTITY_SLACK:6.3f} {i['lr'] * IDENTITY_SLACK:6.3f} | {i['exact']}", flush=True)
 
+
+# ---------------------------------------------------------------------------------------------------------------- the step as a function of its inputs
+# (tests/test_gpu_train_state.py).  Every comparison below is bit equality: the step has no float atomics and fixed combination orders,
+# so parameters, momenta, running statistics, Hyper and the batch decide every bit of a step -- whatever the workspace held before,
+# whatever ran earlier in the process, wherever the caller's arrays lie.  No tolerance, no float64 model, hence no ReLU ties.
+STATE_CASES = [("connect4", 32), ("connect4", 144), ("connect4", 512), ("connect4_5x8", 64), ("othello6", 48), ("othello6", 80), ("othello8", 144),
+               ("tictactoe", 2), ("tictactoe", 64)]  # the smallest batch that reaches each dispatch of enqueue_step
+STATE_HYPER = (0.1, 0.9, 1e-4)  # lr, momentum, weight decay: the reference's
+
+
+def state_dropout(tag):
+    return 0.0 if tag == "tictactoe" else 0.3  # (TicTacToeNet has no dropout)
+
+
+class StateProblem:
+    """problem(tag, B, steps) on the GPU with a batch order that includes row 0 and the LAST row of the sample arrays (a read before or
+    past a row shows at the arrays' ends); `net` is the CUDA module every run loads"""
+
+    def __init__(self, tag, B, steps=2, seed=0):
+        self.tag, self.B, self.n = tag, B, steps
+        net, state, pi, z, _ = problem(tag, B, steps, seed)
+        S = state.shape[0]
+        perm = torch.randperm(S, generator=torch.Generator().manual_seed(5 + seed))[: B * steps].clone()
+        for row, slot in ((0, 1), (S - 1, B * steps - 2)):  # into a slot that does not hold the other one
+            if not (perm == row).any():
+                perm[slot if perm[slot] not in (0, S - 1) else slot + 1] = row
+        assert len(set(perm.tolist())) == B * steps and 0 in perm and S - 1 in perm
+        self.net = net.cuda()
+        self.arrays = {"state": state.cuda(), "pi": pi.cuda(), "z": z.cuda(), "perm": perm.cuda(),
+                       "loss_pi": torch.zeros(steps, device="cuda"), "loss_v": torch.zeros(steps, device="cuda")}
+
+    def trainer(self, max_batch=None):
+        from alphazero_amd.train_step import HipTrainStep
+        return HipTrainStep(self.net, max_batch=max_batch or self.B)
+
+
+TWO_CALLS = ((0, 1), (1, 1))  # step 0 as a plain launch, step 1 from other pointers as a freshly captured graph
+
+
+def state_begin(hip, prob, load=None, begin=True):
+    """load: the module to load (None: prob.net; False: keep the trainer's parameters); begin: a fresh optimizer at STATE_HYPER, the
+    case's dropout and Philox seed 3 -> the (still empty) result of the run"""
+    if load is not False:
+        hip.load(prob.net if load is None else load)
+    if begin:
+        hip.begin(*STATE_HYPER, state_dropout(prob.tag), seed=3)
+    return {}
+
+
+def state_call(hip, prob, res, k, call, B=None, arrays=None):
+    """call k = (s, n) of a run: n steps in one az_trainer_steps from the pointers of step s (perm[s * B:], loss[s:]); the losses it wrote
+    go into res"""
+    (s, n), B, a = call, B or prob.B, arrays or prob.arrays
+    hip.steps(a["state"], a["pi"], a["z"], a["perm"][s * B:], n, B, a["loss_pi"][s:], a["loss_v"][s:])
+    hip.check()
+    torch.cuda.synchronize()
+    res[f"call{k}.loss_pi"], res[f"call{k}.loss_v"] = a["loss_pi"][s:s + n].cpu().numpy(), a["loss_v"][s:s + n].cpu().numpy()
+
+
+def state_end(hip, prob, res, out=None, workspace=False):
+    """reads the trainer back into res: every tensor of the state dict store() writes (into `out`; None: a copy of prob.net), and with
+    `workspace` every workspace buffer's bytes"""
+    out = copy.deepcopy(prob.net) if out is None else out
+    hip.store(out)
+    res.update({"sd." + k: v.detach().cpu().numpy() for k, v in out.state_dict().items()})
+    if workspace:
+        res.update({"ws." + k: v.cpu().numpy() for k, v in hip.views("workspace")})
+    return res
+
+
+def state_run(hip, prob, calls=TWO_CALLS, B=None, arrays=None, load=None, begin=True, out=None, before_call=None, workspace=False):
+    """state_begin, every call of `calls` (before_call(k) runs before call k; k = 0: after begin()), state_end -> {name: numpy array}"""
+    res = state_begin(hip, prob, load, begin)
+    for k, call in enumerate(calls):
+        if before_call is not None:
+            before_call(k)
+        state_call(hip, prob, res, k, call, B, arrays)
+    return state_end(hip, prob, res, out, workspace)
+
+
+def same_bits(a, b, what):
+    """asserts two results of state_run() equal bit for bit (as bytes: a NaN equals itself, -0.0 differs from 0.0)"""
+    assert sorted(a) == sorted(b), (what, sorted(set(a) ^ set(b)))
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
+        if a[k].tobytes() != b[k].tobytes():
+            x, y = np.ascontiguousarray(a[k]).reshape(-1), np.ascontiguousarray(b[k]).reshape(-1)
+            off = np.flatnonzero(x.view(np.uint8) != y.view(np.uint8)) // x.itemsize
+            raise AssertionError((what, k, f"{len(set(off.tolist()))} of {x.size} elements differ, first at {int(off[0])}: {x[off[0]]!r} != {y[off[0]]!r}"))
+
+
+def all_finite(res):
+    return all(np.isfinite(v).all() for k, v in res.items() if not k.startswith("ws.") and v.dtype.kind == "f")
+
+
+def poison_workspace(hip, kind):
+    """every byte of every workspace-class buffer: 0xFF (a NaN as float and as double: a multiplication by zero does not hide it) or
+    the float 1e30 repeated (finite, but nothing of the step's scale survives it)"""
+    n = 0
+    for _, v in hip.views("workspace"):
+        if kind == "nan":
+            v.fill_(0xFF)
+        else:
+            v.view(torch.float32).fill_(1e30)
+        n += 1
+    torch.cuda.synchronize()
+    return n
+
+
+def copy_state(src, dst):
+    """everything a step depends on besides its batch -- parameters, momenta, running statistics, Hyper (learning rate, step counter of
+    the dropout stream) -- from one trainer into another of the same network (their sizes do not depend on max_batch)"""
+    theirs = {name: (cls, p, n) for name, cls, p, n in dst.buffers()}
+    mine = [(name, cls, n) for name, cls, p, n in src.buffers() if cls != "workspace"]
+    assert sorted((name, cls, n) for name, (cls, p, n) in theirs.items() if cls != "workspace") == sorted(mine)
+    for cls in ("parameter", "momentum", "running_stat", "hyper"):
+        for (name, s), (name2, d) in zip(src.views(cls), dst.views(cls)):
+            assert name == name2
+            d.copy_(s)
+    dst.steps_done = src.steps_done
+    torch.cuda.synchronize()
+
+
+class Banded:
+    """Tensors carved as contiguous views out of larger buffers: on either side of a view lie at least `rows` rows of its array, every
+    byte of them `fill`; with `odd` the view starts at an odd element offset (the ABI promises no alignment beyond the element's own).
+    A stray read finds the band's bytes instead of whatever the allocator put there, a stray write is found by check()."""
+
+    def __init__(self, rows, fill, odd):
+        self.rows, self.fill, self.odd, self.items = rows, fill, odd, []
+
+    def empty(self, shape, dtype):
+        shape = tuple(shape)
+        n = int(np.prod(shape))
+        row = max(1, n // shape[0]) if shape and shape[0] else 1
+        band = (self.rows * row + 63) // 64 * 64
+        start = band + (1 if self.odd else 0)
+        buf = torch.empty(start + n + band, dtype=dtype, device="cuda")
+        buf.view(torch.uint8).fill_(self.fill)
+        self.items.append((buf, start, n))
+        return buf[start:start + n].view(shape)
+
+    def carve(self, t):
+        v = self.empty(t.shape, t.dtype)
+        v.copy_(t)
+        return v
+
+    def module(self, net):
+        """a copy of `net` whose float tensors -- what load() reads from and store() writes into -- are such views"""
+        m = copy.deepcopy(net)
+        for t in list(m.parameters()) + [b for b in m.buffers() if b.dtype == torch.float32]:
+            t.data = self.carve(t.data)
+        assert all(v.is_cuda and v.is_contiguous() for v in m.state_dict().values())
+        return m
+
+    def check(self):
+        """every band byte is what was written into it -> the number of band bytes checked"""
+        torch.cuda.synchronize()
+        total = 0
+        for buf, start, n in self.items:
+            b, e = buf.view(torch.uint8), buf.element_size()
+            lo, hi = b[: start * e], b[(start + n) * e:]
+            assert lo.numel() >= self.rows and hi.numel() >= self.rows
+            assert bool((lo == self.fill).all()) and bool((hi == self.fill).all()), ("a guard band was written", tuple(buf.shape), start, n)
+            total += lo.numel() + hi.numel()
+        return total
 
 if __name__ == "__main__":
     a = sys.argv[1:]
