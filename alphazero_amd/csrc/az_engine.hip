@@ -108,6 +108,9 @@ struct EngDev {
     // az_engine_set_gumbel_batch (k_step_gumbel_multi; then K above = its walkers): the slot's cursor = the simulations of the search
     // call already dealt, and the cursor at the start of the slot's current lock-step, [G] each
     int *gcur, *gstart;
+    // az_engine_set_gumbel_full: the network value of every evaluated node, [G][2][C] like nodes, in the frame of the player to move at
+    // the node.  Null unless the switch is in force (on, and the Gumbel mode on): then no kernel touches it.
+    float *nval;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -147,6 +150,8 @@ AZ_D Node fresh_node(int action, int parent, double P, int flags) {
 }
 
 AZ_D Node *pool_of(const EngDev &E, int g) { return E.nodes + ((size_t)g * 2 + E.pool_sel[g]) * E.C; }
+// the stored network values of a pool's nodes (az_engine_set_gumbel_full in force only): nval is laid out like nodes
+AZ_D float *nval_of(const EngDev &E, const Node *pool) { return E.nval + (pool - E.nodes); }
 
 // does this engine search slot g now? (active, and in arena mode only when its colour is to move)
 AZ_D bool searches(const EngDev &E, int g) { return E.active[g] && (E.side[g] == 0 || E.side[g] == E.root_player[g]); }
@@ -265,7 +270,8 @@ AZ_D int pick4(int v0, int v1, int v2, int v3, int r) { return r == 0 ? v0 : (r 
 // fair_max (utils.py:28-34) among the children a group has scored: one lane per child, 16 children per round.  Children [0, nvote)
 // take part in the ballot; when none of them holds the maximum, `none_err` (0: nothing) is raised.  `gid` is read only where a tie is
 // drawn.  The chosen child's header is handed back by shuffle from the lane that scored it (no second memory trip); returns the
-// child's index among the parent's children.
+// child's index among the parent's children.  DRAW false: ties go to the lowest index whatever tie_mode says, no Philox draw.
+template <bool DRAW = true>
 AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int depth, const Scored &s, int nvote, int none_err,
                         int sub, Node &chosen) {
     double best = grp_max(fmax(fmax(s.key[0], s.key[1]), fmax(s.key[2], s.key[3])));
@@ -275,7 +281,7 @@ AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int d
     for (int r = 0; r < 4; ++r) { mask[r] = grp_ballot((r * LPG + sub) < nvote && s.key[r] == best); cnt += __popc(mask[r]); }
     if (none_err && cnt == 0 && sub == 0) atomicOr(E.err, none_err);
     int k = 0;
-    if (E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {  // with a single maximum the draw cannot change the result
+    if (DRAW && E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {  // with a single maximum the draw cannot change the result
         Philox4 rr = az_philox(E.seed, gid, (u32)ply, (u32)sim + E.sim_base, AZ_P_TIE_SELECT, (u32)depth);
         k = (int)(((u64)rr.x * (u64)cnt) >> 32);
     }
@@ -348,7 +354,13 @@ struct Walk {
     bool bad;
 };
 
-// select_node's descent (mcts.py:127-171) of walker j, from wk (the root, or wherever wk stands) to its leaf.
+// the deterministic scorer of az_engine_set_gumbel_full (defined with the Gumbel root search below): pick_child_vl_grp's signature
+AZ_D int pick_child_gumbel_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
+                               int ply, int sim, int depth, int sub, Node &chosen);
+
+// select_node's descent (mcts.py:127-171) of walker j, from wk (the root, or wherever wk stands) to its leaf.  GUMBEL: the children
+// are scored by pick_child_gumbel_grp instead of PUCT (the full Gumbel kernels only; every other kernel takes the default).
+template <bool GUMBEL = false>
 AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], int j, int ply, int sim, int sub, Walk &wk) {
     for (;;) {
         bool fresh = false;
@@ -360,7 +372,8 @@ AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], 
             fresh = true;
         }
         Node ch;
-        const int c = pick_child_vl_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch);
+        const int c = GUMBEL ? pick_child_gumbel_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch)
+                             : pick_child_vl_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch);
         wk.node = c; wk.cur = ch;
         if (sub == wk.plen) wk.my_path = c;
         ++wk.plen;
@@ -554,7 +567,10 @@ __global__ __launch_bounds__(256) void k_root_init(EngDev E, int g0, int g1) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     if (g >= g1 || !E.root_fresh[g]) return;
     BB b = {E.root_p1[g], E.root_m1[g], E.root_player[g]};
-    create_children_grp(E, g, pool_of(E, g), E.n_nodes[g], E.root[g], b, E.probs + (size_t)E.row_of_slot[g] * E.A, sub);
+    Node *pool = pool_of(E, g);
+    const int k = create_children_grp(E, g, pool, E.n_nodes[g], E.root[g], b, E.probs + (size_t)E.row_of_slot[g] * E.A, sub);
+    // the value is discarded for the backup, as the reference discards it; az_engine_set_gumbel_full keeps it for the root's v_mix
+    if (E.nval && k > 0 && sub == 0) nval_of(E, pool)[E.root[g]] = E.value[E.row_of_slot[g]];
     if (sub == 0) E.evals[g] += 1;
 }
 
@@ -847,6 +863,14 @@ AZ_D void gumbel_phase(int s, int n, int m0, int &p, int &mp, int &i) {
     i = s - start;
 }
 
+// The paper's v_mix of a node (az_engine_set_gumbel_full): vhat = the network value stored for the node, sumN = the
+// sum of its children's real counts, num / den = the sums over its visited children of the contract above.
+AZ_D double gumbel_vmix_full(double vhat, int sumN, double num, double den) {
+    if (sumN == 0 || !(den > 0.0)) return vhat;
+    const double wq = num / den;
+    return (vhat + (double)sumN * wq) / (double)(1 + sumN);
+}
+
 AZ_D int kth_set_bit64(u64 mask, int k) {
     for (int i = 0; i < k; ++i) mask &= mask - 1;
     return mask ? __ffsll((long long)mask) - 1 : -1;
@@ -855,25 +879,32 @@ AZ_D u64 first_bits64(int n) { return n >= 64 ? ~0ULL : (1ULL << n) - 1ULL; }
 
 // The mp best by score among the children `prev` of the root, one lane per child and round: N / Q / P [r] are child r * LPG + sub
 // (absent: N = 0, P = 0).  At most 16 rounds of one group maximum each; a NaN score is an error (it equals no maximum).
+// FULL (az_engine_set_gumbel_full): vmix is the paper's, with vhat = the root's stored network value.
+template <bool FULL>
 AZ_D u64 gumbel_rerank_grp(const EngDev &E, const int (&N)[4], const double (&Q)[4], const double (&P)[4], const uint8_t (&act)[4],
-                           int nch, u64 prev, int mp, u32 gid, int ply, int sub) {
+                           int nch, u64 prev, int mp, u32 gid, int ply, double vhat, int sub) {
     double pq[4], pp[4];
-    int mx = 0;
+    int mx = 0, sn = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const bool vis = N[r] > 0;
         pq[r] = vis ? P[r] * Q[r] : 0.0;
         pp[r] = vis ? P[r] : 0.0;
         mx = N[r] > mx ? N[r] : mx;
+        sn += N[r];
     }
 #pragma unroll
     for (int m = 8; m >= 1; m >>= 1) { const int o = __shfl_xor(mx, m, LPG); mx = o > mx ? o : mx; }
+    if (FULL) {
+#pragma unroll
+        for (int m = 8; m >= 1; m >>= 1) sn += __shfl_xor(sn, m, LPG);
+    }
     double num = 0.0, den = 0.0;  // sequential sums in child-index order (an unvisited child adds an exact 0.0)
     for (int i = 0; i < nch; ++i) {
         num += __shfl(sel4(pq, i >> 4), i & 15, LPG);
         den += __shfl(sel4(pp, i >> 4), i & 15, LPG);
     }
-    const double vmix = den > 0.0 ? num / den : 0.0;
+    const double vmix = FULL ? gumbel_vmix_full(vhat, sn, num, den) : (den > 0.0 ? num / den : 0.0);
     const double k = (E.g_cvisit + (double)mx) * E.g_cscale;
     double sc[4];
     bool nan = false;
@@ -905,9 +936,82 @@ AZ_D u64 gumbel_rerank_grp(const EngDev &E, const int (&N)[4], const double (&Q)
     return sel;
 }
 
+// The deterministic non-root selection of the paper (az_engine_set_gumbel_full) for walker j at parent p, depth >= 1.
+// v(b) = the virtual count of child b (the walkers i < j of this lock-step whose recorded path holds b, pick_child_vl_grp's), vsum
+// their sum; sumN, maxN, vmix(p) and pi' on the real counts only; float64, one operation at a time, sums in child-index order:
+//   k      = (c_visit + (double)maxN) * c_scale          cq(b) = N(b) > 0 ? Q(b) : vmix(p)
+//   x(b)   = az_det_log(P(b)) + k * cq(b)                e(b)  = az_det_exp(x(b) - max x)       pi'(b) = e(b) / sum e
+//   key(b) = pi'(b) - (double)(N(b) + v(b)) / (double)(1 + sumN + vsum)
+// The child is the maximum of key, the lowest index among equals whatever tie_mode says (no Philox draw); NaN keys are an error.
+AZ_D int pick_child_gumbel_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
+                               int ply, int sim, int depth, int sub, Node &chosen) {
+    const int fc = parent.first, nch = parent.nch;
+    int vc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < MLB; ++i) {
+        if (i < j) {  // uniform over the group
+            const int cd = depth + 1 < LPG ? __shfl(vpath[i], (depth + 1) & (LPG - 1), LPG) : -1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vc[r] += cd == fc + r * LPG + sub ? 1 : 0;
+        }
+    }
+    Scored s;
+    double cQ[4], cP[4], pq[4], pp[4];
+    int mx = 0, sn = 0, sv = 0;
+    const float vhat = nval_of(E, pool)[pnode];  // one address for the group: a broadcast, in flight with the children
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        Node c;
+        cQ[r] = 0.0; cP[r] = 0.0;
+        if (load_child_grp(pool, parent, r, sub, s, c)) { cQ[r] = c.Q; cP[r] = c.P; }
+        const bool vis = s.N[r] > 0;
+        pq[r] = vis ? cP[r] * cQ[r] : 0.0;
+        pp[r] = vis ? cP[r] : 0.0;
+        mx = s.N[r] > mx ? s.N[r] : mx;
+        sn += s.N[r];
+        sv += r * LPG + sub < nch ? vc[r] : 0;  // a lane without a child may have matched a neighbouring block's node
+    }
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) {
+        const int o = __shfl_xor(mx, m, LPG);
+        mx = o > mx ? o : mx;
+        sn += __shfl_xor(sn, m, LPG);
+        sv += __shfl_xor(sv, m, LPG);
+    }
+    double num = 0.0, den = 0.0;  // sequential sums in child-index order (an unvisited child adds an exact 0.0)
+    for (int i = 0; i < nch; ++i) {
+        num += __shfl(sel4(pq, i >> 4), i & 15, LPG);
+        den += __shfl(sel4(pp, i >> 4), i & 15, LPG);
+    }
+    const double vmix = gumbel_vmix_full((double)vhat, sn, num, den);
+    const double k = (E.g_cvisit + (double)mx) * E.g_cscale;
+    double x[4], xm = -__builtin_inf();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        x[r] = -__builtin_inf();
+        if (r * LPG + sub < nch) x[r] = az_det_log(cP[r]) + k * (s.N[r] > 0 ? cQ[r] : vmix);
+        xm = fmax(xm, x[r]);
+    }
+    xm = grp_max(xm);
+    double ex[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ex[r] = r * LPG + sub < nch ? az_det_exp(x[r] - xm) : 0.0;
+    double sum = 0.0;
+    for (int i = 0; i < nch; ++i) sum += __shfl(sel4(ex, i >> 4), i & 15, LPG);
+    const double tot = (double)(1 + sn + sv);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (r * LPG + sub < nch) s.key[r] = ex[r] / sum - (double)(s.N[r] + vc[r]) / tot;
+    // every lane votes, and NaN keys (a diverged network) are an error: no key equals the maximum
+    const u32 no_draw = 0;
+    return fc + choose_max_grp<false>(E, no_draw, ply, sim, depth, s, 4 * LPG, ERR_INTERNAL, sub, chosen);
+}
+
 // One lock-step of the search in the Gumbel mode: k_step with the root's child taken from the Sequential Halving schedule instead
 // of pick_child_vl_grp and without root noise.  BACKUP and everything from the root's child downwards are k_step's.
-template <bool BACKUP, bool SELECT>
+// FULL (az_engine_set_gumbel_full): an evaluated leaf keeps its network value, the re-ranking takes the paper's v_mix, and below the
+// root the child is pick_child_gumbel_grp's.
+template <bool BACKUP, bool SELECT, bool FULL>
 __global__ __launch_bounds__(256) void k_step_gumbel(EngDev E, int sim, int n_sim, int g0, int g1) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     if (blockIdx.x == 0 && threadIdx.x == 0 && g0 == 0) { E.batch_cnt[(sim + 1) & 1] = 0; if (!SELECT) E.batch_cnt[2] = 0; }
@@ -944,6 +1048,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel(EngDev E, int sim, int n_si
             ok = k > 0;
             n_nodes += ok ? k : 0;
             outcome = (double)lb.player * (double)v;  // base.py:366
+            if (FULL && ok && sub == 0) nval_of(E, pool)[leaf] = v;
             if (ok) evals += 1;
             else { active = false; if (sub == 0) E.active[g] = 0; }
         } else {
@@ -969,6 +1074,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel(EngDev E, int sim, int n_si
     Walk wk = {b, Node(), node, 1, sub == 0 ? node : -1, false};
     if (active) {
         if (have_root) wk.cur = fwd; else wk.cur = load_node(pool + node);
+        const float vroot = FULL ? nval_of(E, pool)[node] : 0.0f;  // in flight with the root; read where a phase starts
         // the root's step of select_node (walk_grp's first turn) with the scheduled child
         bool fresh = false, stop = false;
         if (!(wk.cur.flags & F_EXPANDED)) {
@@ -996,7 +1102,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel(EngDev E, int sim, int n_si
             }
             const u64 all = first_bits64(nch);
             if (i == 0) {  // a phase starts: the candidates are ranked again
-                mask = mp == 1 ? 1ULL : gumbel_rerank_grp(E, s.N, cQ, cP, cact, nch, p == 0 ? all : (mask & all), mp, gid, ply, sub);
+                mask = mp == 1 ? 1ULL : gumbel_rerank_grp<FULL>(E, s.N, cQ, cP, cact, nch, p == 0 ? all : (mask & all), mp, gid, ply, (double)vroot, sub);
                 if (sub == 0) E.gmask[g] = mask;
             }
             int c = kth_set_bit64(mask & all, i % mp);
@@ -1013,7 +1119,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel(EngDev E, int sim, int n_si
             az_play_grp(E.gd, wk.b, wk.cur.act, sub);
             if (!(fresh || wk.cur.N == 0)) {
                 const int no_walkers[MLB] = {};
-                walk_grp(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
+                walk_grp<FULL>(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
             }
         }
         E.path[(size_t)g * LPG + sub] = wk.my_path;
@@ -1068,7 +1174,8 @@ AZ_D int gumbel_phase_end(int s, int n, int m0) {
 // the slot, the slot count or the block; K = 1 never comes here (k_step_gumbel).
 // gcur [G] = the cursor, gstart [G] = its value at the start of the slot's current lock-step (k_sym_pick's simulation index and the
 // number of walkers the next launch backs up: gcur - gstart).  Lane j of the group owns walker j's pending words, as in k_step_multi.
-template <bool BACKUP, bool SELECT>
+// FULL (az_engine_set_gumbel_full): as in k_step_gumbel; the virtual counts enter pick_child_gumbel_grp's subtracted term only.
+template <bool BACKUP, bool SELECT, bool FULL>
 __global__ __launch_bounds__(256) void k_step_gumbel_multi(EngDev E, int t, int n_sim) {
     const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     if (blockIdx.x == 0 && threadIdx.x == 0) { E.batch_cnt[(t + 1) & 1] = 0; if (!SELECT) E.batch_cnt[2] = 0; }
@@ -1116,6 +1223,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel_multi(EngDev E, int t, int 
                     ok = k > 0;
                     n_nodes += ok ? k : 0;
                     outcome = (double)lb.player * (double)v;  // base.py:366
+                    if (FULL && ok && sub == 0) nval_of(E, pool)[leaf] = v;
                     if (ok) evals += 1;
                     if (sub == j) p_out = outcome;
                 } else if (st >= LS_DUP) {
@@ -1144,6 +1252,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel_multi(EngDev E, int t, int 
     int kt = 0;
     if (active && cur < n_sim) {
         Node rootn = load_node(pool + root);
+        const float vroot = FULL ? nval_of(E, pool)[root] : 0.0f;  // in flight with the root; read where a phase starts
         // k_step_gumbel's tests at the root: the same for every walker of the lock-step but `fresh`, which only walker 0 can see
         const bool unexp = !(rootn.flags & F_EXPANDED);
         const bool root_term = unexp && (rootn.flags & F_TERMINAL);
@@ -1167,7 +1276,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel_multi(EngDev E, int t, int 
             }
             if (i0 == 0) {  // a phase starts with walker 0: the candidates are ranked again, on real statistics
                 const u64 all = first_bits64(nch);
-                mask = mp == 1 ? 1ULL : gumbel_rerank_grp(E, s.N, cQ, cP, cact, nch, p == 0 ? all : (mask & all), mp, gid, ply, sub);
+                mask = mp == 1 ? 1ULL : gumbel_rerank_grp<FULL>(E, s.N, cQ, cP, cact, nch, p == 0 ? all : (mask & all), mp, gid, ply, (double)vroot, sub);
                 if (sub == 0) E.gmask[g] = mask;
             }
             mask &= first_bits64(nch);
@@ -1199,7 +1308,7 @@ __global__ __launch_bounds__(256) void k_step_gumbel_multi(EngDev E, int t, int 
                 if (sub == wk.plen) wk.my_path = wk.node;
                 ++wk.plen;
                 az_play_grp(E.gd, wk.b, wk.cur.act, sub);
-                if (!(fresh || wk.cur.N == 0)) walk_grp(E, g, pool, vpath, j, ply, sim, sub, wk);
+                if (!(fresh || wk.cur.N == 0)) walk_grp<FULL>(E, g, pool, vpath, j, ply, sim, sub, wk);
             }
             E.m_path[((size_t)g * MLB + j) * LPG + sub] = wk.my_path;
 #pragma unroll
@@ -1344,15 +1453,17 @@ AZ_D double linear_temp(int step, int tmax, int tmin) {  // schedulers.py:33-40
 // only reports it) both call this, so what a readout shows is what an advance would record and play.
 // Gumbel mode (the contract above k_step_gumbel): the move is the best score among the candidates `gmask` (0: all children) on the
 // statistics as they stand, pi the softmax of logit + sigma over all children; the temperature plays no part.
-AZ_D int gumbel_move_policy(const EngDev &E, const Node *pool, int fc, int nc, u64 gmask, u32 gid, int ply, float *pi) {
+// vroot: the root's stored network value when az_engine_set_gumbel_full is in force (vmix is then the paper's), else null.
+AZ_D int gumbel_move_policy(const EngDev &E, const Node *pool, int fc, int nc, u64 gmask, u32 gid, int ply, const float *vroot, float *pi) {
     double num = 0.0, den = 0.0;
-    int maxN = 0;
+    int maxN = 0, sumN = 0;
     for (int i = 0; i < nc; ++i) {
         const int n = pool[fc + i].N;
         if (n > 0) { const double P = pool[fc + i].P; num += P * pool[fc + i].Q; den += P; }
         maxN = n > maxN ? n : maxN;
+        sumN += n;
     }
-    const double vmix = den > 0.0 ? num / den : 0.0;
+    const double vmix = vroot ? gumbel_vmix_full((double)*vroot, sumN, num, den) : (den > 0.0 ? num / den : 0.0);
     const double k = (E.g_cvisit + (double)maxN) * E.g_cscale;
     gmask &= first_bits64(nc);
     if (gmask == 0) gmask = first_bits64(nc);
@@ -1382,8 +1493,8 @@ AZ_D int gumbel_move_policy(const EngDev &E, const Node *pool, int fc, int nc, u
     return pick;
 }
 
-AZ_D int move_policy(const EngDev &E, const Node *pool, int fc, int nc, double temp, u32 gid, int ply, u64 gmask, float *pi) {
-    if (E.gm > 0) return gumbel_move_policy(E, pool, fc, nc, gmask, gid, ply, pi);
+AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc, double temp, u32 gid, int ply, u64 gmask, float *pi) {
+    if (E.gm > 0) return gumbel_move_policy(E, pool, fc, nc, gmask, gid, ply, E.nval ? nval_of(E, pool) + root : nullptr, pi);
     if (temp == 0.0) {  // fair_max by N
         int best = -1, cnt = 0, first = 0;
         for (int i = 0; i < nc; ++i) {
@@ -1447,7 +1558,7 @@ __global__ void k_move(EngDev E) {
     int *vis = si >= 0 ? E.o_visits + (size_t)si * E.A : nullptr;
     if (si >= 0) for (int a = 0; a < E.A; ++a) { pi[a] = 0.0f; vis[a] = 0; }
 
-    const int chosen = fc + move_policy(E, pool, fc, nc, temp, gid, ply, E.gmask[g], pi);
+    const int chosen = fc + move_policy(E, pool, root, fc, nc, temp, gid, ply, E.gmask[g], pi);
     E.gmask[g] = 0;  // the candidates belong to the root that is left here
     int action = pool[chosen].act;
     if (si >= 0) {
@@ -1485,16 +1596,21 @@ __global__ void k_move(EngDev E) {
 // copied breadth-first into the slot's other pool and becomes node 0.  While a node waits in the queue its
 // `first` field still holds the OLD index of its children; when its level is processed the children are copied
 // to a freshly bump-allocated block and `first` is rewritten.  16 lanes take 16 queue nodes per round.
+// FULL (az_engine_set_gumbel_full in force): a node's network value travels with the node, to the same new index.
+template <bool FULL>
 __global__ __launch_bounds__(256) void k_reroot(EngDev E) {
     const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     if (g >= E.G || !E.active[g]) return;
     const int sel = E.pool_sel[g];
     const Node *src = E.nodes + ((size_t)g * 2 + sel) * E.C;
     Node *dst = E.nodes + ((size_t)g * 2 + (sel ^ 1)) * E.C;
+    const float *vsrc = FULL ? nval_of(E, src) : nullptr;
+    float *vdst = FULL ? nval_of(E, dst) : nullptr;
     if (sub == 0) {
         Node r = load_node(src + E.root[g]);
         r.parent = -1;
         store_node(dst, r);
+        if (FULL) vdst[0] = vsrc[E.root[g]];
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     int lo = 0, hi = 1, next = 1;
@@ -1515,11 +1631,16 @@ __global__ __launch_bounds__(256) void k_reroot(EngDev E) {
                 // paid the memory latency once per child: the kernel took ~0.4 ms per ply)
                 for (int j = 0; j < cnt; j += 4) {
                     Node c[4];
+                    float cv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                     for (int u = 0; u < 4; ++u) c[u] = load_node(src + oldfc + (j + u < cnt ? j + u : cnt - 1));
+                    if (FULL) {
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) cv[u] = vsrc[oldfc + (j + u < cnt ? j + u : cnt - 1)];
+                    }
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
-                        if (j + u < cnt) { c[u].parent = i; store_node(dst + newfc + j + u, c[u]); }
+                        if (j + u < cnt) { c[u].parent = i; store_node(dst + newfc + j + u, c[u]); if (FULL) vdst[newfc + j + u] = cv[u]; }
                 }
                 dst[i].first = newfc;
             }
@@ -1660,7 +1781,7 @@ __global__ __launch_bounds__(256) void k_root_readout(EngDev E, int n, const dou
         if (served && (o.pi || o.action)) {
             const int ply = E.ply[g];
             const double temp = temps ? temps[g] : linear_temp(ply, E.tmax, E.tmin);
-            act = pool[fc + move_policy(E, pool, fc, nc, temp, E.game_id[g], ply, E.gmask[g], o.pi ? o.pi + (size_t)g * A : nullptr)].act;
+            act = pool[fc + move_policy(E, pool, E.root[g], fc, nc, temp, E.game_id[g], ply, E.gmask[g], o.pi ? o.pi + (size_t)g * A : nullptr)].act;
         }
         if (o.action) o.action[g] = act;
         if (o.root_N) o.root_N[g] = served ? rn.N : 0;
@@ -1908,6 +2029,10 @@ struct az_engine {
     int leaf_batch = 1, net_rows = 0;
     // az_engine_set_gumbel_batch: the walkers of the Gumbel mode, in force (d.K) only while d.gm > 0
     int gumbel_batch = 1;
+    // az_engine_set_gumbel_full: the switch and the per-node network values, [G][2][C], allocated when it first goes on; in force
+    // (d.nval == nval) only while d.gm > 0, else d.nval is null
+    int gumbel_full = 0;
+    float *nval = nullptr;
 };
 
 int az_make_game_desc(int game, int H, int W, GameDesc *gd) {
@@ -1986,6 +2111,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.sample_cap = cfg->sample_capacity;
     d.K = 1; e->net_rows = d.G;
     d.gm = 0; d.g_cvisit = 0.0; d.g_cscale = 0.0; d.g_scale = 0.0;
+    d.nval = nullptr;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2018,6 +2144,14 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
 
 static int fetch_counters(az_engine *e);
 static int check_err(az_engine *e);
+
+// change_root for every active slot; with az_engine_set_gumbel_full in force the instantiation that moves the stored values too
+static void launch_reroot(az_engine *e) {
+    const EngDev &d = e->d;
+    const dim3 gg((unsigned)((d.G + GPB - 1) / GPB)), gb(256);
+    if (d.nval) hipLaunchKernelGGL((k_reroot<true>), gg, gb, 0, e->stream, d);
+    else hipLaunchKernelGGL((k_reroot<false>), gg, gb, 0, e->stream, d);
+}
 
 extern "C" void az_engine_destroy(az_engine *e) {
     if (!e) return;
@@ -2122,14 +2256,19 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
     hipLaunchKernelGGL(k_root_prep, gg, gb, 0, e->stream, d, 0, d.G);
     AZ_TRY(forward(e, d.batch_cnt + 2, cap, -1));
     hipLaunchKernelGGL(k_root_init, gg, gb, 0, e->stream, d, 0, d.G);
+    // az_engine_set_gumbel_full in force: the other instantiation of the two Gumbel kernels (no run-time branch inside the walk)
+    const bool full = d.nval != nullptr;
+#define GUMBEL_LAUNCH(kern, B, S, ...) do { \
+        if (full) hipLaunchKernelGGL((kern<B, S, true>), gg, gb, 0, e->stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kern<B, S, false>), gg, gb, 0, e->stream, __VA_ARGS__); } while (0)
     if (d.gm > 0 && d.K > 1) {  // Sequential Halving with K walkers: Lmax lock-steps, cut per slot by its own cursor, then the last backup
         const int L = gumbel_locksteps(n_sim, d.gm, d.K);
         for (int t = 0; t < L; ++t) {
-            if (t == 0) hipLaunchKernelGGL((k_step_gumbel_multi<false, true>), gg, gb, 0, e->stream, d, t, n_sim);
-            else hipLaunchKernelGGL((k_step_gumbel_multi<true, true>), gg, gb, 0, e->stream, d, t, n_sim);
+            if (t == 0) GUMBEL_LAUNCH(k_step_gumbel_multi, false, true, d, t, n_sim);
+            else GUMBEL_LAUNCH(k_step_gumbel_multi, true, true, d, t, n_sim);
             AZ_TRY(forward(e, d.batch_cnt + (t & 1), cap, t, d.K));
         }
-        hipLaunchKernelGGL((k_step_gumbel_multi<true, false>), gg, gb, 0, e->stream, d, L, n_sim);
+        GUMBEL_LAUNCH(k_step_gumbel_multi, true, false, d, L, n_sim);
         AZ_HIP(hipGetLastError());
         return AZ_OK;
     }
@@ -2147,14 +2286,15 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
     }
     if (d.gm > 0) {  // the Gumbel root search: k_step's launch sequence with k_step_gumbel
         for (int s = 0; s < n_sim; ++s) {
-            if (s == 0) hipLaunchKernelGGL((k_step_gumbel<false, true>), gg, gb, 0, e->stream, d, s, n_sim, 0, d.G);
-            else hipLaunchKernelGGL((k_step_gumbel<true, true>), gg, gb, 0, e->stream, d, s, n_sim, 0, d.G);
+            if (s == 0) GUMBEL_LAUNCH(k_step_gumbel, false, true, d, s, n_sim, 0, d.G);
+            else GUMBEL_LAUNCH(k_step_gumbel, true, true, d, s, n_sim, 0, d.G);
             AZ_TRY(forward(e, d.batch_cnt + (s & 1), cap, s));
         }
-        hipLaunchKernelGGL((k_step_gumbel<true, false>), gg, gb, 0, e->stream, d, n_sim, n_sim, 0, d.G);
+        GUMBEL_LAUNCH(k_step_gumbel, true, false, d, n_sim, n_sim, 0, d.G);
         AZ_HIP(hipGetLastError());
         return AZ_OK;
     }
+#undef GUMBEL_LAUNCH
     for (int s = 0; s < n_sim; ++s) {
         if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
         else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
@@ -2184,8 +2324,9 @@ static int do_search(az_engine *e, int n_sim) {
     if (!graphable) return enqueue_search(e, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
     cap = cap_q;
     // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31).  A change
-    // of K (either setter) drops every graph.
-    const unsigned long long key = ((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)n_sim << 32) | (unsigned)cap;
+    // of K (either setter) drops every graph.  The full Gumbel kernels are other kernels again (bit 31; cap < 2^31).
+    const unsigned long long key = ((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)n_sim << 32) |
+                                   ((unsigned long long)(d.nval != nullptr) << 31) | (unsigned)cap;
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) {
         AZ_HIP(hipGraphLaunch(it->second, e->stream));
@@ -2270,7 +2411,7 @@ extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_gam
         e->sim_base = 0;
         AZ_TRY(do_search(e, e->cfg.n_sim));
         hipLaunchKernelGGL(k_move, grid_for(d.G, TB), dim3(TB), 0, e->stream, d);
-        hipLaunchKernelGGL(k_reroot, dim3((unsigned)((d.G + GPB - 1) / GPB)), dim3(256), 0, e->stream, d);
+        launch_reroot(e);
         AZ_TRY(fetch_counters(e));
         AZ_TRY(check_err(e));
         if (e->h_ctr[CTR_GAMES_DONE] >= (unsigned long long)n_games) return AZ_OK;
@@ -2418,7 +2559,7 @@ extern "C" int az_engine_advance(az_engine *e) {
     EngDev &d = e->d;
     // games that end here must not be refilled: cap the queue at what has been started
     hipLaunchKernelGGL(k_move, grid_for(d.G, TB), dim3(TB), 0, e->stream, d);
-    hipLaunchKernelGGL(k_reroot, dim3((unsigned)((d.G + GPB - 1) / GPB)), dim3(256), 0, e->stream, d);
+    launch_reroot(e);
     AZ_TRY(fetch_counters(e));
     return check_err(e);
 }
@@ -2512,10 +2653,30 @@ extern "C" int az_engine_grow_pools(az_engine *e, int32_t node_capacity) {
         er = hipMemcpy2DAsync(fresh, (size_t)node_capacity * sizeof(Node), d.nodes, (size_t)d.C * sizeof(Node), (size_t)d.C * sizeof(Node), rows,
                               hipMemcpyDeviceToDevice, e->stream);
     if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
-    if (er != hipSuccess) { (void)hipFree(fresh); az_set_error("growing the node pools failed: %s", hipGetErrorString(er)); return AZ_EHIP; }
+    float *fresh_v = nullptr;  // the stored network values (az_engine_set_gumbel_full) are laid out like the nodes and move with them
+    if (er == hipSuccess && e->nval) {
+        er = hipMalloc((void **)&fresh_v, rows * (size_t)node_capacity * sizeof(float));
+        if (er == hipSuccess) er = hipMemsetAsync(fresh_v, 0, rows * (size_t)node_capacity * sizeof(float), e->stream);
+        if (er == hipSuccess)
+            er = hipMemcpy2DAsync(fresh_v, (size_t)node_capacity * sizeof(float), e->nval, (size_t)d.C * sizeof(float), (size_t)d.C * sizeof(float), rows,
+                                  hipMemcpyDeviceToDevice, e->stream);
+        if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
+    }
+    if (er != hipSuccess) {
+        (void)hipFree(fresh);
+        if (fresh_v) (void)hipFree(fresh_v);
+        az_set_error("growing the node pools failed: %s", hipGetErrorString(er));
+        return AZ_EHIP;
+    }
     for (auto &p : e->allocs) if (p == (void *)d.nodes) p = (void *)fresh;
     (void)hipFree(d.nodes);
     d.nodes = fresh;
+    if (fresh_v) {
+        for (auto &p : e->allocs) if (p == (void *)e->nval) p = (void *)fresh_v;
+        (void)hipFree(e->nval);
+        if (d.nval) d.nval = fresh_v;
+        e->nval = fresh_v;
+    }
     d.C = node_capacity;
     e->cfg.node_capacity = node_capacity;
     // captured searches hold the old pool pointer and capacity by value
@@ -2535,7 +2696,7 @@ extern "C" int az_engine_play(az_engine *e, const int32_t *h_actions, int32_t n,
     int *d_act = e->scr_a, *d_st = e->scr_b;
     AZ_HIP(hipMemcpyAsync(d_act, h_actions, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_apply_moves, grid_for(n, TB), dim3(TB), 0, e->stream, d, d_act, (int)n, d_st);
-    hipLaunchKernelGGL(k_reroot, dim3((unsigned)((d.G + GPB - 1) / GPB)), dim3(256), 0, e->stream, d);
+    launch_reroot(e);
     AZ_HIP(hipMemcpyAsync(h_status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
     for (int i = 0; i < n; ++i)
@@ -2738,6 +2899,28 @@ extern "C" int az_engine_collisions(az_engine *e, int64_t *n) {
 }
 
 // ---- Gumbel root search (k_step_gumbel, gumbel_move_policy) -------------------------------------------------------------
+// az_engine_set_gumbel_full comes into force (the switch goes on while the mode is on, or the mode with the switch on): from then on
+// v_mix reads the stored value of every evaluated node it meets, so no active slot may hold a tree that was evaluated without
+// storing.  A fresh root (not evaluated: after az_engine_set_roots, a reset slot of az_engine_run) has no such node.
+__global__ void k_count_evaluated_roots(EngDev E, int *out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G || !E.active[g]) return;
+    if (pool_of(E, g)[E.root[g]].flags & F_EVALUATED) atomicAdd(out, 1);
+}
+
+static int full_needs_fresh_roots(az_engine *e, const char *who) {
+    EngDev &d = e->d;
+    int n = 0;
+    AZ_HIP(hipMemsetAsync(e->scr_a, 0, sizeof(int), e->stream));
+    hipLaunchKernelGGL(k_count_evaluated_roots, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, e->scr_a);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipMemcpyAsync(&n, e->scr_a, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    AZ_REQUIRE(n == 0, AZ_ESTATE, "%s: gumbel_full would come into force while %d active slot(s) hold evaluated nodes whose network value was "
+               "never stored; start the trees afresh first (az_engine_set_roots / az_engine_run; Python: set_roots, reset)", who, n);
+    return AZ_OK;
+}
+
 extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, double c_scale, double gumbel_scale) {
     AZ_REQUIRE(e, AZ_EINVAL, "null engine");
     AZ_NO_OPEN_SEARCH(e, "az_engine_set_gumbel");
@@ -2757,10 +2940,12 @@ extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, dou
         AZ_REQUIRE((long long)e->gumbel_batch * d.G <= az_net_max_batch(e->net), AZ_EINVAL, "az_engine_set_gumbel: gumbel_batch %d of %d slots are %lld rows, the network's max_batch is %d",
                    e->gumbel_batch, d.G, (long long)e->gumbel_batch * d.G, az_net_max_batch(e->net));
     AZ_TRY(enter(e));
+    if (m > 0 && d.gm == 0 && e->gumbel_full) AZ_TRY(full_needs_fresh_roots(e, "az_engine_set_gumbel"));  // the switch comes into force with the mode
     AZ_HIP(hipMemsetAsync(d.gmask, 0, sizeof(u64) * (size_t)d.G, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
     AZ_TRY(set_walkers(e, m > 0 ? e->gumbel_batch : e->leaf_batch));  // gumbel_batch is in force only while the mode is on
     d.gm = m;
+    d.nval = (m > 0 && e->gumbel_full) ? e->nval : nullptr;
     d.g_cvisit = m > 0 ? c_visit : 0.0; d.g_cscale = m > 0 ? c_scale : 0.0; d.g_scale = m > 0 ? gumbel_scale : 0.0;
     // the launch sequence of a search changes: nothing captured before may be replayed
     drop_graphs(e);
@@ -2800,5 +2985,51 @@ extern "C" int az_engine_gumbel_considered(az_engine *e, int32_t slot, uint64_t 
     AZ_TRY(enter(e));
     AZ_HIP(hipMemcpyAsync(mask, e->d.gmask + slot, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
+    return AZ_OK;
+}
+
+// the paper's v_mix and deterministic non-root selection on top of the Gumbel mode: accepted with the mode on or
+// off, in force while it is on
+extern "C" int az_engine_set_gumbel_full(az_engine *e, int32_t on) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_gumbel_full");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_gumbel_full");
+    EngDev &d = e->d;
+    AZ_REQUIRE(on == 0 || on == 1, AZ_EINVAL, "gumbel_full must be 0 or 1, got %d", on);
+    if (on == e->gumbel_full) return AZ_OK;
+    AZ_TRY(enter(e));
+    if (on) {
+        if (d.gm > 0) AZ_TRY(full_needs_fresh_roots(e, "az_engine_set_gumbel_full"));
+        if (!e->nval) {
+            AZ_TRY(dev_alloc(e, &e->nval, 2 * (size_t)d.G * (size_t)d.C));
+            AZ_HIP(hipStreamSynchronize(e->stream));
+        }
+    }
+    e->gumbel_full = on;
+    d.nval = (on && d.gm > 0) ? e->nval : nullptr;
+    // the Gumbel kernels of a search change: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_root_value(az_engine *e, int32_t slot, float *v) {
+    AZ_REQUIRE(e && v, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_root_value");
+    AZ_USABLE(e, "az_engine_root_value");
+    EngDev &d = e->d;
+    AZ_REQUIRE(slot >= 0 && slot < d.G, AZ_EINVAL, "slot %d outside [0, %d)", slot, d.G);
+    AZ_REQUIRE(d.nval, AZ_ESTATE, "az_engine_root_value: no network values are kept (az_engine_set_gumbel_full is off, or the Gumbel mode is)");
+    AZ_TRY(enter(e));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    int root = 0;
+    uint8_t sel = 0, active = 0;
+    AZ_HIP(hipMemcpy(&sel, d.pool_sel + slot, 1, hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(&active, d.active + slot, 1, hipMemcpyDeviceToHost));
+    AZ_HIP(hipMemcpy(&root, d.root + slot, sizeof(int), hipMemcpyDeviceToHost));
+    const size_t at = ((size_t)slot * 2 + sel) * d.C + root;
+    Node rn;
+    AZ_HIP(hipMemcpy(&rn, d.nodes + at, sizeof(Node), hipMemcpyDeviceToHost));
+    AZ_REQUIRE(active && (rn.flags & F_EVALUATED), AZ_ESTATE, "az_engine_root_value: the root of slot %d has not been evaluated (or the slot holds no game)", slot);
+    AZ_HIP(hipMemcpy(v, d.nval + at, sizeof(float), hipMemcpyDeviceToHost));
     return AZ_OK;
 }

@@ -380,6 +380,21 @@ class SelfPlayEngine:
         from .gumbel import check_gumbel_batch
         check(lib().az_engine_set_gumbel_batch(self.h, check_gumbel_batch(k, gumbel=True)))
 
+    def set_gumbel_full(self, on):
+        """the full Gumbel search (az_engine_set_gumbel_full): every evaluated node keeps its network value, v_mix
+        is the paper's (the node's own value mixed with its visited children), and below the root the child is chosen
+        deterministically by pi' - N / (1 + sum N) instead of PUCT.  Accepted with the Gumbel mode on or off, in force while it is
+        on.  It cannot come into force on trees that were searched without it: set_roots (or a reset of the player) first."""
+        from .gumbel import check_gumbel_full
+        check(lib().az_engine_set_gumbel_full(self.h, int(check_gumbel_full(on, gumbel=True))))
+
+    def root_value(self, slot=0):
+        """the network value stored for the slot's root, in the frame of the player to move there (float32 as a Python float); an
+        error unless set_gumbel_full is in force and the root is evaluated"""
+        v = C.c_float()
+        check(lib().az_engine_root_value(self.h, int(slot), C.byref(v)))
+        return v.value
+
     def considered(self, slot=0):
         """the root children the slot's Sequential Halving considers now, as ascending child indices ([]: none chosen yet, which
         reads as all children)"""

@@ -9,6 +9,7 @@ import struct
 
 import numpy as np
 
+_INF = float("inf")
 MAX_GUMBEL = 16  # AZ_MAX_GUMBEL (include/az_amd.h)
 P_GUMBEL = 9     # AZ_P_GUMBEL: Philox counter word 2 of the root's Gumbel draws
 DEFAULTS = {"m": 16, "c_visit": 50.0, "c_scale": 0.5, "gumbel_scale": 1.0}
@@ -112,6 +113,34 @@ def check_gumbel_batch(gumbel_batch, gumbel=None, symmetry=None):
     return k
 
 
+def check_gumbel_full(full, gumbel=None):
+    """bool(full) (az_engine_set_gumbel_full; DESIGN section 18: the paper's v_mix and its deterministic selection below the root);
+    ValueError -- before any device work -- for anything but a bool, and for True without the Gumbel mode (gumbel=...)."""
+    if not isinstance(full, (bool, np.bool_)):
+        raise ValueError(f"gumbel_full must be True or False, got {full!r}")
+    if full and gumbel is None:
+        raise ValueError("gumbel_full=True needs the Gumbel root search (gumbel=...): it completes that search below the root")
+    return bool(full)
+
+
+def nonroot_choice(pi, counts, virtual=None):
+    """the child the full Gumbel search takes below the root: the index of the greatest
+    key(b) = pi[b] - (counts[b] + virtual[b]) / (1 + sum(counts) + sum(virtual)) in float64, the lowest index among equals.
+    pi: the improved policy pi' at the parent (real counts only); counts: the children's real visit counts; virtual: their virtual
+    counts (None: all 0).  ValueError when no key compares (NaN)."""
+    n = len(pi)
+    virtual = [0] * n if virtual is None else virtual
+    tot = float(1 + sum(int(c) for c in counts) + sum(int(v) for v in virtual))
+    best, pick = -_INF, -1
+    for b in range(n):
+        key = float(pi[b]) - float(int(counts[b]) + int(virtual[b])) / tot
+        if pick < 0 and key == key or key > best:
+            best, pick = key, b
+    if pick < 0:
+        raise ValueError("nonroot_choice: every key is NaN")
+    return pick
+
+
 def lockstep_plan(n, m0, K):
     """the lock-steps [(s, kt)] of a search call of n simulations over m0 sampled actions with gumbel_batch = K: s is the slot's
     cursor at the start of the lock-step, kt = min(K, end of the current phase - s, n - s) its walkers.  No lock-step crosses a
@@ -137,9 +166,6 @@ def locksteps(n, m, K):
     """Lmax(n, m, K): the lock-steps the host enqueues per search call (plus the final backup-only launch) -- the longest plan of
     any m0 in 1..m, a pure function, so the launch sequence is the same for every slot count and captures as a graph"""
     return max((len(lockstep_plan(n, m0, K)) for m0 in range(1, int(m) + 1)), default=0)
-
-
-_INF = float("inf")
 
 
 def det_log(x):

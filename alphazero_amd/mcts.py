@@ -55,7 +55,7 @@ def check_symmetry(symmetry, nn):
 
 MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
 
-from .gumbel import check_gumbel, check_gumbel_batch  # noqa: E402  (the Gumbel root search's spec and refusals)
+from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full  # noqa: E402  (the Gumbel root search's spec and refusals)
 
 
 def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
@@ -87,7 +87,7 @@ def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
 
 class MCT:
     def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None,
-                 leaf_batch=None, gumbel=None, gumbel_batch=1):
+                 leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False):
         self.n_rollouts = 0
         self.simulation_time = 0
         self.eval_method = TreeEval.to_dict()["rollout" if eval_method is None else eval_method]
@@ -122,6 +122,11 @@ class MCT:
         self.gumbel_batch = gumbel_batch
         self._engine_gb = 1           # the gumbel_batch the engine is set to
         check_gumbel_batch(gumbel_batch, gumbel, symmetry)
+        # the full Gumbel search: the paper's v_mix with every node's own network value and its deterministic
+        # selection below the root; needs `gumbel`
+        self.gumbel_full = gumbel_full
+        self._engine_gf = False       # the gumbel_full the engine is set to
+        check_gumbel_full(gumbel_full, gumbel)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -151,6 +156,7 @@ class MCT:
             raise ValueError("MCT.search needs to have either n_sim or compute_time specified.")
         check_gumbel(self.gumbel, self._nn, self.leaf_batch, self.eval_method == TreeEval.NEURAL, compute_time)
         check_gumbel_batch(self.gumbel_batch, self.gumbel, self.symmetry)
+        check_gumbel_full(self.gumbel_full, self.gumbel)
         self._sync_device_root(board, n_sim)
         if n_sim is not None:
             self._ensure_room(n_sim)
@@ -262,11 +268,16 @@ class MCT:
             self._engine_lb = 1
             self._engine_gumbel = None
             self._engine_gb = 1
+            self._engine_gf = False
         lb = check_leaf_batch(self.leaf_batch, self._nn if neural else None, self.symmetry, neural)
         if self._engine_lb != lb:
             self._engine.set_leaf_batch(lb)
             self._engine_lb = lb
         gum = check_gumbel(self.gumbel, self._nn if neural else None, self.leaf_batch, neural)
+        gf = check_gumbel_full(self.gumbel_full, self.gumbel)
+        if self._engine_gf and not gf:  # off before the mode may change: the switch never comes into force with set_gumbel
+            self._engine.set_gumbel_full(False)
+            self._engine_gf = False
         if self._engine_gumbel != gum:
             self._engine.set_gumbel(self.gumbel)
             self._engine_gumbel = gum
@@ -280,6 +291,9 @@ class MCT:
                                    game_ids=np.array([np.random.randint(0, 2**31 - 1)], np.uint32))
             self._root_key = key
             self._used_bound = 1  # a fresh tree: the root
+        if self._engine_gf != gf:  # on after set_roots: a fresh tree holds no node evaluated without its value; a kept one is refused
+            self._engine.set_gumbel_full(gf)
+            self._engine_gf = gf
         self._last_board = board.clone()
 
     _MAX_POOL = 1 << 24  # nodes per pool (512 MiB): beyond it the engine reports AZ_ECAPACITY

@@ -62,7 +62,7 @@ class AlphaZeroTrainer:
     DEFAULT_EXP_NAME = "alphazero-undefined"
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
-                 selfplay_gumbel=None, selfplay_gumbel_batch=1):
+                 selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -96,6 +96,10 @@ class AlphaZeroTrainer:
         self.selfplay_gumbel_batch = selfplay_gumbel_batch
         from .gumbel import check_gumbel_batch
         check_gumbel_batch(selfplay_gumbel_batch, selfplay_gumbel)
+        # the full Gumbel search for that wave: the paper's v_mix and its deterministic selection below the root
+        self.selfplay_gumbel_full = selfplay_gumbel_full
+        from .gumbel import check_gumbel_full
+        check_gumbel_full(selfplay_gumbel_full, selfplay_gumbel)
 
     def _check_selfplay_symmetry(self):
         from .symmetry import parse
@@ -173,8 +177,9 @@ class AlphaZeroTrainer:
             raise ValueError("the batched engine needs config.simulations (compute_time-bounded search is host-only)")
         slots = max(1, min(self.engine_slots, c.episodes))
         sym = self._check_selfplay_symmetry()
-        from .gumbel import check_gumbel, check_gumbel_batch
+        from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full
         gb = check_gumbel_batch(self.selfplay_gumbel_batch, self.selfplay_gumbel)
+        gf = check_gumbel_full(self.selfplay_gumbel_full, self.selfplay_gumbel)
         if sym is not None:
             from .mcts import check_symmetry
             from .symmetry import members, parse
@@ -209,12 +214,18 @@ class AlphaZeroTrainer:
         elif sym is not None or self._engine._sym_mode is not None:
             self._engine.set_symmetry(sym)
         gum = check_gumbel(self.selfplay_gumbel, self.nn)  # ValueError for a network routed to the external evaluator
+        if getattr(self._engine, "_gumbel_full", False) and not gf:
+            self._engine.set_gumbel_full(False)
+            self._engine._gumbel_full = False
         if gum != getattr(self._engine, "_gumbel_spec", None):
             self._engine.set_gumbel(self.selfplay_gumbel)
             self._engine._gumbel_spec = gum
         if gb != getattr(self._engine, "_gumbel_batch", 1):
             self._engine.set_gumbel_batch(gb)
             self._engine._gumbel_batch = gb
+        if gf != getattr(self._engine, "_gumbel_full", False):  # every game of the last wave is over: no active slot holds a tree
+            self._engine.set_gumbel_full(gf)
+            self._engine._gumbel_full = gf
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

@@ -302,7 +302,7 @@ int az_engine_collisions(az_engine *e, int64_t *n);
  *              every search call on that root, never a function of slot, row or batch shape
  *   vmix     = (sum over N(b) > 0 of P(b) Q(b)) / (sum over N(b) > 0 of P(b)), both in child-index order; 0.0 when no child is
  *              visited (or the divisor is 0).  The root's own network value is discarded, as the reference discards it: this is
- *              the visited-children term of the paper's v_mix alone
+ *              the visited-children term of the paper's v_mix alone (az_engine_set_gumbel_full below keeps the value and mixes it in)
  *   cq(a)    = N(a) > 0 ? Q(a) : vmix               (Q is in the root mover's frame)
  *   maxN     = max N(b), the real counts, visits kept by a re-rooting included
  *   sigma(a) = ((c_visit + (double)maxN) * c_scale) * cq(a)
@@ -354,6 +354,37 @@ int az_engine_gumbel_considered(az_engine *e, int32_t slot, uint64_t *mask);
  * search graphs. */
 int az_engine_set_gumbel_batch(az_engine *e, int32_t k);
 int az_gumbel_locksteps(int32_t n_sim, int32_t m, int32_t k);
+
+/* Full Gumbel search: the paper's v_mix with the node's own network value, and its deterministic selection below the root.  A switch
+ * on top of the Gumbel mode: opt-in, default 0; accepted with the mode on or off and in force only while m > 0 (as gumbel_batch);
+ * with it off nothing is allocated, no kernel touches the values and every launch and every bit are unchanged.  It works at
+ * gumbel_batch 1 and above and with both symmetry modes the Gumbel mode combines with.  Everything not named here is the contract of
+ * az_engine_set_gumbel and az_engine_set_gumbel_batch.  While it is in force:
+ *   1. Every evaluated node keeps vhat = the raw float32 value row of the network call that evaluated it, in the frame of the player
+ *      to move at the node (a fresh root's value is still not backed up, but it is kept).  A re-rooting copies the values with the
+ *      nodes; az_engine_grow_pools moves them with the pools.
+ *   2. For a node p with children b, in float64, one operation at a time, sums in child-index order:
+ *        sumN = sum of N(b) (the real counts);  num, den = the sums over N(b) > 0 of P(b) Q(b) and of P(b)
+ *        vmix(p) = vhat(p) when sumN == 0 or not den > 0; else (vhat(p) + (double)sumN * (num / den)) / (double)(1 + sumN)
+ *      and this vmix replaces az_engine_set_gumbel's wherever that is used: the scores of Sequential Halving, the move, the policy
+ *      target (samples' pi, d_pi of the readout; layouts unchanged).
+ *   3. Below the root (depth >= 1) walker j at parent p takes, instead of the PUCT child, the maximum of
+ *        key(b) = pi'(b) - (double)(N(b) + v(b)) / (double)(1 + sumN + vsum)
+ *      with v(b) = the virtual count of az_engine_set_leaf_batch (the walkers i < j of this lock-step whose recorded path holds b;
+ *      all 0 at gumbel_batch 1), vsum their sum over p's children, and pi' the policy target's formula at p:
+ *        maxN = max N(b);  k = (c_visit + (double)maxN) * c_scale;  cq(b) = N(b) > 0 ? Q(b) : vmix(p)
+ *        x(b) = L(P(b)) + k * cq(b);  e(b) = E(x(b) - max x);  pi'(b) = e(b) / sum e      (L = az_det_log, E = az_det_exp)
+ *      Only real counts enter vmix, maxN and pi'.  Ties go to the lowest child index whatever the tie mode: no Philox draw is made
+ *      below the root.  A NaN key is reported like a NaN PUCT score.  Break tests, first-visit expansion, leaf status, collisions,
+ *      backup and allocation order are unchanged; the root step stays the scheduled pick.
+ * A value that was never stored is never read: the call that brings the switch into force (this setter with on = 1 while m > 0, or
+ * az_engine_set_gumbel(m > 0) with the switch on) returns AZ_ESTATE while an active slot's root is already evaluated -- start the
+ * trees afresh first (az_engine_set_roots, az_engine_run; Python: set_roots, reset).  AZ_EINVAL: on outside {0, 1}; AZ_ESTATE while
+ * a search is open.  A change of the value drops the cached search graphs.
+ * az_engine_root_value reads vhat of a slot's root (inspection, as az_engine_gumbel_considered); AZ_ESTATE when the switch is not
+ * in force, the slot holds no game or its root is not evaluated. */
+int az_engine_set_gumbel_full(az_engine *e, int32_t on);
+int az_engine_root_value(az_engine *e, int32_t slot, float *v);
 
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
