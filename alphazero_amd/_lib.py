@@ -64,7 +64,7 @@ SYMBOLS = [
     "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
     "az_engine_get_stats", "az_engine_samples", "az_engine_set_roots", "az_engine_search", "az_engine_search_begin", "az_engine_search_end", "az_engine_pair", "az_engine_advance",
     "az_engine_root_children", "az_engine_root_readout", "az_engine_nodes_used", "az_engine_grow_pools", "az_engine_play", "az_augment_count", "az_augment",
-    "az_engine_set_sides", "az_engine_best_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator", "az_engine_set_symmetry", "az_engine_set_symmetry_random", "az_engine_set_leaf_batch", "az_engine_collisions",
+    "az_engine_set_sides", "az_engine_best_moves", "az_engine_player_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator", "az_engine_set_symmetry", "az_engine_set_symmetry_random", "az_engine_set_leaf_batch", "az_engine_collisions",
     "az_engine_set_gumbel", "az_engine_gumbel_considered", "az_engine_set_gumbel_batch", "az_gumbel_locksteps",
     "az_engine_set_gumbel_full", "az_engine_root_value",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
@@ -120,6 +120,7 @@ def lib():
     L.az_engine_play.argtypes = [vp, vp, i32, vp]
     L.az_engine_set_sides.argtypes = [vp, vp, i32]
     L.az_engine_best_moves.argtypes = [vp, vp]
+    L.az_engine_player_moves.argtypes = [vp, C.c_double, vp]
     L.az_engine_baseline_moves.argtypes = [vp, i32, C.c_uint32, vp]
     L.az_engine_root_status.argtypes = [vp, vp, vp, vp, vp]
     L.az_engine_set_evaluator.argtypes = [vp, EVAL_FN, vp]

@@ -66,6 +66,49 @@ class Arena:
         print(f"{player1} wins: {n1} | {player2} wins: {n2} | draws: {d}")
 
 
+SEARCH_KEYS = ("symmetry", "leaf_batch", "gumbel", "gumbel_batch", "gumbel_full")
+
+
+def check_search(search, player, what="search"):
+    """the search modes of one tree player of BatchedArena: None, or a dict with any of SEARCH_KEYS, which take the values of
+    BatchedAlphaZeroPlayer's keywords and its checks (mcts.check_symmetry / check_leaf_batch, gumbel.check_gumbel / _batch / _full).
+    Returns None or the dict with every key filled in; ValueError -- before any device work -- for anything else, for a `player` that
+    has no tree ("random", "greedy") and for a mode the player's kind cannot run (rollout "mcts", a network routed to the external
+    evaluator).  `player` None: a network not known yet -- the checks that need none."""
+    from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full
+    from .mcts import check_leaf_batch, check_symmetry
+    if search is None:
+        return None
+    if not isinstance(search, dict):
+        raise ValueError(f"{what}: expected None or a dict with any of {list(SEARCH_KEYS)}, got {search!r}")
+    unknown = sorted(set(search) - set(SEARCH_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"{what}: unknown keys {unknown}; expected {list(SEARCH_KEYS)}")
+    if player in ("random", "greedy"):
+        raise ValueError(f"{what}: player '{player}' has no search tree to take search modes")
+    spec = {"symmetry": None, "leaf_batch": None, "gumbel": None, "gumbel_batch": 1, "gumbel_full": False}
+    spec.update(search)
+    neural = player != "mcts"  # "fake", the closed-form test network, is searched as a network is
+    nn = None if isinstance(player, str) else player
+    if check_symmetry(spec["symmetry"], nn) != 0 and isinstance(player, str):
+        raise ValueError(f"{what}: symmetry={spec['symmetry']!r} needs a network the HIP network serves; player '{player}' has none")
+    check_leaf_batch(spec["leaf_batch"], nn, spec["symmetry"], neural)
+    check_gumbel(spec["gumbel"], nn, spec["leaf_batch"], neural)
+    check_gumbel_batch(spec["gumbel_batch"], spec["gumbel"], spec["symmetry"])
+    check_gumbel_full(spec["gumbel_full"], spec["gumbel"])
+    return spec
+
+
+def check_opening_plies(opening_plies):
+    """None, or the int >= 0 of BatchedArena's `opening_plies`; ValueError for anything else"""
+    if opening_plies is None:
+        return None
+    import numpy as np
+    if isinstance(opening_plies, (bool, np.bool_)) or not isinstance(opening_plies, (int, np.integer)) or int(opening_plies) < 0:
+        raise ValueError(f"opening_plies must be None or an integer >= 0, got {opening_plies!r}")
+    return int(opening_plies)
+
+
 class BatchedArena:
     """Arena.play_games (arena.py:119-185) with all rounds played at once on the GPU.
 
@@ -73,20 +116,47 @@ class BatchedArena:
     AlphaZeroTrainer.evaluate builds, trainer.py:421-425) or "mcts" (MCTSPlayer: UCT + random playouts on the device);
     `opponent` is "random", "greedy", "mcts" or another network (evaluation against a previous network).
     Returns the reference's stats dict.
+
+    `search` / `opponent_search` (check_search: symmetry, leaf_batch, gumbel, gumbel_batch, gumbel_full, as BatchedAlphaZeroPlayer takes
+    them) put player 1's / the opponent's tree search in those modes; a tree player then plays the move of its mode
+    (SelfPlayEngine.player_moves: the Gumbel move in the Gumbel mode).  `opening_plies` = k seeds the first k plies (passes count) of
+    every round: a visit-based tree player samples its move from the visit counts (temperature 1, the AZ_P_MOVE_SAMPLE draw of seed,
+    game id and ply) while the root's ply is < k and plays the most visited one from ply k on; a Gumbel player searches and moves with
+    its spec's gumbel_scale (1.0 where the spec says 0) while the ply is < k and with gumbel_scale 0 from ply k on.  None: nothing is
+    switched -- temperature 0 and the spec's scale throughout.  With all three None the arena is the visit-based one, call for call.
+    A round is a function of (seed, round, the two specs, opening_plies) alone.
     """
 
     def __init__(self, game, nn, opponent="random", n_sim=100, opponent_n_sim=None, seed=0, board_size=None,
-                 board_width=7, board_height=6):
+                 board_width=7, board_height=6, search=None, opponent_search=None, opening_plies=None):
         from .engine import game_shape
+        self.search = check_search(search, nn, "search")
+        self.opponent_search = check_search(opponent_search, opponent, "opponent_search")
+        self.opening_plies = check_opening_plies(opening_plies)
+        # the move of a tree player: best_moves() as ever, player_moves(temp) as soon as one of the three keywords is given
+        self._modes = search is not None or opponent_search is not None or opening_plies is not None
         self.game = game
         self.gid, self.H, self.W, self.A = game_shape(game, board_size if board_size is not None else getattr(nn, "n", None),
                                                       board_width, board_height)
         self.nn, self.opponent, self.n_sim, self.seed = nn, opponent, n_sim, seed
+        for spec in (self.search, self.opponent_search):  # a symmetry code this board does not have
+            if spec is not None:
+                from .symmetry import members, parse
+                members(game, self.H, self.W, parse(spec["symmetry"])[0])
         self.opponent_n_sim = opponent_n_sim if opponent_n_sim is not None else n_sim
         self.overlap = True  # two tree players search at the same time (each on its own stream); False: one after the other
         self.tie_mode = None  # None: fair_max draws among equals (utils.py:28-34); tests pin it to engine.TIE_LOWEST (golden G7)
 
-    def _engine(self, net, G, n_sim, seed):
+    def _gumbel_spec(self, spec, opening):
+        """the set_gumbel dict of a Gumbel player: the spec's own when opening_plies is None; else its gumbel_scale (1.0 for 0) while
+        the opening lasts (`opening` True) and 0 after it"""
+        from .gumbel import parse
+        m, cv, cs, gs = parse(spec["gumbel"])
+        if self.opening_plies is not None:
+            gs = (gs if gs != 0.0 else 1.0) if opening else 0.0
+        return {"m": m, "c_visit": cv, "c_scale": cs, "gumbel_scale": gs}
+
+    def _engine(self, net, G, n_sim, seed, spec=None):
         from .engine import EVAL_EXTERNAL, EVAL_NET, EVAL_ROLLOUT, NOISE_OFF, TIE_RANDOM, SelfPlayEngine
         from .evaluators import check_normalizer, make_evaluator, route
         plies = 4 * self.H * self.W + 16
@@ -98,13 +168,32 @@ class BatchedArena:
         external = not isinstance(net, str) and route(net) != "hip"
         if external:
             check_normalizer(net)
-        hipnet = None if isinstance(net, str) or external else net.to_hip(max_batch=G)
+        sym, rnd, lb, gb = [], False, 1, 1
+        if spec is not None:
+            from .symmetry import members, parse
+            mask, rnd = parse(spec["symmetry"])
+            sym = members(self.game, self.H, self.W, mask)
+            lb = 1 if spec["leaf_batch"] is None else int(spec["leaf_batch"])
+            gb = int(spec["gumbel_batch"])
+        # the rows of a lock-step: every slot's leaf in each twin of an ensemble, or every slot's leaf_batch / gumbel_batch walkers
+        rows = G * max(1, 1 if rnd else len(sym), lb, gb)
+        hipnet = None if isinstance(net, str) or external else net.to_hip(max_batch=rows)
         kind = EVAL_ROLLOUT if rollout else (EVAL_FAKE if fake else (EVAL_EXTERNAL if external else EVAL_NET))
         eng = SelfPlayEngine(self.gid, self.H, self.W, n_slots=G, n_sim=n_sim, net=hipnet,
                              evaluator=kind, dirichlet_alpha=None, dirichlet_epsilon=None, temp_max_step=-1, temp_min_step=0,
                              tie_mode=TIE_RANDOM if self.tie_mode is None else self.tie_mode, noise_mode=NOISE_OFF, seed=seed, max_plies=plies, sample_capacity=16)
         if external:
             eng.set_evaluator(make_evaluator(net, self.game, self.H, self.W))
+        if sym:
+            eng.set_symmetry(("random", sym) if rnd else sym)
+        if lb > 1:
+            eng.set_leaf_batch(lb)
+        if spec is not None and spec["gumbel"] is not None:
+            eng.set_gumbel(self._gumbel_spec(spec, (self.opening_plies or 0) > 0))
+            if gb > 1:
+                eng.set_gumbel_batch(gb)
+            if spec["gumbel_full"]:
+                eng.set_gumbel_full(True)
         return eng
 
     def play_games(self, n_rounds, start_player=None, return_stats=True, shard=True, record_moves=False):
@@ -154,20 +243,26 @@ class BatchedArena:
         ones = np.ones(G, np.int8)
         # game id = (round + seed * 100003) mod 2^32: any seed is fine (np.uint32(big) raises, and uint32 + uint32 warns on wrap-around)
         ids = ((round_ids.astype(np.uint64) + np.uint64((self.seed * 100003) & 0xFFFFFFFF)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-        e1 = self._engine(self.nn, G, self.n_sim, self.seed)
+        e1 = self._engine(self.nn, G, self.n_sim, self.seed, self.search)
         e1.set_roots(grids, ones, game_ids=ids)
         e1.set_sides(side1)
         e2 = None
         if self.opponent in ("mcts", "fake") or not isinstance(self.opponent, str):
-            e2 = self._engine(self.opponent, G, self.opponent_n_sim, self.seed + 1)
+            e2 = self._engine(self.opponent, G, self.opponent_n_sim, self.seed + 1, self.opponent_search)
             e2.set_roots(grids, ones, game_ids=ids)
             e2.set_sides(-side1)
             if self.overlap:
                 e1.pair_with(e2)
-        for _ in range(4 * self.H * self.W + 8):
+        k = self.opening_plies
+        gumbel = [(e, sp) for e, sp in ((e1, self.search), (e2, self.opponent_search)) if e is not None and sp is not None and sp["gumbel"] is not None]
+        for ply in range(4 * self.H * self.W + 8):  # every live round gets one move (a pass is one) per turn: the roots' ply
             _, over, winner, score = e1.root_status()
             if over.all():
                 break
+            if k is not None and k > 0 and ply == k:  # the opening ends: between two plies, so the search and the move of a ply see one scale
+                for e, sp in gumbel:
+                    e.set_gumbel(self._gumbel_spec(sp, False))
+            temp = 1.0 if k is not None and ply < k else 0.0
             if e2 is not None and self.overlap:  # both players think at once: each engine searches the slots where its colour is to move, on its own stream
                 e1.search_begin(self.n_sim)
                 try:
@@ -175,13 +270,13 @@ class BatchedArena:
                     e2.search_end()
                 finally:
                     e1.search_end()
-                a, b = e1.best_moves(), e2.best_moves()
+                a, b = (e1.player_moves(temp), e2.player_moves(temp)) if self._modes else (e1.best_moves(), e2.best_moves())
             else:
                 e1.search(self.n_sim)
-                a = e1.best_moves()
+                a = e1.player_moves(temp) if self._modes else e1.best_moves()
                 if e2 is not None:
                     e2.search(self.opponent_n_sim)
-                    b = e2.best_moves()
+                    b = e2.player_moves(temp) if self._modes else e2.best_moves()
                 else:
                     b = e1.baseline_moves(self.opponent, seed=self.seed + 7)
             moves = np.where(a >= 0, a, b).astype(np.int32)

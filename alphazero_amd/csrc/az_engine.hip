@@ -1717,6 +1717,20 @@ __global__ void k_best_moves(EngDev E, int *actions) {
     actions[g] = pool[fc + pick].act;
 }
 
+// The move every slot's player plays now at temperature `temp` (az_engine_player_moves): move_policy's child for the slots k_root_readout
+// serves (searched now, root expanded with children), -1 elsewhere.  In the Gumbel mode that is the Gumbel move over the slot's
+// candidates; with the mode off and temp 0 it is k_best_moves' pick, draw for draw.  Reads only.  One thread per slot.
+__global__ void k_player_moves(EngDev E, double temp, int *actions) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G) return;
+    actions[g] = -1;
+    if (!searches(E, g)) return;
+    const Node *pool = pool_of(E, g);
+    const int root = E.root[g], fc = pool[root].first, nc = pool[root].nch;
+    if (nc == 0 || !(pool[root].flags & F_EXPANDED)) return;
+    actions[g] = pool[fc + move_policy(E, pool, root, fc, nc, temp, E.game_id[g], E.ply[g], E.gmask[g], nullptr)].act;
+}
+
 // Root readout for slots [0, n) in one launch: everything Player.get_move returns (players.py:158-191: the move, get_action_probs,
 // the visit counts, get_prior_probs of mcts.py:95-116) plus Q and the principal line, as dense rows indexed by action.  Reads only:
 // trees, boards, counters, sample buffers and the Philox state (a pure function of seed, game id and ply) stay as they are.
@@ -2737,6 +2751,22 @@ extern "C" int az_engine_best_moves(az_engine *e, int32_t *h_actions) {
     AZ_NO_OPEN_SEARCH(e, "az_engine_best_moves");
     AZ_USABLE(e, "az_engine_best_moves");
     return moves_out(e, h_actions, 0, 0, 0);
+}
+
+// what az_engine_advance would play now at temperature `temp`, per slot, as host ints: d_action of az_engine_root_readout with every
+// temperature `temp`, without its device rows (the arena's loop works on host int vectors)
+extern "C" int az_engine_player_moves(az_engine *e, double temp, int32_t *h_actions) {
+    AZ_REQUIRE(e && h_actions, AZ_EINVAL, "null argument");
+    AZ_REQUIRE(temp >= 0.0 && temp <= 1.7976931348623157e308, AZ_EINVAL, "az_engine_player_moves: the temperature is negative or not finite (%g)", temp);
+    AZ_NO_OPEN_SEARCH(e, "az_engine_player_moves");
+    AZ_USABLE(e, "az_engine_player_moves");
+    EngDev &d = e->d;
+    int *d_act = e->scr_a;
+    hipLaunchKernelGGL(k_player_moves, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, temp, d_act);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipMemcpyAsync(h_actions, d_act, sizeof(int) * d.G, hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    return AZ_OK;
 }
 
 extern "C" int az_engine_baseline_moves(az_engine *e, int32_t kind, uint32_t seed, int32_t *h_actions) {

@@ -465,6 +465,14 @@ class SelfPlayEngine:
         check(lib().az_engine_best_moves(self.h, a.ctypes.data))
         return a
 
+    def player_moves(self, temp=0.0):
+        """the move every slot's player plays now (az_engine_player_moves): root_readout(temps=temp)["action"] as a host int32 vector,
+        what advance() would play at that temperature -- the Gumbel move in the Gumbel mode, whatever `temp` is; best_moves() stays
+        visit-based in every mode.  -1 for a slot this engine does not search now or whose root is not expanded.  Reads only."""
+        a = np.zeros(self.cfg.n_slots, np.int32)
+        check(lib().az_engine_player_moves(self.h, float(temp), a.ctypes.data))
+        return a
+
     def baseline_moves(self, kind, seed=0):
         a = np.zeros(self.cfg.n_slots, np.int32)
         check(lib().az_engine_baseline_moves(self.h, {"random": 0, "greedy": 1}[kind], seed, a.ctypes.data))

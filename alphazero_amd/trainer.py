@@ -62,7 +62,7 @@ class AlphaZeroTrainer:
     DEFAULT_EXP_NAME = "alphazero-undefined"
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
-                 selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False):
+                 selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, eval_search=None, eval_opening_plies=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -100,6 +100,24 @@ class AlphaZeroTrainer:
         self.selfplay_gumbel_full = selfplay_gumbel_full
         from .gumbel import check_gumbel_full
         check_gumbel_full(selfplay_gumbel_full, selfplay_gumbel)
+        # the search the evaluation arena plays with (BatchedArena's `search`): None (the visit-based PUCT arena), "selfplay" (the modes
+        # of the self-play wave above) or a dict of arena.SEARCH_KEYS; it goes to player 1 and, with eval_opponent "previous", to the
+        # opponent too.  eval_opening_plies: BatchedArena's `opening_plies`, the seeded opening that makes the rounds different games.
+        self.eval_search, self.eval_opening_plies = eval_search, eval_opening_plies
+        self._eval_search_spec()
+
+    def _eval_search_spec(self, nn=None):
+        """BatchedArena's `search` dict for the evaluation (None: today's arena), checked -- against `nn` too when it is given"""
+        from .arena import check_opening_plies, check_search
+        check_opening_plies(self.eval_opening_plies)
+        spec = self.eval_search
+        if isinstance(spec, str):
+            if spec != "selfplay":
+                raise ValueError(f"eval_search={spec!r}: expected None, 'selfplay' or a dict of search modes")
+            spec = {"symmetry": self.selfplay_symmetry, "gumbel": self.selfplay_gumbel, "gumbel_batch": self.selfplay_gumbel_batch,
+                    "gumbel_full": self.selfplay_gumbel_full}
+        check_search(spec, nn, "eval_search")
+        return spec
 
     def _check_selfplay_symmetry(self):
         from .symmetry import parse
@@ -461,6 +479,11 @@ class AlphaZeroTrainer:
 
     # ------------------------------------------------------------------ evaluation (trainer.py:389-446)
     def _init_evaluator(self):
+        if self.eval_search is not None or self.eval_opening_plies is not None:
+            if self.config.simulations is None:
+                raise ValueError("eval_search / eval_opening_plies need config.simulations: the search modes run in the batched arena, "
+                                 "a compute_time-bounded evaluation plays through the host Arena")
+            self._eval_search_spec(self.nn)
         if not self.config.do_eval:
             return
         opp = self.config.eval_opponent
@@ -499,7 +522,9 @@ class AlphaZeroTrainer:
                 p2_name = f"{PLAYERS_REGISTER[c.eval_opponent](**({'n_sim': c.simulations} if c.eval_opponent == 'mcts' else {}))}"
             arena = BatchedArena(self.game, self.nn, opponent=opp_arg, n_sim=c.simulations, seed=self.seed + iter_idx,
                                  board_size=getattr(c, "board_size", None), board_width=getattr(c, "board_width", 7),
-                                 board_height=getattr(c, "board_height", 6))
+                                 board_height=getattr(c, "board_height", 6), search=self._eval_search_spec(self.nn),
+                                 opponent_search=self._eval_search_spec(self.nn) if c.eval_opponent == "previous" else None,
+                                 opening_plies=self.eval_opening_plies)
             stats = arena.play_games(n_rounds=c.eval_episodes, return_stats=True)
             p1_name = f"{type(self.az_player).__name__}"
         else:

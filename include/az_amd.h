@@ -230,7 +230,18 @@ int az_engine_grow_pools(az_engine *e, int32_t node_capacity);
  * (-1 = none) to the boards and trees; az_engine_root_status reads every slot's position back (h_score = Board.get_score of
  * the side to move: sum(player*grid) for Othello / Connect4; TicTacToe 32767 for the reference's +inf, tictactoe.py:119-126, else 0). */
 int az_engine_set_sides(az_engine *e, const int8_t *h_sides, int32_t n);
+/* az_engine_best_moves is visit-based in every search mode: on an engine in the Gumbel mode it is NOT the move az_engine_advance
+ * plays.  The move a player plays now is az_engine_player_moves. */
 int az_engine_best_moves(az_engine *e, int32_t *h_actions);
+/* The move every slot's player plays now, one launch, one thread per slot.  h_actions: HOST int32 [n_slots].  h_actions[g] equals
+ * d_action[g] of az_engine_root_readout called with every temperature equal to `temp`: it is what az_engine_advance would play at
+ * that temperature.  -1 unless the engine searches the slot now (active and, with sides set, its colour to move) and the root is
+ * expanded with at least one child.  In the Gumbel mode (az_engine_set_gumbel) it is the Gumbel move over the slot's current
+ * candidate set, whatever `temp` is.  With the mode off and temp == 0 it equals az_engine_best_moves element for element, with the
+ * same AZ_P_TIE_MOVE draw; with temp > 0 the move is sampled on the AZ_P_MOVE_SAMPLE draw of (seed, game id, ply).  Reads only:
+ * trees, boards, counters, samples and streams stay as they are.  AZ_EINVAL: a null argument, a `temp` that is negative or not
+ * finite; AZ_ESTATE while a search is open. */
+int az_engine_player_moves(az_engine *e, double temp, int32_t *h_actions);
 int az_engine_baseline_moves(az_engine *e, int32_t kind, uint32_t seed, int32_t *h_actions);
 /* az_engine_search in two halves, so that the arena's two players (arena.py:135-140: player1.get_move / player2.get_move, each on
  * the games where it is to move) think at the same time: _begin queues the search on the engine's own stream and returns, _end
@@ -318,7 +329,7 @@ int az_engine_collisions(az_engine *e, int64_t *n);
  * statistics, lowest index among equals; an empty set (after this setter, after a move) means all children.  Policy target:
  * pi'(a) = E(x(a) - max x) / sum with E = az_det_exp, x(a) = logit(a) + sigma(a) (no g), the sum in child-index order, stored as float32 where
  * the visit-count policy is stored (the samples' pi, d_pi of the readout); the visits stay the visit counts.  A NaN score is
- * reported like a NaN PUCT score.  az_engine_best_moves stays visit-based.
+ * reported like a NaN PUCT score.  az_engine_best_moves stays visit-based; az_engine_player_moves reads this move.
  * AZ_EINVAL: m outside [0, AZ_MAX_GUMBEL]; with m > 0 a constant that is negative or not finite, an AZ_EVAL_ROLLOUT or
  * AZ_EVAL_EXTERNAL engine, leaf_batch > 1 in force (az_engine_set_leaf_batch(k > 1) in turn refuses while this mode is on);
  * AZ_ESTATE while a search is open.  The cached search graphs are dropped and the slots' candidate sets cleared; the symmetry
