@@ -89,7 +89,8 @@ struct EngDev {
     float *nn_in, *probs, *value;
     int *row_of_slot;  // network batch row holding the slot's pending leaf (leaves are compacted)
     int *evals;        // per-slot network evaluations since the last move (folded into ctr[] once per ply)
-    int *batch_cnt;    // [3] rows filled: two alternating lock-step counters + the root-prior pass
+    int *batch_cnt;    // [3] rows filled: two alternating lock-step counters + the root-prior pass (a slot group's own three)
+    int *live;         // slots still holding a game after the ply's move (counted by k_reroot; a slot group's own word)
     int *samp_idx;
     int8_t *o_state; float *o_pi; int8_t *o_z; int *o_meta, *o_visits;
     unsigned long long *ctr;
@@ -535,7 +536,7 @@ __global__ void k_reset_all(EngDev E, u32 first_id, int n_games) {
         E.ctr[CTR_TOTAL_GAMES] = (unsigned long long)n_games;
         E.ctr[CTR_FIRST_ID] = first_id;
         *E.err = 0; *E.max_nodes = 0; *E.max_path = 0;
-        E.batch_cnt[0] = E.batch_cnt[1] = E.batch_cnt[2] = 0;
+        for (int i = 0; i < 4 * AZ_MAX_GROUPS; ++i) E.batch_cnt[i] = 0;  // every slot group's counters (E is the whole engine's view)
     }
     if (g >= E.G) return;
     E.pool_sel[g] = 0;
@@ -591,7 +592,8 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
     // previous step's network kernels, which have completed) is cleared for the next step
-    if (blockIdx.x == 0 && threadIdx.x == 0 && g0 == 0) { E.batch_cnt[(sim + 1) & 1] = 0; if (!SELECT) E.batch_cnt[2] = 0; }
+    // (a slot range is a slot group with counters of its own: its first block clears them)
+    if (blockIdx.x == 0 && threadIdx.x == 0) { E.batch_cnt[(sim + 1) & 1] = 0; if (!SELECT) E.batch_cnt[2] = 0; }
 #ifdef AZ_PROBE
     unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -1537,10 +1539,10 @@ AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc
 
 // get_action_probs (mcts.py:95-116) + move choice (players.py:184-189) + Sample (trainer.py:244-250)
 // + play_move / change_root (trainer.py:253-256) + end-of-game bookkeeping (trainer.py:262-268).
-// Once per ply: one thread per slot.
-__global__ void k_move(EngDev E) {
-    int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= E.G || !E.active[g]) return;
+// Once per ply: one thread per slot of [g0, g1).
+__global__ void k_move(EngDev E, int g0, int g1) {
+    int g = g0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= g1 || !E.active[g]) return;
     const GameDesc &gd = E.gd;
     Node *pool = pool_of(E, g);
     int ply = E.ply[g], root = E.root[g];
@@ -1598,9 +1600,9 @@ __global__ void k_move(EngDev E) {
 // to a freshly bump-allocated block and `first` is rewritten.  16 lanes take 16 queue nodes per round.
 // FULL (az_engine_set_gumbel_full in force): a node's network value travels with the node, to the same new index.
 template <bool FULL>
-__global__ __launch_bounds__(256) void k_reroot(EngDev E) {
-    const int g = blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
-    if (g >= E.G || !E.active[g]) return;
+__global__ __launch_bounds__(256) void k_reroot(EngDev E, int g0, int g1) {
+    const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
+    if (g >= g1 || !E.active[g]) return;
     const int sel = E.pool_sel[g];
     const Node *src = E.nodes + ((size_t)g * 2 + sel) * E.C;
     Node *dst = E.nodes + ((size_t)g * 2 + (sel ^ 1)) * E.C;
@@ -1651,6 +1653,7 @@ __global__ __launch_bounds__(256) void k_reroot(EngDev E) {
     }
     if (sub == 0) {
         if (overflow) { atomicOr(E.err, ERR_NODE_POOL); E.active[g] = 0; }
+        else atomicAdd(E.live, 1);
         E.root[g] = 0; E.n_nodes[g] = next; E.pool_sel[g] = (uint8_t)(sel ^ 1);
     }
 }
@@ -2006,9 +2009,9 @@ struct az_engine {
     az_net *net;
     hipStream_t stream;
     std::vector<void *> allocs;
-    unsigned long long *h_ctr;  // pinned
-    int *h_err;                 // pinned [3] : err, max_nodes, max_path
-    long long lockstep_iters;
+    unsigned long long *h_ctr;  // pinned [AZ_MAX_GROUPS][CTR_ALLOC]: a slot group reads the shared counters into its own copy ([0]: every other caller)
+    int *h_err;                 // pinned [AZ_MAX_GROUPS][4] : err, max_nodes, max_path, the group's live slots
+    long long lockstep_iters[AZ_MAX_GROUPS];  // per slot group; the stats report the largest (a ply's lock-steps count once, not once per group)
     u32 sim_base = 0;
     // The engine runs on a stream of its own (graph capture is not allowed on the legacy default stream); every entry
     // point first orders it behind the caller's stream and returns only after its own stream has drained.
@@ -2016,8 +2019,10 @@ struct az_engine {
     bool search_open = false;  // between az_engine_search_begin and _end
     hipEvent_t ev_in = nullptr;
     // One search = 1 + 5 n_sim kernel launches: captured once per (n_sim, batch cap) as a HIP graph and replayed
-    std::map<unsigned long long, hipGraphExec_t> graphs;
-    std::map<unsigned long long, int> graph_seen;
+    // (a slot group's graph: the key's second word holds its slot range, g0 << 32 | g1)
+    typedef std::pair<unsigned long long, unsigned long long> GraphKey;
+    std::map<GraphKey, hipGraphExec_t> graphs;
+    std::map<GraphKey, int> graph_seen;
     bool graphs_ok = true;
     long long graph_replays = 0;
     int *scr_a = nullptr, *scr_b = nullptr;  // [G] int scratch of the arena entry points (moves in/out, status, scores)
@@ -2047,7 +2052,24 @@ struct az_engine {
     // (d.nval == nval) only while d.gm > 0, else d.nval is null
     int gumbel_full = 0;
     float *nval = nullptr;
+    // az_engine_set_groups: the request (0: auto) and whether AZ_ENGINE_GROUPS made it; the later groups' streams (group 0 runs on
+    // `stream`), made at the first grouped run; the event that orders them behind `stream`
+    int groups_req = 0;
+    bool groups_env = false;
+    hipStream_t gstream[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_grp = nullptr;
 };
+
+// One launch chain of a search: the whole engine on its stream, or one slot group of az_engine_run -- slots [g0, g1) on the group's
+// stream, with d = the engine's device view whose network rows, row counters and live word are the group's own.
+struct Chain {
+    EngDev d;
+    int g0, g1, idx;
+    hipStream_t st;
+    bool beside;  // another chain runs next to this one (az_net_forward_lane)
+    int live;     // a slot group: the slots that hold a game (exact: counted by the group's own last ply); bounds its network batch
+};
+static Chain whole_chain(const az_engine *e) { return Chain{e->d, 0, e->d.G, 0, e->stream, false, 0}; }
 
 int az_make_game_desc(int game, int H, int W, GameDesc *gd) {
     AZ_REQUIRE(game >= 0 && game <= 2, AZ_EINVAL, "unknown game id %d", game);
@@ -2109,7 +2131,8 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
                    az_net_action_size(net), gd.A);
     az_engine *e = new az_engine();
     e->h_ctr = nullptr; e->h_err = nullptr;
-    e->cfg = *cfg; e->net = net; e->user_stream = (hipStream_t)stream; e->stream = nullptr; e->lockstep_iters = 0;
+    e->cfg = *cfg; e->net = net; e->user_stream = (hipStream_t)stream; e->stream = nullptr;
+    for (int i = 0; i < AZ_MAX_GROUPS; ++i) e->lockstep_iters[i] = 0;
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming) != hipSuccess) {
         az_engine_destroy(e);
@@ -2133,7 +2156,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     A_(active, G); A_(root_fresh, G); A_(side, G); A_(leaf, G); A_(leaf_p1, G); A_(leaf_m1, G); A_(leaf_player, G);
     A_(leaf_status, G); A_(leaf_winner, G); A_(path, G * LPG); A_(path_len, G);
     A_(nodes, 2 * NC); A_(pool_sel, G);
-    A_(nn_in, G * gd.cells); A_(probs, G * gd.A); A_(value, G); A_(row_of_slot, G); A_(evals, G); A_(batch_cnt, 4);
+    A_(nn_in, G * gd.cells); A_(probs, G * gd.A); A_(value, G); A_(row_of_slot, G); A_(evals, G); A_(batch_cnt, 4 * AZ_MAX_GROUPS); A_(live, AZ_MAX_GROUPS);
     A_(samp_idx, G * (size_t)d.max_plies);
     A_(o_state, S * gd.cells); A_(o_pi, S * gd.A); A_(o_z, S); A_(o_meta, S * 4); A_(o_visits, S * gd.A);
     A_(ctr, CTR_ALLOC); A_(err, 1); A_(max_nodes, 1); A_(max_path, 1);
@@ -2148,29 +2171,38 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
         if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_slots, G);
         if (rc == AZ_OK) rc = dev_alloc(e, &e->ext_bad, 1);
     }
-    if (rc == AZ_OK && hipHostMalloc((void **)&e->h_ctr, sizeof(unsigned long long) * CTR_ALLOC) != hipSuccess) rc = AZ_EHIP;
-    if (rc == AZ_OK && hipHostMalloc((void **)&e->h_err, sizeof(int) * 3) != hipSuccess) rc = AZ_EHIP;
+    if (rc == AZ_OK && hipHostMalloc((void **)&e->h_ctr, sizeof(unsigned long long) * CTR_ALLOC * AZ_MAX_GROUPS) != hipSuccess) rc = AZ_EHIP;
+    if (rc == AZ_OK && hipHostMalloc((void **)&e->h_err, sizeof(int) * 4 * AZ_MAX_GROUPS) != hipSuccess) rc = AZ_EHIP;
+    if (rc == AZ_OK) {  // AZ_ENGINE_GROUPS: one build measured against itself; engines that do not serve groups ignore it (groups_in_force)
+        const char *g = getenv("AZ_ENGINE_GROUPS");
+        const int n = g ? atoi(g) : 0;
+        if (n == 1 || n == 2 || n == 4) { e->groups_req = n; e->groups_env = true; }
+    }
     if (rc != AZ_OK) { az_engine_destroy(e); return rc; }
     if (hipStreamSynchronize(e->stream) != hipSuccess) { az_engine_destroy(e); az_set_error("stream sync failed"); return AZ_EHIP; }
     *out = e;
     return AZ_OK;
 }
 
-static int fetch_counters(az_engine *e);
-static int check_err(az_engine *e);
+static int fetch_counters(az_engine *e, const Chain *grp = nullptr);
+static int check_err(az_engine *e, int idx = 0);
+static void drop_graphs(az_engine *e);
 
 // change_root for every active slot; with az_engine_set_gumbel_full in force the instantiation that moves the stored values too
-static void launch_reroot(az_engine *e) {
-    const EngDev &d = e->d;
-    const dim3 gg((unsigned)((d.G + GPB - 1) / GPB)), gb(256);
-    if (d.nval) hipLaunchKernelGGL((k_reroot<true>), gg, gb, 0, e->stream, d);
-    else hipLaunchKernelGGL((k_reroot<false>), gg, gb, 0, e->stream, d);
+static void launch_reroot(const Chain &c) {
+    const EngDev &d = c.d;
+    const dim3 gg((unsigned)((c.g1 - c.g0 + GPB - 1) / GPB)), gb(256);
+    if (d.nval) hipLaunchKernelGGL((k_reroot<true>), gg, gb, 0, c.st, d, c.g0, c.g1);
+    else hipLaunchKernelGGL((k_reroot<false>), gg, gb, 0, c.st, d, c.g0, c.g1);
 }
 
 extern "C" void az_engine_destroy(az_engine *e) {
     if (!e) return;
     if (e->in_callback) { fprintf(stderr, "az_engine_destroy: called from inside the engine's own evaluator; ignored\n"); return; }
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    for (int i = 1; i < AZ_MAX_GROUPS; ++i)
+        if (e->gstream[i]) { (void)hipStreamSynchronize(e->gstream[i]); (void)hipStreamDestroy(e->gstream[i]); }
+    if (e->ev_grp) (void)hipEventDestroy(e->ev_grp);
     if (e->search_open) {  // destroyed with a search still open: its errors would vanish with the engine -- say so
         e->search_open = false;
         if (fetch_counters(e) == AZ_OK && check_err(e) != AZ_OK)
@@ -2212,11 +2244,12 @@ static int forward_external(az_engine *e, const int *cnt, int cap, int step) {
 }
 
 // network over the compacted leaf rows [0, *cnt)
-static int forward(az_engine *e, const int *cnt, int cap, int step, int kt = 0) {
-    EngDev &d = e->d;
+// (the external evaluator and the symmetry modes run as the whole engine's chain only: their buffers are per engine)
+static int forward(az_engine *e, const Chain &c, const int *cnt, int cap, int step, int kt = 0) {
+    const EngDev &d = c.d;
     if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return forward_external(e, cnt, cap, step);
     if (e->cfg.evaluator == AZ_EVAL_FAKE) {
-        hipLaunchKernelGGL(k_fakenet, grid_for(d.G * d.K, TB), dim3(TB), 0, e->stream, d, cnt);
+        hipLaunchKernelGGL(k_fakenet, grid_for((c.g1 - c.g0) * d.K, TB), dim3(TB), 0, c.st, d, cnt);
         return AZ_OK;
     }
     if (e->symr_mask != 0) {  // one drawn member per pending row: twin -> the network on the same rows -> mapped back (copies)
@@ -2226,7 +2259,7 @@ static int forward(az_engine *e, const int *cnt, int cap, int step, int kt = 0) 
         AZ_TRY(az_net_forward_dyn(e->net, e->sym_in, cnt, cap, e->sym_p, e->sym_v, e->stream));
         return az_sym_unpick(&d.gd, e->sym_code, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
     }
-    if (e->sym_mask == 0) return az_net_forward_dyn(e->net, d.nn_in, cnt, cap, d.probs, d.value, e->stream);
+    if (e->sym_mask == 0) return az_net_forward_lane(e->net, c.idx, c.beside ? 1 : 0, d.nn_in, cnt, cap, d.probs, d.value, c.st);
     // ensemble over the board's symmetries: twins of the pending rows -> the network on sym_n * count rows -> mapped back and averaged
     AZ_TRY(az_sym_expand(&d.gd, e->sym_mask, d.nn_in, cnt, cap, e->sym_in, e->sym_cnt, e->stream));
     AZ_TRY(az_net_forward_dyn(e->net, e->sym_in, e->sym_cnt, e->sym_n * cap, e->sym_p, e->sym_v, e->stream));
@@ -2259,28 +2292,29 @@ static int gumbel_locksteps(int n, int m, int K) {
 // MCT.search for every active slot: one root-prior pass (mcts.py:231-233; empty unless a slot holds a
 // fresh root), then n_sim lock-steps of [backup+select -> network].
 // the raw launch sequence of one search; `cap` bounds the network batch (leaf rows are compact: count <= searching slots)
-static int enqueue_search(az_engine *e, int n_sim, int cap) {
-    EngDev &d = e->d;
-    dim3 gg((unsigned)((d.G + GPB - 1) / GPB)), gb(256);
+static int enqueue_search(az_engine *e, const Chain &c, int n_sim, int cap) {
+    const EngDev &d = c.d;
+    // (the kernels without a slot range -- rollout, K walkers -- run as the whole engine's chain only: g0 = 0, g1 = G)
+    dim3 gg((unsigned)((c.g1 - c.g0 + GPB - 1) / GPB)), gb(256);
     if (d.rollout) {  // no network: one launch per simulation
-        for (int s = 0; s < n_sim; ++s) hipLaunchKernelGGL(k_rollout_step, gg, gb, 0, e->stream, d, s);
+        for (int s = 0; s < n_sim; ++s) hipLaunchKernelGGL(k_rollout_step, gg, gb, 0, c.st, d, s);
         AZ_HIP(hipGetLastError());
         return AZ_OK;
     }
-    hipLaunchKernelGGL(k_root_prep, gg, gb, 0, e->stream, d, 0, d.G);
-    AZ_TRY(forward(e, d.batch_cnt + 2, cap, -1));
-    hipLaunchKernelGGL(k_root_init, gg, gb, 0, e->stream, d, 0, d.G);
+    hipLaunchKernelGGL(k_root_prep, gg, gb, 0, c.st, d, c.g0, c.g1);
+    AZ_TRY(forward(e, c, d.batch_cnt + 2, cap, -1));
+    hipLaunchKernelGGL(k_root_init, gg, gb, 0, c.st, d, c.g0, c.g1);
     // az_engine_set_gumbel_full in force: the other instantiation of the two Gumbel kernels (no run-time branch inside the walk)
     const bool full = d.nval != nullptr;
 #define GUMBEL_LAUNCH(kern, B, S, ...) do { \
-        if (full) hipLaunchKernelGGL((kern<B, S, true>), gg, gb, 0, e->stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kern<B, S, false>), gg, gb, 0, e->stream, __VA_ARGS__); } while (0)
+        if (full) hipLaunchKernelGGL((kern<B, S, true>), gg, gb, 0, c.st, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kern<B, S, false>), gg, gb, 0, c.st, __VA_ARGS__); } while (0)
     if (d.gm > 0 && d.K > 1) {  // Sequential Halving with K walkers: Lmax lock-steps, cut per slot by its own cursor, then the last backup
         const int L = gumbel_locksteps(n_sim, d.gm, d.K);
         for (int t = 0; t < L; ++t) {
             if (t == 0) GUMBEL_LAUNCH(k_step_gumbel_multi, false, true, d, t, n_sim);
             else GUMBEL_LAUNCH(k_step_gumbel_multi, true, true, d, t, n_sim);
-            AZ_TRY(forward(e, d.batch_cnt + (t & 1), cap, t, d.K));
+            AZ_TRY(forward(e, c, d.batch_cnt + (t & 1), cap, t, d.K));
         }
         GUMBEL_LAUNCH(k_step_gumbel_multi, true, false, d, L, n_sim);
         AZ_HIP(hipGetLastError());
@@ -2290,44 +2324,51 @@ static int enqueue_search(az_engine *e, int n_sim, int cap) {
         const int K = d.K, L = (n_sim + K - 1) / K;
         for (int t = 0; t < L; ++t) {
             const int kt = n_sim - t * K < K ? n_sim - t * K : K;
-            if (t == 0) hipLaunchKernelGGL((k_step_multi<false, true>), gg, gb, 0, e->stream, d, t, 0, kt);
-            else hipLaunchKernelGGL((k_step_multi<true, true>), gg, gb, 0, e->stream, d, t, K, kt);
-            AZ_TRY(forward(e, d.batch_cnt + (t & 1), cap, t, kt));
+            if (t == 0) hipLaunchKernelGGL((k_step_multi<false, true>), gg, gb, 0, c.st, d, t, 0, kt);
+            else hipLaunchKernelGGL((k_step_multi<true, true>), gg, gb, 0, c.st, d, t, K, kt);
+            AZ_TRY(forward(e, c, d.batch_cnt + (t & 1), cap, t, kt));
         }
-        hipLaunchKernelGGL((k_step_multi<true, false>), gg, gb, 0, e->stream, d, L, n_sim - (L - 1) * K, 0);
+        hipLaunchKernelGGL((k_step_multi<true, false>), gg, gb, 0, c.st, d, L, n_sim - (L - 1) * K, 0);
         AZ_HIP(hipGetLastError());
         return AZ_OK;
     }
     if (d.gm > 0) {  // the Gumbel root search: k_step's launch sequence with k_step_gumbel
         for (int s = 0; s < n_sim; ++s) {
-            if (s == 0) GUMBEL_LAUNCH(k_step_gumbel, false, true, d, s, n_sim, 0, d.G);
-            else GUMBEL_LAUNCH(k_step_gumbel, true, true, d, s, n_sim, 0, d.G);
-            AZ_TRY(forward(e, d.batch_cnt + (s & 1), cap, s));
+            if (s == 0) GUMBEL_LAUNCH(k_step_gumbel, false, true, d, s, n_sim, c.g0, c.g1);
+            else GUMBEL_LAUNCH(k_step_gumbel, true, true, d, s, n_sim, c.g0, c.g1);
+            AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
         }
-        GUMBEL_LAUNCH(k_step_gumbel, true, false, d, n_sim, n_sim, 0, d.G);
+        GUMBEL_LAUNCH(k_step_gumbel, true, false, d, n_sim, n_sim, c.g0, c.g1);
         AZ_HIP(hipGetLastError());
         return AZ_OK;
     }
 #undef GUMBEL_LAUNCH
     for (int s = 0; s < n_sim; ++s) {
-        if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
-        else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, e->stream, d, s, 0, d.G);
-        AZ_TRY(forward(e, d.batch_cnt + (s & 1), cap, s));
+        if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
+        else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
+        AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
     }
-    hipLaunchKernelGGL((k_step<true, false>), gg, gb, 0, e->stream, d, n_sim, 0, d.G);
+    hipLaunchKernelGGL((k_step<true, false>), gg, gb, 0, c.st, d, n_sim, c.g0, c.g1);
     AZ_HIP(hipGetLastError());
     return AZ_OK;
 }
 
-static int do_search(az_engine *e, int n_sim) {
-    EngDev &d = e->d;
+// queues one search on chain c (null: the whole engine on its stream; a slot group's chain: one search per root, sim_base 0)
+static int do_search(az_engine *e, int n_sim, const Chain *grp = nullptr) {
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL || e->ext_fn, AZ_ESTATE, "AZ_EVAL_EXTERNAL engine without an evaluator (az_engine_set_evaluator)");
-    d.sim_base = e->sim_base;
-    e->sim_base += (u32)n_sim;
-    e->lockstep_iters += d.rollout ? n_sim : ((d.gm > 0 && d.K > 1) ? gumbel_locksteps(n_sim, d.gm, d.K) : (n_sim + d.K - 1) / d.K) + 1;
+    if (!grp) {
+        e->d.sim_base = e->sim_base;
+        e->sim_base += (u32)n_sim;
+    }
+    const Chain whole = whole_chain(e);
+    const Chain &c = grp ? *grp : whole;
+    const EngDev &d = c.d;
+    e->lockstep_iters[c.idx] += d.rollout ? n_sim : ((d.gm > 0 && d.K > 1) ? gumbel_locksteps(n_sim, d.gm, d.K) : (n_sim + d.K - 1) / d.K) + 1;
     // network rows: every searching slot brings up to K leaves per lock-step (K = 1 unless az_engine_set_leaf_batch / _set_gumbel_batch)
-    const int R = d.G * d.K;
-    int cap = (e->active_bound > 0 && e->active_bound < d.G ? e->active_bound : d.G) * d.K;
+    const int W = c.g1 - c.g0, R = W * d.K;
+    // (a group takes its own live count, not active_bound: the shared counters behind that are moving while another group plays its ply)
+    const int ab = grp ? grp->live : e->active_bound;
+    int cap = (ab > 0 && ab < W ? ab : W) * d.K;
     // graph replay needs launch parameters that do not change from search to search: the Philox counter base must be 0
     // (one search per root, as in self-play and the arena), no per-launch event recording, and a quantised batch cap
     const bool graphable = e->graphs_ok && d.sim_base == 0 && !(e->net && az_net_profiling(e->net)) && e->cfg.evaluator != AZ_EVAL_EXTERNAL;
@@ -2335,37 +2376,38 @@ static int do_search(az_engine *e, int n_sim) {
     // launches the kernels the timed (graph-replayed) steps launch (an exact cap of 4095 -- one game of 4096 over, as happens from
     // ply ~11 on: Othello has early wipe-outs -- would hand the trunk to the one-board-per-wave kernel for the rest of the wave)
     const int cap_q = (R >= 4096 && cap < 4096) ? (cap + 511) / 512 * 512 : R;  // below 4096 rows the network picks other kernels
-    if (!graphable) return enqueue_search(e, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
+    if (!graphable) return enqueue_search(e, c, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
     cap = cap_q;
     // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31).  A change
     // of K (either setter) drops every graph.  The full Gumbel kernels are other kernels again (bit 31; cap < 2^31).
-    const unsigned long long key = ((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)n_sim << 32) |
-                                   ((unsigned long long)(d.nval != nullptr) << 31) | (unsigned)cap;
+    const az_engine::GraphKey key(((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)n_sim << 32) |
+                                      ((unsigned long long)(d.nval != nullptr) << 31) | (unsigned)cap,
+                                  ((unsigned long long)c.g0 << 32) | (unsigned)c.g1);
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) {
-        AZ_HIP(hipGraphLaunch(it->second, e->stream));
+        AZ_HIP(hipGraphLaunch(it->second, c.st));
         e->graph_replays++;
         return AZ_OK;
     }
-    if (e->graph_seen[key]++ == 0) return enqueue_search(e, n_sim, cap);  // first time: plain launches (kernel attributes get set)
+    if (e->graph_seen[key]++ == 0) return enqueue_search(e, c, n_sim, cap);  // first time: plain launches (kernel attributes get set)
     hipGraph_t g = nullptr;
     hipGraphExec_t ex = nullptr;
-    if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    if (hipStreamBeginCapture(c.st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
         e->graphs_ok = false;
-        return enqueue_search(e, n_sim, cap);
+        return enqueue_search(e, c, n_sim, cap);
     }
-    const int rc = enqueue_search(e, n_sim, cap);  // recorded, not executed
-    const hipError_t er = hipStreamEndCapture(e->stream, &g);
+    const int rc = enqueue_search(e, c, n_sim, cap);  // recorded, not executed
+    const hipError_t er = hipStreamEndCapture(c.st, &g);
     if (rc != AZ_OK || er != hipSuccess || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
         (void)hipGetLastError();
         if (g) (void)hipGraphDestroy(g);
         e->graphs_ok = false;
-        return enqueue_search(e, n_sim, cap);
+        return enqueue_search(e, c, n_sim, cap);
     }
     (void)hipGraphDestroy(g);
     e->graphs[key] = ex;
-    AZ_HIP(hipGraphLaunch(ex, e->stream));
+    AZ_HIP(hipGraphLaunch(ex, c.st));
     e->graph_replays++;
     return AZ_OK;
 }
@@ -2384,17 +2426,26 @@ static int reset_external(az_engine *e) {
     return AZ_OK;
 }
 
-static int fetch_counters(az_engine *e) {
-    AZ_HIP(hipMemcpyAsync(e->h_ctr, e->d.ctr, sizeof(unsigned long long) * CTR_ALLOC, hipMemcpyDeviceToHost, e->stream));
-    AZ_HIP(hipMemcpyAsync(&e->h_err[0], e->d.err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    AZ_HIP(hipMemcpyAsync(&e->h_err[1], e->d.max_nodes, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    AZ_HIP(hipMemcpyAsync(&e->h_err[2], e->d.max_path, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    AZ_HIP(hipStreamSynchronize(e->stream));
+// the shared counters and error words, read behind everything queued on the chain's stream (null: the engine's) into the chain's own
+// host copy; a slot group also reads its live word
+static int fetch_counters(az_engine *e, const Chain *grp) {
+    const int idx = grp ? grp->idx : 0;
+    hipStream_t st = grp ? grp->st : e->stream;
+    int *he = e->h_err + 4 * idx;
+    AZ_HIP(hipMemcpyAsync(e->h_ctr + (size_t)CTR_ALLOC * idx, e->d.ctr, sizeof(unsigned long long) * CTR_ALLOC, hipMemcpyDeviceToHost, st));
+    AZ_HIP(hipMemcpyAsync(&he[0], e->d.err, sizeof(int), hipMemcpyDeviceToHost, st));
+    AZ_HIP(hipMemcpyAsync(&he[1], e->d.max_nodes, sizeof(int), hipMemcpyDeviceToHost, st));
+    AZ_HIP(hipMemcpyAsync(&he[2], e->d.max_path, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (grp) {  // queued only: the host loop of az_engine_run waits for the group when its turn comes
+        AZ_HIP(hipMemcpyAsync(&he[3], grp->d.live, sizeof(int), hipMemcpyDeviceToHost, st));
+        return AZ_OK;
+    }
+    AZ_HIP(hipStreamSynchronize(st));
     return AZ_OK;
 }
 
-static int check_err(az_engine *e) {
-    int f = e->h_err[0];
+static int check_err(az_engine *e, int idx) {
+    int f = e->h_err[4 * idx];
     if (f & ERR_EVAL) {  // first: the rejected rows were consumed by the step that followed
         e->unevaluated = true;
         int slot = -1;
@@ -2410,6 +2461,140 @@ static int check_err(az_engine *e) {
     return AZ_OK;
 }
 
+// ---- slot groups (az_engine_set_groups) ---------------------------------------------------------------------------------------
+// the mode of this engine that the grouped run does not serve, or null
+static const char *groups_unserved(const az_engine *e) {
+    if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return "an AZ_EVAL_EXTERNAL engine (external evaluator: its export buffers are per engine)";
+    if (e->cfg.evaluator == AZ_EVAL_ROLLOUT) return "a rollout engine (AZ_EVAL_ROLLOUT: no network to overlap with)";
+    if (e->sym_mask != 0) return "the symmetry ensemble (az_engine_set_symmetry: the twins' rows are per engine)";
+    if (e->symr_mask != 0) return "the random symmetry mode (az_engine_set_symmetry_random: the twins' rows are per engine)";
+    if (e->leaf_batch > 1) return "leaf_batch > 1 (az_engine_set_leaf_batch)";
+    if (e->d.gm > 0) return "the Gumbel search (az_engine_set_gumbel)";
+    return nullptr;
+}
+
+// The measured rule (profiles/r14_groups.txt): the groups az_engine_run plays with where nothing was asked for.  A
+// shape has n > 1 only where the worst of three grouped runs beat the best of three runs of the build before by more than that
+// build's own spread; every shape that was not measured plays as one group.
+static int groups_auto(const az_engine *e) {
+    const az_engine_cfg &c = e->cfg;
+    const int G = e->d.G;
+    if (c.evaluator != AZ_EVAL_NET) return 1;  // the fake evaluator has no network kernels to run beside
+    if (c.game == AZ_OTHELLO && c.H == 8) {
+        if (G >= 4096 && G < 8192) return 2;  // 4096 slots: 2 x 2048 +4.5 %; 4 x 1024 loses (-14 %)
+        if (G >= 32768) return 2;             // 32768 slots: 2 x 16384 +1.3 %
+        return 1;                             // 512 slots: +0.4 %, not worth a second chain; 8192 .. 32767: not measured
+    }
+    if (c.game == AZ_CONNECT4 && c.H == 6 && c.W == 7) return G >= 8192 ? 4 : 1;  // 8192 slots: 4 x 2048 +9.4 %, 2 x 4096 +0.2 %
+    return 1;
+}
+
+// groups of the next az_engine_run: the request (auto: the rule) where the mode is served and every group holds a block of slots
+static int groups_in_force(const az_engine *e) {
+    if (groups_unserved(e)) return 1;
+    if (e->net && az_net_profiling(e->net)) return 1;  // the profiled run is today's launch sequence: full-width, un-overlapped kernels
+    int n = e->groups_req > 0 ? e->groups_req : groups_auto(e);
+    return e->d.G > GPB ? n : 1;  // a group is whole blocks of slots (trailing groups may be empty: 40 slots in 4 groups are 16, 16, 8, 0)
+}
+
+extern "C" int az_engine_set_groups(az_engine *e, int32_t n) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_groups");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_groups");
+    AZ_REQUIRE(n == 0 || n == 1 || n == 2 || n == 4, AZ_EINVAL, "az_engine_set_groups: %d groups (0 = auto, 1, 2 or 4)", n);
+    const char *why = groups_unserved(e);
+    AZ_REQUIRE(n <= 1 || !why, AZ_EINVAL, "az_engine_set_groups: %d slot groups are not served for %s", n, why);
+    AZ_REQUIRE(n <= 1 || e->d.G > GPB, AZ_EINVAL, "az_engine_set_groups: %d groups of %d slots: a group is whole blocks of %d slots, this engine is less than a block to split", n, e->d.G, GPB);
+    if (n == e->groups_req && !e->groups_env) return AZ_OK;
+    AZ_TRY(enter(e));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    e->groups_req = n; e->groups_env = false;
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_groups(az_engine *e, int32_t *n) {
+    AZ_REQUIRE(e && n, AZ_EINVAL, "null argument");
+    *n = groups_in_force(e);
+    return AZ_OK;
+}
+
+// group i of n: slots [g0, g1) in whole blocks, the group's stream, rows [g0, g1) of the network batch, counters 4 i .. and live word i
+static int make_chain(az_engine *e, int i, int n, Chain *c) {
+    const EngDev &d = e->d;
+    const int blocks = (d.G + GPB - 1) / GPB, per = (blocks + n - 1) / n;
+    int g0 = i * per * GPB, g1 = (i + 1) * per * GPB;
+    g0 = g0 < d.G ? g0 : d.G; g1 = g1 < d.G ? g1 : d.G;
+    if (i > 0 && !e->gstream[i]) {  // from the other priority pool (az_engine_pair): streams of one priority may share a hardware queue
+        int least = 0, greatest = 0;
+        AZ_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        AZ_HIP(hipStreamCreateWithPriority(&e->gstream[i], hipStreamNonBlocking, greatest));
+    }
+    c->d = d; c->g0 = g0; c->g1 = g1; c->idx = i; c->st = i == 0 ? e->stream : e->gstream[i]; c->beside = true; c->live = 0;
+    c->d.sim_base = 0;
+    c->d.nn_in = d.nn_in + (size_t)g0 * d.gd.cells; c->d.probs = d.probs + (size_t)g0 * d.A; c->d.value = d.value + g0;
+    c->d.batch_cnt = d.batch_cnt + 4 * i; c->d.live = d.live + i;
+    return AZ_OK;
+}
+
+// one ply of a slot group: the search, the move, the re-root, and the counters on their way to the host
+static int issue_ply(az_engine *e, const Chain &c) {
+    AZ_TRY(do_search(e, e->cfg.n_sim, &c));
+    AZ_HIP(hipMemsetAsync(c.d.live, 0, sizeof(int), c.st));
+    hipLaunchKernelGGL(k_move, grid_for(c.g1 - c.g0, TB), dim3(TB), 0, c.st, c.d, c.g0, c.g1);
+    launch_reroot(c);
+    return fetch_counters(e, &c);
+}
+
+// az_engine_run as n slot groups.  The groups' chains are independent (what they share is touched by atomics or disjoint by slot), so
+// each runs on its own stream and the host keeps one ply queued per group: wait for the oldest, read its counters, queue its next.
+// A group without a live slot has nothing left to do -- only a slot's own finished game is refilled -- and is retired.
+static int run_grouped(az_engine *e, int n, int32_t n_games, long long max_iters) {
+    Chain ch[AZ_MAX_GROUPS];
+    bool open[AZ_MAX_GROUPS] = {false, false, false, false};
+    if (!e->ev_grp) AZ_HIP(hipEventCreateWithFlags(&e->ev_grp, hipEventDisableTiming));
+    int widest = 0;
+    for (int i = 0; i < n; ++i) {
+        AZ_TRY(make_chain(e, i, n, &ch[i]));
+        widest = ch[i].g1 - ch[i].g0 > widest ? ch[i].g1 - ch[i].g0 : widest;
+    }
+    if (e->cfg.evaluator == AZ_EVAL_NET) AZ_TRY(az_net_set_lanes(e->net, n, widest));
+    AZ_HIP(hipEventRecord(e->ev_grp, e->stream));  // behind k_reset_all
+    int rc = AZ_OK, n_open = 0;
+    for (int i = 0; i < n && rc == AZ_OK; ++i) {
+        if (i > 0) AZ_HIP(hipStreamWaitEvent(ch[i].st, e->ev_grp, 0));
+        const int first = n_games - ch[i].g0;  // k_reset_all seats games 0 .. in slots 0 ..
+        ch[i].live = first < 0 ? 0 : (first < ch[i].g1 - ch[i].g0 ? first : ch[i].g1 - ch[i].g0);
+        if (ch[i].live == 0) continue;
+        rc = issue_ply(e, ch[i]);
+        open[i] = rc == AZ_OK;
+        n_open += open[i] ? 1 : 0;
+    }
+    bool done = false;
+    for (long long it = 0; rc == AZ_OK && n_open > 0 && !done; ++it) {
+        if (it >= max_iters) { az_set_error("self-play did not finish within %lld plies", max_iters); rc = AZ_ESTATE; break; }
+        for (int i = 0; i < n && rc == AZ_OK && !done; ++i) {
+            if (!open[i]) continue;
+            if (hipStreamSynchronize(ch[i].st) != hipSuccess) { az_set_error("HIP error: slot group %d: %s", i, hipGetErrorString(hipGetLastError())); rc = AZ_EHIP; break; }
+            rc = check_err(e, i);
+            if (rc != AZ_OK) break;
+            ch[i].live = e->h_err[4 * i + 3];
+            if (e->h_ctr[(size_t)CTR_ALLOC * i + CTR_GAMES_DONE] >= (unsigned long long)n_games) { done = true; break; }
+            if (ch[i].live == 0) { open[i] = false; --n_open; continue; }
+            rc = issue_ply(e, ch[i]);
+        }
+    }
+    // nothing of any group may be in flight when the call returns, whatever ended it (a ply queued by a group that did not see the
+    // last game end plays on empty slots)
+    for (int i = 0; i < n; ++i) (void)hipStreamSynchronize(ch[i].st);
+    if (rc != AZ_OK) return rc;
+    AZ_TRY(fetch_counters(e));  // the final words, as every later reader expects them (slot 0 of the host copies)
+    AZ_TRY(check_err(e));
+    if (e->h_ctr[CTR_GAMES_DONE] >= (unsigned long long)n_games) return AZ_OK;
+    az_set_error("self-play: every slot group is empty and %llu of %d games are done", e->h_ctr[CTR_GAMES_DONE], (int)n_games);
+    return AZ_ESTATE;
+}
+
 extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_games) {
     AZ_REQUIRE(e && n_games > 0, AZ_EINVAL, "bad arguments");
     AZ_NO_OPEN_SEARCH(e, "az_engine_run");
@@ -2417,15 +2602,22 @@ extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_gam
     AZ_TRY(enter(e));
     EngDev &d = e->d;
     AZ_TRY(reset_external(e));
-    e->lockstep_iters = 0;
+    for (int i = 0; i < AZ_MAX_GROUPS; ++i) e->lockstep_iters[i] = 0;
+    const int n_groups = groups_in_force(e);
+    if (e->groups_req > 1 && !e->groups_env && n_groups == 1 && groups_unserved(e)) {
+        az_set_error("az_engine_run: %d slot groups were asked for (az_engine_set_groups) and are not served for %s", e->groups_req, groups_unserved(e));
+        return AZ_EINVAL;
+    }
     hipLaunchKernelGGL(k_reset_all, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, (u32)first_game_id, (int)n_games);
     long long max_iters = ((long long)n_games / d.G + 2) * (long long)d.max_plies + 8;
     e->active_bound = n_games < d.G ? n_games : d.G;
+    if (n_groups > 1) return run_grouped(e, n_groups, n_games, max_iters);
+    const Chain whole = whole_chain(e);
     for (long long it = 0; it < max_iters; ++it) {
         e->sim_base = 0;
         AZ_TRY(do_search(e, e->cfg.n_sim));
-        hipLaunchKernelGGL(k_move, grid_for(d.G, TB), dim3(TB), 0, e->stream, d);
-        launch_reroot(e);
+        hipLaunchKernelGGL(k_move, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, 0, d.G);
+        launch_reroot(whole);
         AZ_TRY(fetch_counters(e));
         AZ_TRY(check_err(e));
         if (e->h_ctr[CTR_GAMES_DONE] >= (unsigned long long)n_games) return AZ_OK;
@@ -2448,7 +2640,8 @@ extern "C" int az_engine_get_stats(az_engine *e, az_engine_stats *out) {
     out->samples = s < e->cfg.sample_capacity ? s : e->cfg.sample_capacity;
     out->net_evals = (int64_t)e->h_ctr[CTR_NET_EVALS];
     out->plies = (int64_t)e->h_ctr[CTR_PLIES];
-    out->lockstep_iters = e->lockstep_iters;
+    out->lockstep_iters = 0;  // a ply's lock-steps once: the group that played the most plies
+    for (int i = 0; i < AZ_MAX_GROUPS; ++i) out->lockstep_iters = e->lockstep_iters[i] > out->lockstep_iters ? e->lockstep_iters[i] : out->lockstep_iters;
     out->max_nodes_used = e->h_err[1];
     out->error_flags = e->h_err[0];
     out->graph_replays = e->graph_replays;
@@ -2572,8 +2765,8 @@ extern "C" int az_engine_advance(az_engine *e) {
     e->sim_base = 0;
     EngDev &d = e->d;
     // games that end here must not be refilled: cap the queue at what has been started
-    hipLaunchKernelGGL(k_move, grid_for(d.G, TB), dim3(TB), 0, e->stream, d);
-    launch_reroot(e);
+    hipLaunchKernelGGL(k_move, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, 0, d.G);
+    launch_reroot(whole_chain(e));
     AZ_TRY(fetch_counters(e));
     return check_err(e);
 }
@@ -2710,7 +2903,7 @@ extern "C" int az_engine_play(az_engine *e, const int32_t *h_actions, int32_t n,
     int *d_act = e->scr_a, *d_st = e->scr_b;
     AZ_HIP(hipMemcpyAsync(d_act, h_actions, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_apply_moves, grid_for(n, TB), dim3(TB), 0, e->stream, d, d_act, (int)n, d_st);
-    launch_reroot(e);
+    launch_reroot(whole_chain(e));
     AZ_HIP(hipMemcpyAsync(h_status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
     for (int i = 0; i < n; ++i)

@@ -2703,6 +2703,11 @@ struct az_net {
     float *hwq = nullptr;  // head matrix in 16x16x4 B-fragment order [F2/16][NH/16][64 lanes][4] (k_heads2)
     float *fc1wq = nullptr, *fc2wq = nullptr;  // fc1 / fc2 in the same fragment order (k_dense_frag); null where the shapes do not tile
     float *feat, *h1, *h2;
+    // az_net_set_lanes: the activation rows of lanes 1 .. (lane 0 = the three above), lane_rows each.  A forward of lane l runs with
+    // feat / h1 / h2 pointing at lane l's rows for the duration of its launches (forward_impl): the net is driven by one host thread.
+    struct Acts { float *feat, *h1, *h2; };
+    std::vector<Acts> lanes;
+    int lane_rows = 0;
     // exact block-fixed-point dense layers (AZ_DENSE_I8=1, OthelloNet): digit planes + exponents of the two weight matrices and of the
     // activation rows (one buffer, used by fc1 and then by fc2)
     bool qd_on = false;
@@ -3296,6 +3301,20 @@ static int launch_trunk2(az_net *n, const float *in, int B, const int *dyn, hipS
     return AZ_OK;
 }
 
+// az_net_forward_lane(beside = 1): the forward shares the chip with another launch chain.  Per host thread, like the event pair above:
+// set around run_stage by forward_impl, read by the launchers that pick a kernel by size.
+static thread_local int g_beside = 0;
+// Thresholds of that regime, measured with two 2048-row chains of OthelloNet side by side (games/s of the headline):
+//   * dense layers: k_dense_frag up to 1024 rows only, and k_gemm's 64 x 64 tile from ONE block per CU up (fc2 at 2048 rows: 256 blocks
+//     instead of 128 of 64 x 128).  4 352 against 3 830 with the lone launch's picks (k_dense_frag for fc2, L2-bound at ~9 TB/s, or the
+//     64 x 128 tile: the same 3 830): the other chain's kernels are the second resident block the lone launch needs two of its own for.
+//   * trunk: k_trunk stays below 4096 boards (k_trunk2 from 2048: 3 652, its one-wave-per-SIMD blocks leave no room for the neighbour).
+// AZ_BESIDE_FRAG_MAX / AZ_BESIDE_TILE (AZ_GEMM_TILE's codes) / AZ_BESIDE_TRUNK2_MIN override, for A/B runs.
+static int beside_env(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+static int beside_trunk2_min() { static int v = -2; if (v == -2) v = beside_env("AZ_BESIDE_TRUNK2_MIN", 4096); return v; }
+static int beside_frag_max() { static int v = -2; if (v == -2) v = beside_env("AZ_BESIDE_FRAG_MAX", 1024); return v; }
+static int beside_tile() { static int v = -2; if (v == -2) v = beside_env("AZ_BESIDE_TILE", 0); return v; }
+
 static bool trunk_v1() { static int v = -1; if (v < 0) { const char *e = getenv("AZ_TRUNK_V1"); v = (e && atoi(e)) ? 1 : 0; } return v == 1; }
 
 // boards up to which the trunk runs four waves per board (AZ_TRUNK_Q_MAX; 0: never)
@@ -3305,7 +3324,7 @@ template <int CH, int CW, bool WINO>
 static int launch_trunk(az_net *n, const float *in, int B, const int *dyn, hipStream_t st) {
     // two boards per wave on 32x32x2 pays from ~4096 boards up (16384: 325 vs 331 us); below that the one-board-
     // per-wave kernel fills the chip better (2048: 45 vs 77 us).  AZ_TRUNK_V1=1 forces the latter.
-    n->last_trunk_two_boards = (!trunk_v1() && B >= 4096) ? 1 : 0;
+    n->last_trunk_two_boards = (!trunk_v1() && B >= (g_beside ? beside_trunk2_min() : 4096)) ? 1 : 0;
     n->last_trunk_q = 0;
     if (n->last_trunk_two_boards) return launch_trunk2<CH, CW, WINO>(n, in, B, dyn, st);
     if (B <= trunk_q_max()) {  // few boards: four waves per board (k_trunk_q)
@@ -3391,7 +3410,8 @@ static int frag_max_rows(int K) {
     return v >= 0 ? v : (K >= 1024 ? 2048 : 1024);
 }
 static GemmKind gemm_kind(int M, int N, int K, bool have_q = true) {
-    if (have_q && M <= frag_max_rows(K) && frag_shape(N, K)) return GK_FRAG;  // latency-bound row counts: the shortest accumulation chain
+    const int fmax = (g_beside && beside_frag_max() < frag_max_rows(K)) ? beside_frag_max() : frag_max_rows(K);
+    if (have_q && M <= fmax && frag_shape(N, K)) return GK_FRAG;  // latency-bound row counts: the shortest accumulation chain
     // measured crossover against the tiled GEMM (MI355X): K = 512 up to 128 rows (15 vs 21 us), K = 1024 up to 256 rows (28 vs 40 us)
     if (M <= (K >= 1024 ? 256 : 128) && K % 32 == 0) return GK_SMALL;  // few rows: latency matters, not throughput
     // large row counts: the one-wave-per-SIMD kernel (256x256 workgroup tiles), from one tile per CU up.  AZ_GEMM_SOLO=0 / 1 forces.
@@ -3458,13 +3478,14 @@ static int launch_gemm(const float *A, const float *Bw, const float *Bq, const f
     const long long mb128 = (M + 127) / 128, mb64 = (M + 63) / 64;
     static int force = -1;
     if (force < 0) { const char *e = getenv("AZ_GEMM_TILE"); force = e ? atoi(e) : 0; }
-    if (force == 1 && N % 128 == 0) return gemm_go<128, 128, 64, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (force == 2 && N % 64 == 0) return gemm_go<128, 64, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (force == 3 && N % 64 == 0) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (force == 4 && N % 128 == 0) return gemm_go<64, 128, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
+    const int tile = force ? force : (g_beside ? beside_tile() : 0);
+    if (tile == 1 && N % 128 == 0) return gemm_go<128, 128, 64, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
+    if (tile == 2 && N % 64 == 0) return gemm_go<128, 64, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
+    if (tile == 3 && N % 64 == 0) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
+    if (tile == 4 && N % 128 == 0) return gemm_go<64, 128, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
     if (N % 128 == 0 && mb128 * (N / 128) >= 512) return gemm_go<128, 128, 64, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
     if (N % 64 == 0 && mb128 * (N / 64) >= 512) return gemm_go<128, 64, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (N % 64 == 0 && mb64 * (N / 64) >= 512) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
+    if (N % 64 == 0 && mb64 * (N / 64) >= (g_beside ? 256 : 512)) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
     if (N % 128 == 0) return gemm_go<64, 128, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
     if (N % 64 == 0) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
     if (N % 32 == 0) return gemm_go<128, 32, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
@@ -3715,8 +3736,23 @@ extern "C" int az_net_profile_read(az_net *n, double *ms_total, int64_t *launche
     return AZ_OK;
 }
 
-static int forward_impl(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream) {
+static int forward_lane0(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream);
+
+// the forward on the activation rows of `lane`; beside: see g_beside
+static int forward_impl(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream, int lane = 0, int beside = 0) {
     AZ_REQUIRE(n && d_input && d_probs && d_value, AZ_EINVAL, "null argument");
+    AZ_REQUIRE(lane >= 0 && lane <= (int)n->lanes.size(), AZ_EINVAL, "lane %d of %d (az_net_set_lanes)", lane, (int)n->lanes.size() + 1);
+    AZ_REQUIRE(lane == 0 || B <= n->lane_rows, AZ_EINVAL, "batch %d beyond the %d rows of lane %d", B, n->lane_rows, lane);
+    const az_net::Acts own = {n->feat, n->h1, n->h2};
+    if (lane > 0) { const az_net::Acts &a = n->lanes[lane - 1]; n->feat = a.feat; n->h1 = a.h1; n->h2 = a.h2; }
+    g_beside = beside;
+    const int rc = forward_lane0(n, d_input, B, dyn, d_probs, d_value, stream);
+    g_beside = 0;
+    n->feat = own.feat; n->h1 = own.h1; n->h2 = own.h2;
+    return rc;
+}
+
+static int forward_lane0(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream) {
     AZ_REQUIRE(n->committed, AZ_ESTATE, "az_net_commit has not been called since the last az_net_set_tensor");
     AZ_REQUIRE(B > 0 && B <= n->max_batch, AZ_EINVAL, "batch %d outside (0, max_batch=%d]", B, n->max_batch);
     hipStream_t st = (hipStream_t)stream;
@@ -3754,6 +3790,32 @@ extern "C" int az_net_forward_dyn(az_net *n, const float *d_input, const int32_t
                                   float *d_value, void *stream) {
     AZ_REQUIRE(d_count, AZ_EINVAL, "null count pointer");
     return forward_impl(n, d_input, max_B, d_count, d_probs, d_value, stream);
+}
+
+extern "C" int az_net_forward_lane(az_net *n, int lane, int beside, const float *d_input, const int32_t *d_count, int max_B, float *d_probs,
+                                   float *d_value, void *stream) {
+    AZ_REQUIRE(d_count, AZ_EINVAL, "null count pointer");
+    return forward_impl(n, d_input, max_B, d_count, d_probs, d_value, stream, lane, beside);
+}
+
+extern "C" int az_net_set_lanes(az_net *n, int n_lanes, int rows) {
+    AZ_REQUIRE(n, AZ_EINVAL, "null net");
+    AZ_REQUIRE(n_lanes >= 1 && n_lanes <= AZ_MAX_GROUPS, AZ_EINVAL, "az_net_set_lanes: %d lanes outside [1, %d]", n_lanes, AZ_MAX_GROUPS);
+    AZ_REQUIRE(rows > 0 && rows <= n->max_batch, AZ_EINVAL, "az_net_set_lanes: %d rows outside (0, max_batch=%d]", rows, n->max_batch);
+    AZ_REQUIRE(n_lanes == 1 || !n->qd_on, AZ_EINVAL, "az_net_set_lanes: the fixed-point dense layers (AZ_DENSE_I8) keep one set of digit planes");
+    if (n->game == AZ_TICTACTOE || n_lanes == 1) return AZ_OK;  // the MLP keeps no activation in memory
+    AZ_HIP(hipDeviceSynchronize());  // a lane's rows may be replaced: no forward may be in flight
+    if (rows > n->lane_rows) n->lanes.clear();  // the smaller rows stay in n->allocs until the net goes
+    const int want_rows = rows > n->lane_rows ? rows : n->lane_rows;
+    while ((int)n->lanes.size() < n_lanes - 1) {
+        az_net::Acts a = {nullptr, nullptr, nullptr};
+        AZ_TRY(net_alloc(n, &a.feat, (size_t)want_rows * n->FIN));
+        AZ_TRY(net_alloc(n, &a.h1, (size_t)want_rows * n->F1));
+        AZ_TRY(net_alloc(n, &a.h2, (size_t)want_rows * n->F2));
+        n->lanes.push_back(a);
+    }
+    n->lane_rows = want_rows;
+    return AZ_OK;
 }
 
 extern "C" int az_net_time_stage(az_net *n, int stage, int B, int iters, void *stream, float *ms_per_launch) {

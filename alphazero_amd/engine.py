@@ -249,7 +249,7 @@ class SelfPlayEngine:
 
     def __init__(self, game_id, H, W, n_slots, n_sim, net=None, dirichlet_alpha=0.03, dirichlet_epsilon=0.25,
                  temp_max_step=4, temp_min_step=4, tie_mode=TIE_RANDOM, noise_mode=NOISE_PHILOX, evaluator=EVAL_NET,
-                 seed=0, node_capacity=None, max_plies=None, sample_capacity=None):
+                 seed=0, node_capacity=None, max_plies=None, sample_capacity=None, groups=None):
         cells = H * W
         if max_plies is None:
             max_plies = 2 * cells if game_id == 0 else cells + 1
@@ -275,6 +275,8 @@ class SelfPlayEngine:
         self._eval_views = {}    # device pointer -> full-size view (the rows are sliced per call)
         self._eval_streams = {}
         self._sym_mode = None    # which symmetry mode set_symmetry last put in force: None, "ensemble" or "random"
+        if groups is not None:
+            self.set_groups(groups)
 
     # ---------------------------------------------------------------------------------------- external evaluator
     def set_evaluator(self, fn):
@@ -351,6 +353,19 @@ class SelfPlayEngine:
                 self._sym_mode = None
             check(lib().az_engine_set_symmetry(self.h, mask))
             self._sym_mode = "ensemble" if mask != 0 else None
+
+    def set_groups(self, n):
+        """run() plays the slots as n contiguous slot groups, each a launch chain of its own on its own stream, so that one group's
+        tree kernels overlap another's network kernels (az_engine_set_groups; 1, 2 or 4; None / 0: the measured default).  The
+        samples are the same rows in another order.  Plain search of EVAL_NET / EVAL_FAKE engines only: anything else with n > 1
+        is a ValueError that names the mode."""
+        check(lib().az_engine_set_groups(self.h, int(n or 0)))
+
+    def groups(self):
+        """the slot groups the next run() would play with (1 under HipNet.profile and in every mode groups are not served for)"""
+        n = C.c_int32()
+        check(lib().az_engine_groups(self.h, C.byref(n)))
+        return n.value
 
     def set_leaf_batch(self, k):
         """k simulations per slot and lock-step, kept apart by virtual loss (az_engine_set_leaf_batch; 1: the plain search, the

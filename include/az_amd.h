@@ -94,6 +94,18 @@ int az_net_forward(az_net *net, const float *d_input, int B, float *d_probs, flo
  * earlier kernel on `stream` (the engine compacts the leaves that need an evaluation into the front rows). */
 int az_net_forward_dyn(az_net *net, const float *d_input, const int32_t *d_count, int max_B, float *d_probs,
                        float *d_value, void *stream);
+/* Lanes: a net has ONE set of activation rows (conv features, fc1 and fc2 outputs), so two forwards in flight on two streams
+ * would overwrite each other.  az_net_set_lanes(net, n, rows) gives lanes 1 .. n - 1 activation rows of their own, `rows` each
+ * (lane 0 is the net's own set, max_batch rows); it only grows, and waits for the device before it returns.  n in [1, 4];
+ * AZ_EINVAL: n outside that, rows outside (0, max_batch], n > 1 on a net under AZ_DENSE_I8 (its digit planes are one set).
+ * az_net_forward_lane is az_net_forward_dyn on the activation rows of `lane` (lane 0: exactly az_net_forward_dyn); forwards of
+ * different lanes may be in flight together on different streams, issued from one host thread.  beside != 0 says that the
+ * forward runs next to another one: the size thresholds that pick a layer's kernel were measured with the chip to itself, and
+ * a forward that shares it picks by the thresholds measured for that regime.  Every kernel of a layer gives the same bits, so
+ * the flag never changes a result; az_net_stage_kernel keeps answering for a lone launch. */
+int az_net_set_lanes(az_net *net, int n_lanes, int rows);
+int az_net_forward_lane(az_net *net, int lane, int beside, const float *d_input, const int32_t *d_count, int max_B,
+                        float *d_probs, float *d_value, void *stream);
 /* Evaluation averaged over the board's symmetries (ensemble inference: AlphaGo Zero evaluates each leaf in one of the eight
  * orientations, Silver et al. 2017 "Mastering the game of Go without human knowledge", Methods; KataGo's analysis mode averages
  * over all of them).  The reference has no counterpart: it uses the symmetries for training samples only (trainer.py:275-284).
@@ -250,6 +262,21 @@ int az_engine_search_begin(az_engine *e, int32_t n_sim);
 /* puts b's stream on a hardware queue that a's does not share (a stream of another priority), so that the two searches really
  * run side by side; before b's first search */
 int az_engine_pair(az_engine *a, az_engine *b);
+/* Slot groups of az_engine_run: the engine's slots are split into n contiguous groups (boundaries at multiples of the 16 games
+ * a search block holds), and every group plays its plies as a launch chain of its own -- its own stream (the later groups' from
+ * the other priority pool, as az_engine_pair), its own leaf-row counters and rows of the network batch, its own lane of the net,
+ * its own linear search graph -- so that one group's tree kernels run while another group's network kernels hold the matrix
+ * pipe.  The host keeps one ply queued per group.  Games depend on (seed, game id) only: the samples are the same rows bit for
+ * bit, appended in another order.  n in {1, 2, 4}; 0 = auto (the default: the measured rule on game and slot count, DESIGN
+ * section 20; 1 wherever groups are not served).  Served: az_engine_run of AZ_EVAL_NET / AZ_EVAL_FAKE engines in the plain
+ * search.  Not served (auto: 1; an explicit n > 1: AZ_EINVAL naming the mode): AZ_EVAL_EXTERNAL, AZ_EVAL_ROLLOUT, either
+ * symmetry mode, leaf_batch > 1, the Gumbel search, an engine of one block (16 slots) or less.  az_engine_search / _search_begin / _advance
+ * never group.  Under az_net_profile a run plays as one group (today's launch sequence, so the profiled step describes
+ * full-width kernels).  AZ_ENGINE_GROUPS=n in the environment overrides the setting at az_engine_create (ignored, as auto is,
+ * by engines that do not serve groups).  Drops the captured graphs; AZ_ESTATE while a search is open.
+ * az_engine_groups: the groups the next az_engine_run would play with. */
+int az_engine_set_groups(az_engine *e, int32_t n);
+int az_engine_groups(az_engine *e, int32_t *n);
 int az_engine_search_end(az_engine *e);
 int az_engine_root_status(az_engine *e, int8_t *h_players, uint8_t *h_over, int8_t *h_winner, int32_t *h_score);
 
@@ -294,6 +321,7 @@ int az_engine_set_symmetry_random(az_engine *e, int32_t mask);
  * max_batch, a symmetry mask in force (and az_engine_set_symmetry refuses a mask while k > 1); AZ_ESTATE while a search is open
  * or from inside an evaluator.  The engine's cached search graphs are dropped. */
 #define AZ_MAX_LEAF_BATCH 16
+#define AZ_MAX_GROUPS 4  /* slot groups of az_engine_run (az_engine_set_groups) */
 int az_engine_set_leaf_batch(az_engine *e, int32_t k);
 int az_engine_collisions(az_engine *e, int64_t *n);
 
