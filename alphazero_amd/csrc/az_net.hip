@@ -18,6 +18,7 @@
 //                    never leave the wave's private LDS region; weights stream from L2 already tiled in MFMA
 //                    B-fragment order (one coalesced dword per lane).  Batches from 4096 boards up.
 //   k_trunk<CH,CW> : the same layers, one wavefront per board on 16x16x4 MFMA: smaller batches.
+//   k_trunk_quad<CH,CW>: k_trunk with conv3 / conv4 over row tiles that the workgroup's four boards share (8x8, 7x6 planes).
 //   k_gemm<...>    : LDS-tiled f32 MFMA GEMM with bias(+ReLU) epilogue for fc1 / fc2.
 //   k_heads        : policy+value GEMM (N padded to 16) fused with softmax / tanh.
 //   k_mlp          : the 316-parameter TicTacToe MLP, one thread per board.
@@ -430,12 +431,112 @@ struct TrunkGeom {
     static_assert(INP >= CW + 1 && TAIL >= CW + 1, "guard bands for the masked out-of-plane reads");
 };
 
+// ---------------------------------------------------------------------------------------------
+// The valid convolutions (conv3, conv4) of k_trunk with the workgroup's (up to) four boards SHARING row tiles (QUAD form).  The row space of a
+// layer is the boards' output positions back to back -- row r is position r % P_OUT of board r / P_OUT, the board's planes BS floats
+// behind its neighbour's -- so the layer issues ceil(nb * P_OUT / 16) tiles instead of nb * ceil(P_OUT / 16): 8x8 conv3, 4 x 36 rows
+// = 9 tiles for 12.  The A operand is a per-lane LDS read, so a tile may straddle two boards' planes.  Every output element keeps
+// its chain (bias, then tap-major / ic-minor) whichever tile row it sits in: the same bits as the per-board form and k_trunk_q.
+// Dealing: wave w takes channel half nt = w >> 1 of every second row tile, mt = par + 2 i with par = (w & 1) ^ rot, so of NT tiles
+// two waves run ceil(NT / 2) and two run floor(NT / 2) (8x8 conv3: 5, 4, 5, 4 of the 18 (row tile, channel half) units).  Wave w of
+// every workgroup sits on SIMD w of its CU, so a FIXED deal would leave the SIMDs of the 5-unit waves as the bound.  rot is the parity
+// of popcount(blockIdx.x): it differs between blocks i and i + 256 of a launch of 512 blocks (the pair a CU holds after a round-robin
+// placement of 2048 boards) and between even / odd neighbours, so the workgroups resident on a CU put their heavier share on different
+// SIMDs: 9 units per SIMD and workgroup pair where the per-board form issues 12.  (Dealing single units round-robin, 5, 5, 4, 4, is
+// this deal without the rotation; the rotation was chosen because it also halves a wave's weight-fragment registers: one channel half.)
+//   rows = nb * P_OUT (>= 1).  Rows past the last valid one repeat it (finite operands from a valid board) and are never stored.
+//   NA: size of the caller's accumulator array, NU <= NA tiles are computed.
+// ---------------------------------------------------------------------------------------------
+template <int P_OUT, int W_OUT, int IN_W, int IN_PS, int BS, int NU, int NA>
+AZ_D void conv_quad(const float *planes, const float *__restrict__ wf, const float *__restrict__ bias, int lane, int nt, int mt0, int rows,
+                    f32x4 (&acc)[NA]) {
+    static_assert(NU >= 1 && NU <= NA, "accumulators for every tile of the wave");
+    const int m_lane = lane & 15, kq = lane >> 4;
+    int abase[NU];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+        int r = 16 * (mt0 + 2 * i) + m_lane;
+        r = r < rows ? r : rows - 1;
+        const int bd = r / P_OUT, p = r % P_OUT;
+        const int y = p / W_OUT, x = p % W_OUT;
+        abase[i] = bd * BS + kq * IN_PS + y * IN_W + x;
+    }
+    const float *wl = wf + 4 * lane;  // fragment i = 2 j + nt of a tap sits at [tap][i / 4][lane][i % 4]
+    float bfr[2][8];
+#define QUAD_BLOAD(tap_, buf_)                                                             \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                        \
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(wl + ((tap_) * 4 + q) * 256);     \
+        bfr[buf_][2 * q] = nt ? v[1] : v[0];                                               \
+        bfr[buf_][2 * q + 1] = nt ? v[3] : v[2];                                           \
+    }
+    QUAD_BLOAD(0, 0)
+    const float bv = bias[16 * nt + m_lane];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) acc[i] = (f32x4){bv, bv, bv, bv};
+    float ar[A_RING][NU];
+#define QUAD_LOAD(c, i) planes[abase[i] + ((c) / 8 / 3) * IN_W + ((c) / 8 % 3) + 4 * ((c) % 8) * IN_PS]
+#pragma unroll
+    for (int c = 0; c < A_RING; ++c)
+#pragma unroll
+        for (int i = 0; i < NU; ++i) ar[c][i] = QUAD_LOAD(c, i);
+#pragma unroll
+    for (int c = 0; c < 72; ++c) {
+        const int tap = c / 8, j = c % 8;
+        if (j == 0 && tap < 8) { QUAD_BLOAD(tap + 1, (tap + 1) & 1) }
+        float ac[NU];
+#pragma unroll
+        for (int i = 0; i < NU; ++i) ac[i] = ar[c % A_RING][i];
+        if (c + A_RING < 72) {
+#pragma unroll
+            for (int i = 0; i < NU; ++i) ar[c % A_RING][i] = QUAD_LOAD(c + A_RING, i);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // loads stay issued ahead of this step's MFMAs (see conv_mfma)
+#pragma unroll
+        for (int i = 0; i < NU; ++i) acc[i] = MFMA(ac[i], bfr[tap & 1][j], acc[i]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#undef QUAD_LOAD
+#undef QUAD_BLOAD
+}
+
+// one layer of the QUAD form on the wave's share of the NT = ceil(4 P_OUT / 16) row tiles: nu = the number of tiles computed
+template <int P_OUT, int W_OUT, int IN_W, int IN_PS, int BS, int NA>
+AZ_D int conv_quad_deal(const float *planes, const float *__restrict__ wf, const float *__restrict__ bias, int lane, int nt, int par, int rows,
+                        f32x4 (&acc)[NA]) {
+    constexpr int NT = (4 * P_OUT + 15) / 16, NH = (NT + 1) / 2, NL = NT / 2;
+    static_assert(NA == NH, "the accumulators of the heavier share");
+    if constexpr (NH == NL) {
+        conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NH, NA>(planes, wf, bias, lane, nt, par, rows, acc);
+        return NH;
+    } else {
+        if (par == 0) { conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NH, NA>(planes, wf, bias, lane, nt, 0, rows, acc); return NH; }
+        if constexpr (NL > 0) conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NL, NA>(planes, wf, bias, lane, nt, 1, rows, acc);
+        return NL;
+    }
+}
+
+// relu and store of the wave's nu tiles: row r -> out + (r / P_OUT) * OUT_BS + channel * OUT_CS + r % P_OUT
+template <int P_OUT, int OUT_CS, int OUT_BS, int NA>
+AZ_D void store_quad_relu(float *out, int lane, int nt, int par, int nu, int rows, const f32x4 (&acc)[NA]) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i)
+        if (i < nu) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = 16 * (par + 2 * i) + (lane >> 4) * 4 + q;
+                const float v = acc[i][q];
+                if (r < rows) out[(r / P_OUT) * OUT_BS + (nt * 16 + (lane & 15)) * OUT_CS + r % P_OUT] = v > 0.0f ? v : 0.0f;
+            }
+        }
+}
+
 // One wavefront per board; activations never leave the wave's private LDS region and every layer writes
 // its output IN PLACE over its input (the outputs wait in the MFMA accumulators until the layer's last
 // LDS read has been consumed):
 //   inp : (CH+2)x(CW+2) zero-padded input plane        act : [32 ch][PS] planes, conv1 -> conv2 -> conv3 outputs
-// 8.8 KB of LDS per wave -> four 4-wave blocks per CU, i.e. four waves per SIMD: the MFMA pipe always has
-// another wave's k-steps to run while one wave is in a load / store / conv1 phase.
+// 8.8 KB of LDS per wave; the launchers pad the request to three 4-wave blocks per CU.  The Winograd kernels hold 256 registers per
+// wave, i.e. two blocks per CU and two waves per SIMD: the MFMA pipe has another wave's k-steps to run while one wave is in a load /
+// store / conv1 phase.
 template <int CH, int CW, bool WINO>
 __global__ __launch_bounds__(256, 2) void k_trunk(const float *__restrict__ in, int B, const int *__restrict__ dyn_count, TrunkParams tp, float *__restrict__ feat) {
     using G = TrunkGeom<CH, CW>;
@@ -504,6 +605,78 @@ __global__ __launch_bounds__(256, 2) void k_trunk(const float *__restrict__ in, 
                     float v = acc[mt][nt][r];
                     if (m < G::P4) fo[(nt * 16 + (lane & 15)) * G::P4 + m] = v > 0.0f ? v : 0.0f;
                 }
+    }
+}
+
+// k_trunk_quad: k_trunk's layers (Winograd conv2) with conv3 and conv4 over the row tiles the workgroup's four boards share (conv_quad).
+// Built for the 8x8 and 7x6 planes; launch_trunk runs it where trunk_quad says so, and az_net_stage_kernel reports it as k_trunk, the
+// one-wave-per-board trunk it is.  Load, conv1 and conv2 stay per board in the wave's own LDS region.  conv3 then reads the planes
+// across waves: workgroup barrier (conv2 of every board is in LDS), compute, barrier (every wave has finished reading), store in place,
+// barrier -- k_trunk_q's scheme -- and conv4 follows from the shared planes.  Every wave of a workgroup that holds a board reaches each
+// of the three barriers exactly once: a wave without a board (the last workgroup, or beyond dyn_count) skips the per-board phases only
+// and still computes its share of the tiles, which read valid boards' planes alone.  A workgroup wholly beyond the row count leaves
+// before the first barrier.  Sharing the tiles of conv1 / the direct conv2 as well (6x6: 9 for 12) needs three more barriers and
+// measured slower.
+template <int CH, int CW>
+__global__ __launch_bounds__(256, 2) void k_trunk_quad(const float *__restrict__ in, int B, const int *__restrict__ dyn_count, TrunkParams tp, float *__restrict__ feat) {
+    using G = TrunkGeom<CH, CW>;
+    if (dyn_count) { int c = *dyn_count; B = c < B ? c : B; }  // rows actually filled this step
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + wave;
+    if ((int)blockIdx.x * 4 >= B) return;  // the whole workgroup (B and blockIdx.x are uniform): no barrier is left behind
+    const bool has = b < B;  // a wave without a board takes part in the shared layers and in every barrier
+    const int nb = B - (int)blockIdx.x * 4 < 4 ? B - (int)blockIdx.x * 4 : 4;  // boards of this workgroup
+    const int nt = wave >> 1, par = (wave & 1) ^ (__builtin_popcount(blockIdx.x) & 1);  // the wave's share of a shared layer (conv_quad)
+    float *inp = smem + wave * G::WAVE_FLOATS;
+    float *act = inp + G::INP;
+    float *act0 = smem + G::INP;  // board 0's planes: board d's are d * WAVE_FLOATS behind
+    if (has) {
+        for (int i = lane; i < G::INP; i += 64) inp[i] = 0.0f;
+        if (lane < NCH) act[lane * G::PS + G::P1] = 0.0f;  // every plane's zero slot: where the Winograd patches read outside the plane
+        LDS_FENCE();
+        for (int p = lane; p < G::P1; p += 64) inp[(p / CW + 1) * G::PW + (p % CW) + 1] = in[(size_t)b * G::P1 + p];
+        LDS_FENCE();
+    }
+    if (has) {  // conv1 1->32, pad 1 (othello.py:370) as a K = 12 MFMA product: taps 0..8, taps 9..11 carry zero weights
+        f32x4 acc[G::MT2][2];
+        const int m_lane = lane & 15, kq = lane >> 4;
+        const float bv0 = tp.b1[m_lane], bv1 = tp.b1[16 + m_lane];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            int tap = 4 * s + kq;
+            tap = tap < 9 ? tap : 8;  // finite operand for the zero-weight columns
+            const int toff = (tap / 3) * G::PW + tap % 3;
+            const float b0 = tp.w1f[(s * 2 + 0) * 64 + lane], b1 = tp.w1f[(s * 2 + 1) * 64 + lane];
+#pragma unroll
+            for (int mt = 0; mt < G::MT2; ++mt) {
+                int p = 16 * mt + m_lane;
+                p = p < G::P1 ? p : G::P1 - 1;
+                const float a = inp[(p / CW) * G::PW + (p % CW) + toff];
+                if (s == 0) { acc[mt][0] = (f32x4){bv0, bv0, bv0, bv0}; acc[mt][1] = (f32x4){bv1, bv1, bv1, bv1}; }
+                acc[mt][0] = MFMA(a, b0, acc[mt][0]);
+                acc[mt][1] = MFMA(a, b1, acc[mt][1]);
+            }
+        }
+        store_relu_lds<G::P1, G::PS, G::MT2>(act, lane, acc);
+        LDS_FENCE();
+    }
+    if (has) {  // conv2 32->32, pad 1 (othello.py:371), Winograd form
+        conv2_wino<CH, CW, G::PS, 3>(act, reinterpret_cast<const float4 *>(tp.wu), tp.cb[0], lane);
+        LDS_FENCE();
+    }
+    __syncthreads();  // conv2 of every board is in LDS
+    {  // conv3 32->32, valid (othello.py:372)
+        f32x4 acc[((4 * G::P3 + 15) / 16 + 1) / 2];
+        const int nu = conv_quad_deal<G::P3, G::W3, CW, G::PS, G::WAVE_FLOATS>(act0, tp.wq[1], tp.cb[1], lane, nt, par, nb * G::P3, acc);
+        __syncthreads();  // every wave has finished reading the conv2 planes
+        store_quad_relu<G::P3, G::PS, G::WAVE_FLOATS>(act0, lane, nt, par, nu, nb * G::P3, acc);
+    }
+    __syncthreads();  // conv3 of every board is in LDS
+    {  // conv4 32->32, valid (othello.py:373) -> flattened NCHW features (othello.py:374) of boards 4 blockIdx.x .. + nb - 1
+        f32x4 acc[((4 * G::P4 + 15) / 16 + 1) / 2];
+        const int nu = conv_quad_deal<G::P4, G::W4, G::W3, G::PS, G::WAVE_FLOATS>(act0, tp.wq[2], tp.cb[2], lane, nt, par, nb * G::P4, acc);
+        store_quad_relu<G::P4, G::P4, NCH * G::P4>(feat + (size_t)blockIdx.x * 4 * (NCH * G::P4), lane, nt, par, nu, nb * G::P4, acc);
     }
 }
 
@@ -3317,6 +3490,19 @@ static int beside_tile() { static int v = -2; if (v == -2) v = beside_env("AZ_BE
 
 static bool trunk_v1() { static int v = -1; if (v < 0) { const char *e = getenv("AZ_TRUNK_V1"); v = (e && atoi(e)) ? 1 : 0; } return v == 1; }
 
+// Which form of k_trunk a launch runs: its workgroup's four boards sharing row tiles (QUAD) or every board its own tiles.  The QUAD
+// form exists for the Winograd 8x8 and 7x6 kernels, the planes it was measured on: 7x6 gains alone (4095 boards:
+// 51.6 vs 55.7 us) and beside another chain; 8x8 gains beside another chain (the headline's two groups) and loses ~1 us alone.
+// AZ_TRUNK_QUAD=1 / 0 forces one form on those two kernels for A/B runs; every other k_trunk keeps its own tiles.
+static int trunk_quad_env() { static int v = -2; if (v == -2) { const char *e = getenv("AZ_TRUNK_QUAD"); v = e ? (atoi(e) ? 1 : 0) : -1; } return v; }
+template <int CH, int CW, bool WINO>
+constexpr bool trunk_has_quad() { return WINO && ((CH == 8 && CW == 8) || (CH == 7 && CW == 6)); }
+template <int CH, int CW>
+static bool trunk_quad() {
+    if (trunk_quad_env() >= 0) return trunk_quad_env() == 1;
+    return (CH == 7 && CW == 6) || g_beside;
+}
+
 // boards up to which the trunk runs four waves per board (AZ_TRUNK_Q_MAX; 0: never)
 static int trunk_q_max() { static int v = -1; if (v < 0) { const char *e = getenv("AZ_TRUNK_Q_MAX"); v = e ? atoi(e) : 512; } return v; }
 
@@ -3346,7 +3532,15 @@ static int launch_trunk(az_net *n, const float *in, int B, const int *dyn, hipSt
         int want = e ? atoi(e) : 3;
         if (want >= 1 && want <= 8 && 160 * 1024 / want > G::LDS_BYTES) lds_bytes = (160 * 1024 / want) & ~15;
         AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk<CH, CW, WINO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        if constexpr (trunk_has_quad<CH, CW, WINO>())
+            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
         attr_set = true;
+    }
+    if constexpr (trunk_has_quad<CH, CW, WINO>()) {
+        if (trunk_quad<CH, CW>()) {
+            AZ_LAUNCH((k_trunk_quad<CH, CW>), dim3((B + 3) / 4), dim3(256), lds_bytes, st, in, B, dyn, n->tp, n->feat);
+            return AZ_OK;
+        }
     }
     AZ_LAUNCH((k_trunk<CH, CW, WINO>), dim3((B + 3) / 4), dim3(256), lds_bytes, st, in, B, dyn, n->tp, n->feat);
     return AZ_OK;
