@@ -2881,6 +2881,7 @@ struct az_net {
     struct Acts { float *feat, *h1, *h2; };
     std::vector<Acts> lanes;
     int lane_rows = 0;
+    int mlp_lanes = 1;  // the TicTacToe MLP: the lanes az_net_set_lanes has named (k_mlp keeps no activation rows to give them)
     // exact block-fixed-point dense layers (AZ_DENSE_I8=1, OthelloNet): digit planes + exponents of the two weight matrices and of the
     // activation rows (one buffer, used by fc1 and then by fc2)
     bool qd_on = false;
@@ -3935,10 +3936,12 @@ static int forward_lane0(az_net *n, const float *d_input, int B, const int *dyn,
 // the forward on the activation rows of `lane`; beside: see g_beside
 static int forward_impl(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream, int lane = 0, int beside = 0) {
     AZ_REQUIRE(n && d_input && d_probs && d_value, AZ_EINVAL, "null argument");
-    AZ_REQUIRE(lane >= 0 && lane <= (int)n->lanes.size(), AZ_EINVAL, "lane %d of %d (az_net_set_lanes)", lane, (int)n->lanes.size() + 1);
-    AZ_REQUIRE(lane == 0 || B <= n->lane_rows, AZ_EINVAL, "batch %d beyond the %d rows of lane %d", B, n->lane_rows, lane);
+    const bool mlp = n->game == AZ_TICTACTOE;  // no activation rows: a lane is a name only
+    const int n_lanes = mlp ? n->mlp_lanes : (int)n->lanes.size() + 1;
+    AZ_REQUIRE(lane >= 0 && lane < n_lanes, AZ_EINVAL, "lane %d of %d (az_net_set_lanes)", lane, n_lanes);
+    AZ_REQUIRE(lane == 0 || mlp || B <= n->lane_rows, AZ_EINVAL, "batch %d beyond the %d rows of lane %d", B, n->lane_rows, lane);
     const az_net::Acts own = {n->feat, n->h1, n->h2};
-    if (lane > 0) { const az_net::Acts &a = n->lanes[lane - 1]; n->feat = a.feat; n->h1 = a.h1; n->h2 = a.h2; }
+    if (lane > 0 && !mlp) { const az_net::Acts &a = n->lanes[lane - 1]; n->feat = a.feat; n->h1 = a.h1; n->h2 = a.h2; }
     g_beside = beside;
     const int rc = forward_lane0(n, d_input, B, dyn, d_probs, d_value, stream);
     g_beside = 0;
@@ -3997,7 +4000,11 @@ extern "C" int az_net_set_lanes(az_net *n, int n_lanes, int rows) {
     AZ_REQUIRE(n_lanes >= 1 && n_lanes <= AZ_MAX_GROUPS, AZ_EINVAL, "az_net_set_lanes: %d lanes outside [1, %d]", n_lanes, AZ_MAX_GROUPS);
     AZ_REQUIRE(rows > 0 && rows <= n->max_batch, AZ_EINVAL, "az_net_set_lanes: %d rows outside (0, max_batch=%d]", rows, n->max_batch);
     AZ_REQUIRE(n_lanes == 1 || !n->qd_on, AZ_EINVAL, "az_net_set_lanes: the fixed-point dense layers (AZ_DENSE_I8) keep one set of digit planes");
-    if (n->game == AZ_TICTACTOE || n_lanes == 1) return AZ_OK;  // the MLP keeps no activation in memory
+    if (n->game == AZ_TICTACTOE) {  // the MLP keeps no activation in memory: only the count is recorded (lanes never go away)
+        n->mlp_lanes = n_lanes > n->mlp_lanes ? n_lanes : n->mlp_lanes;
+        return AZ_OK;
+    }
+    if (n_lanes == 1) return AZ_OK;
     AZ_HIP(hipDeviceSynchronize());  // a lane's rows may be replaced: no forward may be in flight
     if (rows > n->lane_rows) n->lanes.clear();  // the smaller rows stay in n->allocs until the net goes
     const int want_rows = rows > n->lane_rows ? rows : n->lane_rows;

@@ -98,6 +98,7 @@ int az_net_forward_dyn(az_net *net, const float *d_input, const int32_t *d_count
  * would overwrite each other.  az_net_set_lanes(net, n, rows) gives lanes 1 .. n - 1 activation rows of their own, `rows` each
  * (lane 0 is the net's own set, max_batch rows); it only grows, and waits for the device before it returns.  n in [1, 4];
  * AZ_EINVAL: n outside that, rows outside (0, max_batch], n > 1 on a net under AZ_DENSE_I8 (its digit planes are one set).
+ * The TicTacToe MLP keeps no activation in memory: its lanes are names, only their count is recorded.
  * az_net_forward_lane is az_net_forward_dyn on the activation rows of `lane` (lane 0: exactly az_net_forward_dyn); forwards of
  * different lanes may be in flight together on different streams, issued from one host thread.  beside != 0 says that the
  * forward runs next to another one: the size thresholds that pick a layer's kernel were measured with the chip to itself, and
