@@ -133,7 +133,7 @@ AZ_D double az_det_pow(double n, double inv_temp) {
 
 struct Philox4 { u32 x, y, z, w; };
 
-AZ_D Philox4 az_philox(u32 k0, u32 k1, u32 c0, u32 c1, u32 c2, u32 c3) {
+AZ_HD Philox4 az_philox(u32 k0, u32 k1, u32 c0, u32 c1, u32 c2, u32 c3) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         u64 p0 = (u64)0xD2511F53u * c0;
@@ -149,7 +149,7 @@ AZ_D Philox4 az_philox(u32 k0, u32 k1, u32 c0, u32 c1, u32 c2, u32 c3) {
     return o;
 }
 
-AZ_D double az_u53(u32 a, u32 b) {
+AZ_HD double az_u53(u32 a, u32 b) {
     return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
 }
 

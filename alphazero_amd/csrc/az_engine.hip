@@ -4,6 +4,8 @@
 // batch for the policy-value network.  Every tree still sees strictly sequential simulations, so
 // per-game semantics equal the reference's MCT.search (mcts.py:226-269) exactly -- no virtual loss.  (Opt-in, default off:
 // az_engine_set_leaf_batch walks K simulations per game and lock-step with virtual loss -- k_step_multi below, another search.)
+// (Opt-in, default off: az_engine_set_playout_cap searches most plies with a few simulations and records the fully searched ones only --
+// k_step_cap below, k_step with a per-slot simulation budget.)
 // (Opt-in, default off: az_engine_set_gumbel replaces the root's PUCT pick by Sequential Halving over actions sampled with Gumbel
 // noise and reads the root out by the completed Q-values -- k_step_gumbel below, another search again; az_engine_set_gumbel_batch
 // walks up to K simulations of a Sequential Halving phase per game and lock-step -- k_step_gumbel_multi.)
@@ -56,7 +58,9 @@
 #define LPG 16          // lanes per game
 #define GPB (256 / LPG) // games per 256-thread block
 
-enum { CTR_SAMPLES = 0, CTR_GAMES_DONE, CTR_NET_EVALS, CTR_NEXT_GAME, CTR_TOTAL_GAMES, CTR_FIRST_ID, CTR_PLIES, CTR_COUNT };
+enum { CTR_SAMPLES = 0, CTR_GAMES_DONE, CTR_NET_EVALS, CTR_NEXT_GAME, CTR_TOTAL_GAMES, CTR_FIRST_ID, CTR_PLIES,
+       CTR_FULL_PLIES, CTR_FAST_PLIES,  // az_engine_set_playout_cap: the plies k_move played after a full / a fast search (counted while the mode is on)
+       CTR_COUNT };
 // entries beyond CTR_COUNT live as long as the engine (k_reset_all clears [0, CTR_COUNT) only)
 enum { CTR_COLLISIONS = CTR_COUNT, CTR_ALLOC };
 #define MLB AZ_MAX_LEAF_BATCH  // walkers per slot and lock-step: one per lane of the game's group
@@ -112,7 +116,14 @@ struct EngDev {
     // az_engine_set_gumbel_full: the network value of every evaluated node, [G][2][C] like nodes, in the frame of the player to move at
     // the node.  Null unless the switch is in force (on, and the Gumbel mode on): then no kernel touches it.
     float *nval;
+    // az_engine_set_playout_cap (k_step_cap): cap_nfast = the simulations of a fast ply (0: off), cap_pfull = the share of full plies;
+    // budget [G] = the simulations the slot walks in a search call, written by k_root_prep from the coin of the slot's (game id, ply):
+    // CAP_FULL for a full ply, cap_nfast for a fast one.  Null unless the mode is on: then no kernel touches it.
+    int cap_nfast;
+    double cap_pfull;
+    int *budget;
 };
+#define CAP_FULL 0x7fffffff  // the budget of a full ply: every simulation of any search call, and the mark root noise asks for
 
 // ---------------------------------------------------------------------------------------------
 // node access (two 16-byte transactions) and 16-lane group primitives
@@ -544,10 +555,21 @@ __global__ void k_reset_all(EngDev E, u32 first_id, int n_games) {
     else { E.active[g] = 0; E.leaf_status[g] = LS_NONE; }
 }
 
+// Playout cap randomization (az_engine_set_playout_cap): the coin of (game id, ply).  The same arithmetic on the host
+// (az_playout_cap_full) and in the two kernels that draw it: k_root_prep for the search budget, k_move for the record.
+#define AZ_P_PLAYOUT_CAP 10
+AZ_HD bool playout_cap_full(u32 seed, u32 gid, int ply, double p_full) {
+    const Philox4 r = az_philox(seed, gid, (u32)ply, 0xFFFFu, AZ_P_PLAYOUT_CAP, 0);
+    return az_u53(r.x, r.y) < p_full;
+}
+
 // mcts.py:231-233 : a root without priors is evaluated first (value discarded)
+// (no barrier in here: a group leaves as a whole, and the rows are drawn per group)
 __global__ __launch_bounds__(256) void k_root_prep(EngDev E, int g0, int g1) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     if (g >= g1) return;
+    // the playout cap's budget of this search call, once per slot and ply: one Philox draw on the group's first lane
+    if (E.budget && sub == 0) E.budget[g] = playout_cap_full(E.seed, E.game_id[g], E.ply[g], E.cap_pfull) ? CAP_FULL : E.cap_nfast;
     uint8_t fresh = 0;
     if (searches(E, g)) {
         uint8_t f = pool_of(E, g)[E.root[g]].flags;
@@ -587,8 +609,12 @@ __device__ unsigned long long az_step_probe[4096 * 8];
 //            leaf selected in the previous step, whose policy/value the network has just produced
 //   SELECT : root noise (mcts.py:235-240) + select_node (mcts.py:127-171) of simulation `sim`,
 //            writing the next leaf's canonical board into the network's input batch
-template <bool BACKUP, bool SELECT>
-__global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1) {
+// CAP (az_engine_set_playout_cap, k_step_cap): the slot walks the simulations sim < budget[g] of the search call only (k_root_prep
+// wrote the budget: CAP_FULL on a full ply, n_fast on a fast one) and takes root noise on a full ply only.  A slot past its budget
+// stays an inert group for the SELECT half -- no walk, no row, leaf_status LS_NONE, so the next BACKUP does nothing for it -- and
+// still reaches every barrier of alloc_rows_block; it is NOT deactivated.  CAP false is the kernel as it always was.
+template <bool BACKUP, bool SELECT, bool CAP>
+AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
     // previous step's network kernels, which have completed) is cleared for the next step
@@ -620,6 +646,7 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
     const int ply = E.ply[gs];
     BB b = {E.root_p1[gs], E.root_m1[gs], E.root_player[gs]};
     int node = E.root[gs];
+    const int budget = CAP ? E.budget[gs] : CAP_FULL;  // with the loads above: no round trip of its own
     Node fwd;
     bool have_root = false;
     PSTAMP(1)
@@ -663,9 +690,11 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
     // From here on no group may leave early: the leaf rows are handed out per block (alloc_rows_block) behind workgroup barriers.
     int status = LS_NONE, w = 0;
     Walk wk = {b, Node(), node, 1, sub == 0 ? node : -1, false};
-    if (active) {
+    const bool walks = active && (!CAP || sim < budget);  // uniform over the game's group
+    if (walks) {
         if (have_root) wk.cur = fwd; else wk.cur = load_node(pool + node);
-        if (E.noise_mode != AZ_NOISE_OFF && E.alpha >= 0.0 && E.eps >= 0.0 && (wk.cur.flags & F_EXPANDED) && !(wk.cur.flags & F_NOISED)) {
+        const bool noise_ply = !CAP || budget == CAP_FULL;  // a fast ply takes no root noise and leaves F_NOISED clear
+        if (noise_ply && E.noise_mode != AZ_NOISE_OFF && E.alpha >= 0.0 && E.eps >= 0.0 && (wk.cur.flags & F_EXPANDED) && !(wk.cur.flags & F_NOISED)) {
             apply_root_noise_grp(E, g, pool, node, wk.cur, b, ply, sim, sub);
             wk.cur.flags |= F_NOISED;
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -684,7 +713,7 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
         if (sub == 0) E.row_of_slot[g] = row;
     }
     if (sub == 0 && in_range) {
-        if (active) {
+        if (walks) {
             E.leaf[g] = wk.node; E.leaf_p1[g] = wk.b.p1; E.leaf_m1[g] = wk.b.m1; E.leaf_player[g] = (int8_t)wk.b.player;
             E.leaf_winner[g] = (int8_t)w;
         }
@@ -699,6 +728,12 @@ __global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1)
     }
 #endif
 }
+
+// the plain search's lock-step, under the name and with the code it always had, and the playout cap's
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, false>(E, sim, g0, g1); }
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_cap(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, true>(E, sim, g0, g1); }
 
 // One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
 // SELECT of kt walkers.  Lane j of the game's group owns walker j's pending words (loaded / stored coalesced, handed round by
@@ -1552,8 +1587,13 @@ __global__ void k_move(EngDev E, int g0, int g1) {
     if (nc == 0 || !(pool[root].flags & F_EXPANDED)) { atomicOr(E.err, ERR_INTERNAL); E.active[g] = 0; return; }
     double temp = linear_temp(ply, E.tmax, E.tmin);
 
-    long long si = (long long)atomicAdd(&E.ctr[CTR_SAMPLES], 1ULL);
-    if (si >= E.sample_cap) { atomicOr(E.err, ERR_SAMPLE_CAP); si = -1; }
+    // az_engine_set_playout_cap: a fast ply plays its move like any other and records no sample (samp_idx -1, as the z patch expects)
+    const bool fast = E.cap_nfast > 0 && !playout_cap_full(E.seed, gid, ply, E.cap_pfull);
+    long long si = -1;
+    if (!fast) {
+        si = (long long)atomicAdd(&E.ctr[CTR_SAMPLES], 1ULL);
+        if (si >= E.sample_cap) { atomicOr(E.err, ERR_SAMPLE_CAP); si = -1; }
+    }
     if (ply >= E.max_plies) { atomicOr(E.err, ERR_PLY_CAP); E.active[g] = 0; return; }
     E.samp_idx[(size_t)g * E.max_plies + ply] = (int)si;
     float *pi = si >= 0 ? E.o_pi + (size_t)si * E.A : nullptr;
@@ -1578,6 +1618,7 @@ __global__ void k_move(EngDev E, int g0, int g1) {
     pool[chosen].parent = -1;  // mcts.py:121-123
     E.ply[g] = ply + 1;
     atomicAdd(&E.ctr[CTR_PLIES], 1ULL);
+    if (E.cap_nfast > 0) atomicAdd(&E.ctr[fast ? CTR_FAST_PLIES : CTR_FULL_PLIES], 1ULL);
     atomicAdd(&E.ctr[CTR_NET_EVALS], (unsigned long long)E.evals[g]);
     E.evals[g] = 0;
     atomicMax(E.max_nodes, E.n_nodes[g]);
@@ -2054,6 +2095,9 @@ struct az_engine {
     float *nval = nullptr;
     // az_engine_set_groups: the request (0: auto) and whether AZ_ENGINE_GROUPS made it; the later groups' streams (group 0 runs on
     // `stream`), made at the first grouped run; the event that orders them behind `stream`
+    // az_engine_set_playout_cap: the per-slot budgets, [G], allocated when the mode first goes on; in force (d.budget == cap_budget,
+    // d.cap_nfast > 0) only while it is on, else d.budget is null
+    int *cap_budget = nullptr;
     int groups_req = 0;
     bool groups_env = false;
     hipStream_t gstream[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2149,6 +2193,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.K = 1; e->net_rows = d.G;
     d.gm = 0; d.g_cvisit = 0.0; d.g_cscale = 0.0; d.g_scale = 0.0;
     d.nval = nullptr;
+    d.cap_nfast = 0; d.cap_pfull = 1.0; d.budget = nullptr;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2343,6 +2388,16 @@ static int enqueue_search(az_engine *e, const Chain &c, int n_sim, int cap) {
         return AZ_OK;
     }
 #undef GUMBEL_LAUNCH
+    if (d.budget) {  // the playout cap: k_step's launch sequence with k_step_cap (a slot past its budget idles: no walk, no row)
+        for (int s = 0; s < n_sim; ++s) {
+            if (s == 0) hipLaunchKernelGGL((k_step_cap<false, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step_cap<true, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
+            AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
+        }
+        hipLaunchKernelGGL((k_step_cap<true, false>), gg, gb, 0, c.st, d, n_sim, c.g0, c.g1);
+        AZ_HIP(hipGetLastError());
+        return AZ_OK;
+    }
     for (int s = 0; s < n_sim; ++s) {
         if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
         else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
@@ -2379,8 +2434,9 @@ static int do_search(az_engine *e, int n_sim, const Chain *grp = nullptr) {
     if (!graphable) return enqueue_search(e, c, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
     cap = cap_q;
     // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31).  A change
-    // of K (either setter) drops every graph.  The full Gumbel kernels are other kernels again (bit 31; cap < 2^31).
-    const az_engine::GraphKey key(((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)n_sim << 32) |
+    // of K (either setter) drops every graph.  The full Gumbel kernels are other kernels again (bit 31; cap < 2^31), and so are the
+    // playout cap's (bit 62; its n_fast and p_full travel in the launch arguments: the setter drops every graph when they change).
+    const az_engine::GraphKey key(((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)(d.budget != nullptr) << 62) | ((unsigned long long)n_sim << 32) |
                                       ((unsigned long long)(d.nval != nullptr) << 31) | (unsigned)cap,
                                   ((unsigned long long)c.g0 << 32) | (unsigned)c.g1);
     auto it = e->graphs.find(key);
@@ -3020,6 +3076,7 @@ extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
     AZ_REQUIRE(mask == 0 || e->symr_mask == 0, AZ_EINVAL, "az_engine_set_symmetry: the engine draws one symmetry per evaluation (az_engine_set_symmetry_random, mask 0x%x); switch that mode off first", (unsigned)e->symr_mask);
     AZ_REQUIRE(mask == 0 || e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with leaf_batch %d > 1 (az_engine_set_leaf_batch)", e->leaf_batch);
     AZ_REQUIRE(mask == 0 || e->gumbel_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with gumbel_batch %d > 1 (az_engine_set_gumbel_batch)", e->gumbel_batch);
+    AZ_REQUIRE(mask == 0 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_symmetry: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the plain search only; switch it off first", d.cap_nfast);
     AZ_REQUIRE((long long)n * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "%d symmetries of %d slots are %lld rows, the network's max_batch is %d", n, d.G, (long long)n * d.G, az_net_max_batch(e->net));
     if (mask == e->sym_mask) return AZ_OK;
@@ -3042,6 +3099,7 @@ extern "C" int az_engine_set_symmetry_random(az_engine *e, int32_t mask) {
     int n = 0;
     AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
     AZ_REQUIRE(mask == 0 || e->sym_mask == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the engine averages over a symmetry mask (az_engine_set_symmetry, mask 0x%x); switch the ensemble off first", (unsigned)e->sym_mask);
+    AZ_REQUIRE(mask == 0 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the plain search only; switch it off first", d.cap_nfast);
     AZ_REQUIRE((long long)d.K * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", d.K, d.G, (long long)d.K * d.G, az_net_max_batch(e->net));
     if (mask == e->symr_mask) return AZ_OK;
@@ -3100,6 +3158,7 @@ extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_ROLLOUT, AZ_EINVAL, "az_engine_set_leaf_batch: a rollout engine (AZ_EVAL_ROLLOUT) evaluates no leaf with a network");
     AZ_REQUIRE(e->sym_mask == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the engine evaluates over a symmetry mask (0x%x); the ensemble does not combine with leaf_batch", e->sym_mask);
     AZ_REQUIRE(k == 1 || d.gm == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the Gumbel root search is on (az_engine_set_gumbel, m = %d) and searches one leaf per lock-step; switch it off first", d.gm);
+    AZ_REQUIRE(k == 1 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served at one leaf per lock-step only; switch it off first", d.cap_nfast);
     const long long rows = (long long)k * d.G;
     if (e->cfg.evaluator == AZ_EVAL_NET)
         AZ_REQUIRE(rows <= az_net_max_batch(e->net), AZ_EINVAL, "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", k, d.G,
@@ -3158,6 +3217,7 @@ extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, dou
         AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_ROLLOUT, AZ_EINVAL, "az_engine_set_gumbel: a rollout engine (AZ_EVAL_ROLLOUT) has no priors to sample the root's actions from");
         AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_gumbel: an AZ_EVAL_EXTERNAL engine searches with the PUCT root only");
         AZ_REQUIRE(e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_gumbel: leaf_batch %d > 1 is in force (az_engine_set_leaf_batch); the Gumbel root search takes one leaf per lock-step", e->leaf_batch);
+        AZ_REQUIRE(d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_gumbel: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the PUCT search only; switch it off first", d.cap_nfast);
     }
     if (m > 0 && e->gumbel_batch > 1 && e->cfg.evaluator == AZ_EVAL_NET)
         AZ_REQUIRE((long long)e->gumbel_batch * d.G <= az_net_max_batch(e->net), AZ_EINVAL, "az_engine_set_gumbel: gumbel_batch %d of %d slots are %lld rows, the network's max_batch is %d",
@@ -3255,4 +3315,55 @@ extern "C" int az_engine_root_value(az_engine *e, int32_t slot, float *v) {
     AZ_REQUIRE(active && (rn.flags & F_EVALUATED), AZ_ESTATE, "az_engine_root_value: the root of slot %d has not been evaluated (or the slot holds no game)", slot);
     AZ_HIP(hipMemcpy(v, d.nval + at, sizeof(float), hipMemcpyDeviceToHost));
     return AZ_OK;
+}
+
+// ---- playout cap randomization (k_step_cap, k_root_prep, k_move) -----------------------------------------------
+// the mode of this engine that the playout cap is not served in, or null (the style of groups_unserved)
+static const char *cap_unserved(const az_engine *e) {
+    if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return "an AZ_EVAL_EXTERNAL engine (external evaluator)";
+    if (e->cfg.evaluator == AZ_EVAL_ROLLOUT) return "a rollout engine (AZ_EVAL_ROLLOUT)";
+    if (e->sym_mask != 0) return "the symmetry ensemble (az_engine_set_symmetry)";
+    if (e->symr_mask != 0) return "the random symmetry mode (az_engine_set_symmetry_random)";
+    if (e->leaf_batch > 1) return "leaf_batch > 1 (az_engine_set_leaf_batch)";
+    if (e->d.gm > 0) return "the Gumbel search (az_engine_set_gumbel)";
+    return nullptr;
+}
+
+extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_playout_cap");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_playout_cap");
+    EngDev &d = e->d;
+    if (n_fast == 0) {  // off: p_full is not looked at
+        if (d.cap_nfast == 0) return AZ_OK;
+    } else {
+        AZ_REQUIRE(n_fast >= 1 && n_fast < e->cfg.n_sim, AZ_EINVAL, "az_engine_set_playout_cap: n_fast must be in [1, n_sim = %d) (0 = off), got %d", e->cfg.n_sim, n_fast);
+        AZ_REQUIRE(p_full > 0.0 && p_full <= 1.0, AZ_EINVAL, "az_engine_set_playout_cap: p_full must be in (0, 1], got %g", p_full);
+        const char *why = cap_unserved(e);
+        AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_playout_cap: the playout cap is not served for %s", why);
+        if (n_fast == d.cap_nfast && p_full == d.cap_pfull) return AZ_OK;
+    }
+    AZ_TRY(enter(e));
+    if (n_fast > 0 && !e->cap_budget) AZ_TRY(dev_alloc(e, &e->cap_budget, (size_t)d.G));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    d.cap_nfast = n_fast; d.cap_pfull = n_fast > 0 ? p_full : 1.0;
+    d.budget = n_fast > 0 ? e->cap_budget : nullptr;
+    // other kernels, and n_fast / p_full are launch arguments: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_playout_cap_stats(az_engine *e, int64_t *full_plies, int64_t *fast_plies) {
+    AZ_REQUIRE(e && full_plies && fast_plies, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_playout_cap_stats");
+    AZ_USABLE(e, "az_engine_playout_cap_stats");
+    AZ_TRY(enter(e));
+    AZ_TRY(fetch_counters(e));
+    *full_plies = (int64_t)e->h_ctr[CTR_FULL_PLIES];
+    *fast_plies = (int64_t)e->h_ctr[CTR_FAST_PLIES];
+    return AZ_OK;
+}
+
+extern "C" int az_playout_cap_full(uint32_t seed, uint32_t game_id, int32_t ply, double p_full) {
+    return playout_cap_full(seed, game_id, ply, p_full) ? 1 : 0;
 }

@@ -379,6 +379,27 @@ class SelfPlayEngine:
         check(lib().az_engine_collisions(self.h, C.byref(n)))
         return n.value
 
+    def set_playout_cap(self, cap):
+        """playout cap randomization (az_engine_set_playout_cap): None = off, or (n_fast, p_full) -- a ply is searched
+        in full (n_sim simulations, root noise, recorded) with probability p_full and fast otherwise (n_fast simulations, no noise,
+        played but not recorded), by a coin of (seed, game id, ply).  Plain search of EVAL_NET / EVAL_FAKE engines; any other mode
+        is a ValueError that names it."""
+        from .playout_cap import parse
+        cap = parse(cap)
+        check(lib().az_engine_set_playout_cap(self.h, *((0, 1.0) if cap is None else cap)))
+
+    def playout_cap_stats(self):
+        """{"full_plies", "fast_plies"}: the plies played after a full / a fast search since the last run() / set_roots(), counted
+        while the playout cap is on (both 0 with it off)"""
+        full, fast = C.c_int64(), C.c_int64()
+        check(lib().az_engine_playout_cap_stats(self.h, C.byref(full), C.byref(fast)))
+        return {"full_plies": full.value, "fast_plies": fast.value}
+
+    @staticmethod
+    def playout_cap_full(seed, game_id, ply, p_full):
+        """the playout cap's coin of (seed, game id, ply): True = a full ply (az_playout_cap_full: host code, the kernels' arithmetic)"""
+        return bool(lib().az_playout_cap_full(int(seed) & 0xFFFFFFFF, int(game_id) & 0xFFFFFFFF, int(ply), float(p_full)))
+
     def set_gumbel(self, gumbel):
         """the Gumbel root search (az_engine_set_gumbel; alphazero_amd.gumbel.parse: None = off, an int m or a dict of m, c_visit,
         c_scale, gumbel_scale): Sequential Halving over m root actions sampled with Gumbel noise, the move and the policy target

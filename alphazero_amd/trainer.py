@@ -62,7 +62,8 @@ class AlphaZeroTrainer:
     DEFAULT_EXP_NAME = "alphazero-undefined"
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
-                 selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, eval_search=None, eval_opening_plies=None):
+                 selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, selfplay_playout_cap=None, eval_search=None,
+                 eval_opening_plies=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -100,6 +101,11 @@ class AlphaZeroTrainer:
         self.selfplay_gumbel_full = selfplay_gumbel_full
         from .gumbel import check_gumbel_full
         check_gumbel_full(selfplay_gumbel_full, selfplay_gumbel)
+        # playout cap randomization of that wave: None (off) or (n_fast, p_full) -- a ply is searched in full and
+        # recorded with probability p_full, else with n_fast simulations and only played.  The self-play engine alone: the arena's
+        # engines never take it.  The plain PUCT wave only: the engine serves it without the Gumbel search and the symmetry modes.
+        self.selfplay_playout_cap = selfplay_playout_cap
+        self._check_selfplay_playout_cap()
         # the search the evaluation arena plays with (BatchedArena's `search`): None (the visit-based PUCT arena), "selfplay" (the modes
         # of the self-play wave above) or a dict of arena.SEARCH_KEYS; it goes to player 1 and, with eval_opponent "previous", to the
         # opponent too.  eval_opening_plies: BatchedArena's `opening_plies`, the seeded opening that makes the rounds different games.
@@ -118,6 +124,17 @@ class AlphaZeroTrainer:
                     "gumbel_full": self.selfplay_gumbel_full}
         check_search(spec, nn, "eval_search")
         return spec
+
+    def _check_selfplay_playout_cap(self):
+        from .playout_cap import parse
+        cap = parse(self.selfplay_playout_cap, "selfplay_playout_cap")
+        if cap is not None and self.selfplay_gumbel is not None:
+            raise ValueError(f"selfplay_playout_cap={self.selfplay_playout_cap!r} does not combine with selfplay_gumbel={self.selfplay_gumbel!r}: "
+                             f"the playout cap is served in the plain PUCT search only")
+        if cap is not None and self.selfplay_symmetry is not None:
+            raise ValueError(f"selfplay_playout_cap={self.selfplay_playout_cap!r} does not combine with selfplay_symmetry={self.selfplay_symmetry!r}: "
+                             f"the playout cap is served in the plain PUCT search only")
+        return cap
 
     def _check_selfplay_symmetry(self):
         from .symmetry import parse
@@ -195,6 +212,7 @@ class AlphaZeroTrainer:
             raise ValueError("the batched engine needs config.simulations (compute_time-bounded search is host-only)")
         slots = max(1, min(self.engine_slots, c.episodes))
         sym = self._check_selfplay_symmetry()
+        cap = self._check_selfplay_playout_cap()
         from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full
         gb = check_gumbel_batch(self.selfplay_gumbel_batch, self.selfplay_gumbel)
         gf = check_gumbel_full(self.selfplay_gumbel_full, self.selfplay_gumbel)
@@ -227,6 +245,9 @@ class AlphaZeroTrainer:
                                           dirichlet_alpha=c.dirichlet_alpha, dirichlet_epsilon=c.dirichlet_epsilon,
                                           temp_max_step=tmax, temp_min_step=tmin, seed=self.seed, max_plies=plies,
                                           sample_capacity=c.episodes * plies, evaluator=EVAL_EXTERNAL if external else EVAL_NET)
+        if cap is None and getattr(self._engine, "_playout_cap", None) is not None:  # off before the modes it excludes come on
+            self._engine.set_playout_cap(None)
+            self._engine._playout_cap = None
         if external:  # a fresh evaluator for the network of this wave (update_network replaces self.nn)
             self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
         elif sym is not None or self._engine._sym_mode is not None:
@@ -244,6 +265,9 @@ class AlphaZeroTrainer:
         if gf != getattr(self._engine, "_gumbel_full", False):  # every game of the last wave is over: no active slot holds a tree
             self._engine.set_gumbel_full(gf)
             self._engine._gumbel_full = gf
+        if cap != getattr(self._engine, "_playout_cap", None):  # ValueError for a network routed to the external evaluator, n_fast >= simulations
+            self._engine.set_playout_cap(cap)
+            self._engine._playout_cap = cap
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

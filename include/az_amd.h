@@ -426,6 +426,39 @@ int az_gumbel_locksteps(int32_t n_sim, int32_t m, int32_t k);
 int az_engine_set_gumbel_full(az_engine *e, int32_t on);
 int az_engine_root_value(az_engine *e, int32_t slot, float *v);
 
+/* Playout cap randomization (KataGo: Wu 2019, "Accelerating Self-Play Learning in Go", section 3.1): most plies of a self-play game are
+ * searched with a few simulations and only played, a share p_full of them is searched in full and recorded, so that games -- and
+ * with them independent value targets -- get cheaper while every recorded policy target comes from a full search.  The reference has
+ * no counterpart: it spends config.simulations on every ply (trainer.py:215-273).  Opt-in: n_fast = 0 (the default) is off, when no
+ * launch, kernel, allocation or output bit differs from an engine that never had it on; p_full is then not looked at.  On:
+ * n_fast in [1, cfg.n_sim), p_full in (0, 1].  Contract:
+ *   the coin of a ply   r = Philox4x32-10 keyed (seed, game_id) at counter (ply, 0xFFFF, AZ_P_PLAYOUT_CAP = 10, 0),
+ *                       u = the 53-bit uniform az_u53 of (r.x, r.y); the ply is FULL iff u < p_full (p_full = 1.0: every ply).
+ *                       One draw per (game id, ply): never a function of the slot, the slot group, the batch or the games resident.
+ *   full ply            exactly the search with the mode off: every simulation of the search call, root noise under the engine's
+ *                       noise mode, the sample recorded.
+ *   fast ply            in a search call of n simulations the slot takes part in the lock-steps of the local simulation indices
+ *                       s < min(n, n_fast) only (every search call on the root walks that budget again); after them it neither
+ *                       walks nor takes a network row, and the backup that follows does nothing for it.  No root noise is applied
+ *                       and the root is not marked as noised.  A fresh root is still evaluated in the root-prior pass.  The move is
+ *                       chosen and played as ever -- temperature schedule, the AZ_P_MOVE_SAMPLE / AZ_P_TIE_MOVE draws, re-rooting --
+ *                       but NO sample is recorded: `samples` does not grow, no pi / visits / state / meta row is written, and the
+ *                       end-of-game z patch skips the ply.  The tree under the played move is kept as on any ply: a full ply that
+ *                       follows inherits it (and applies its root noise on top).
+ *   counters            az_engine_stats.plies counts every ply; az_engine_playout_cap_stats reads the plies played after a full and
+ *                       after a fast search since the last az_engine_run / az_engine_set_roots, counted while the mode is on (both 0
+ *                       with it off).  After a run with the mode on: samples == full_plies, plies == full_plies + fast_plies.
+ * meta's move_idx stays the ply, so a game's samples have gaps.  A game still depends on (seed, game id, n_fast, p_full) only.
+ * Served: the plain search of AZ_EVAL_NET / AZ_EVAL_FAKE engines through az_engine_run (1, 2 or 4 slot groups), az_engine_search,
+ * _search_begin / _end and az_engine_advance.  Not served (AZ_EINVAL naming the mode; and while the cap is on the setters of those
+ * modes refuse, naming the cap): leaf_batch > 1, the Gumbel search, either symmetry mode, AZ_EVAL_ROLLOUT, AZ_EVAL_EXTERNAL.
+ * AZ_EINVAL also: n_fast outside [0, n_sim), p_full outside (0, 1] or not a number; AZ_ESTATE while a search is open.  A change of
+ * either value drops the cached search graphs.
+ * az_playout_cap_full: the coin as pure host code, 1 = full, 0 = fast; the arithmetic of the kernels (no engine, no GPU). */
+int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full);
+int az_engine_playout_cap_stats(az_engine *e, int64_t *full_plies, int64_t *fast_plies);
+int az_playout_cap_full(uint32_t seed, uint32_t game_id, int32_t ply, double p_full);
+
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
  * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves
