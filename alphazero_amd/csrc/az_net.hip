@@ -18,7 +18,8 @@
 //                    never leave the wave's private LDS region; weights stream from L2 already tiled in MFMA
 //                    B-fragment order (one coalesced dword per lane).  Batches from 4096 boards up.
 //   k_trunk<CH,CW> : the same layers, one wavefront per board on 16x16x4 MFMA: smaller batches.
-//   k_trunk_quad<CH,CW>: k_trunk with conv3 / conv4 over row tiles that the workgroup's four boards share (8x8, 7x6 planes).
+//   k_trunk_quad<CH,CW,FORM>: k_trunk with conv3 / conv4 over row tiles that the workgroup's four boards share (8x8, 7x6 planes);
+//                    FORM 1 / 2 run conv2 in four passes and fit four / three waves on a SIMD, beside another chain's kernels.
 //   k_gemm<...>    : LDS-tiled f32 MFMA GEMM with bias(+ReLU) epilogue for fc1 / fc2.
 //   k_heads        : policy+value GEMM (N padded to 16) fused with softmax / tanh.
 //   k_mlp          : the 316-parameter TicTacToe MLP, one thread per board.
@@ -179,10 +180,11 @@ AZ_D void store_relu_lds(float *out, int lane, const f32x4 (&acc)[MT][2]) {
 // Y[1][c] = (R[1][c]-R[2][c])-R[3][c], out = relu(Y + bias): one IEEE operation per step, in this order.
 // The output overwrites the input planes (all reads are done before the first write).
 // ---------------------------------------------------------------------------------------------
-template <int CH, int CW, int PS, int RING>
+template <int CH, int CW, int PS, int RING, int NP = 2>
 AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bias, int lane) {
     constexpr int TW = (CW + 1) / 2, NTL = ((CH + 1) / 2) * TW, P1 = CH * CW;
     static_assert(NTL <= 16 && PS > P1, "one 16-row tile of 2x2 output tiles per board; a zero slot behind every plane");
+    static_assert(NP == 2 || NP == 4, "two passes of two frequency rows or four passes of one");
     const int m = lane & 15, kq = lane >> 4;
     const int t = m < NTL ? m : NTL - 1;  // padding rows repeat the last tile (finite operands, never stored)
     const int ty = t / TW, tx = t % TW;
@@ -190,8 +192,98 @@ AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bi
     const float4 *ul = wu4 + lane;
     float cu[2][4][2], cw_[2][4][2];  // pass 0 -> pass 1: R[0][c] + R[1][c] and R[1][c] per (nt, r)
     float yo[2][4][2][2];             // Y[i][c] per (nt, r)
+    // NP = 4: one frequency ROW per pass -- 32 accumulator registers, two patch rows and two U float4 per k-step live instead of 64,
+    // three and four -- for the kernels that are to share a SIMD with another chain's waves (k_trunk_quad forms 1 and 2).  Pass i reads
+    // patch rows (0,2), (1,2), (2,1), (1,3) and forms T[i] = d_a -+ d_b, the row of B^T d the two-pass form takes in its half; V, the
+    // chains and R[i][c] are the same operations, and the column sums are carried as Y[0] = (R0 + R1) + R2 in yo[..][0] and
+    // R1, R1 - R2, Y[1] = (R1 - R2) - R3 in yo[..][1]: the two-pass form's additions in its order, so the same bits.
+    if constexpr (NP == 4) {
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
+        for (int i = 0; i < 4; ++i) {
+            constexpr int RA[4] = {0, 1, 2, 1}, RB[4] = {2, 2, 1, 3};
+            // the pass's patch offsets are formed in the pass, from the lane number alone: not ahead of conv1 for all four passes
+            int off[8], li = lane;
+            asm volatile("" : "+v"(li));
+            const int mi = li & 15, kqi = li >> 4, ti = mi < NTL ? mi : NTL - 1, tyi = ti / TW, txi = ti % TW;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int iy = 2 * tyi - 1 + (a ? RB[i] : RA[i]), ix = 2 * txi - 1 + b;
+                    off[a * 4 + b] = kqi * PS + ((iy >= 0 && iy < CH && ix >= 0 && ix < CW) ? iy * CW + ix : P1);
+                }
+            f32x4 acc[4][2];
+#pragma unroll
+            for (int f = 0; f < 4; ++f) { acc[f][0] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f}; acc[f][1] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f}; }
+            // frequency 4 i + c is fragment pair q = 2 (i & 1) + (c >> 1) of pass i >> 1 in the two-pass U layout
+            const float4 *up = ul + (size_t)((i >> 1) * 32 + 2 * (i & 1)) * 64;
+            float4 ub[RING][2];
+#pragma unroll
+            for (int jj = 0; jj < RING - 1; ++jj)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) ub[jj][q] = up[(size_t)(jj * 4 + q) * 64];
+            float d[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d[e] = act[off[e]];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float dn[8];
+                if (j + RING - 1 < 8) {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) ub[(j + RING - 1) % RING][q] = up[(size_t)((j + RING - 1) * 4 + q) * 64];
+                }
+                if (j + 1 < 8) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) dn[e] = act[off[e] + 4 * (j + 1) * PS];
+                }
+                float T[4], V[4];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) T[b] = (i == 1) ? d[b] + d[4 + b] : d[b] - d[4 + b];
+                V[0] = T[0] - T[2]; V[1] = T[1] + T[2]; V[2] = T[2] - T[1]; V[3] = T[1] - T[3];
+                __builtin_amdgcn_sched_barrier(0);  // the loads above stay issued ahead of this k-step's MFMAs
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    const float4 u = ub[j % RING][f >> 1];
+                    acc[f][0] = MFMA(V[f], (f & 1) ? u.z : u.x, acc[f][0]);
+                    acc[f][1] = MFMA(V[f], (f & 1) ? u.w : u.y, acc[f][1]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (j + 1 < 8) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) d[e] = dn[e];
+                }
+            }
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float R0 = (acc[0][nt][r] + acc[1][nt][r]) + acc[2][nt][r];
+                    const float R1 = (acc[1][nt][r] - acc[2][nt][r]) - acc[3][nt][r];
+                    const float R[2] = {R0, R1};
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        if (i == 0) yo[nt][r][0][c] = R[c];
+                        else if (i == 1) { yo[nt][r][0][c] = yo[nt][r][0][c] + R[c]; yo[nt][r][1][c] = R[c]; }
+                        else if (i == 2) { yo[nt][r][0][c] = yo[nt][r][0][c] + R[c]; yo[nt][r][1][c] = yo[nt][r][1][c] - R[c]; }
+                        else yo[nt][r][1][c] = yo[nt][r][1][c] - R[c];
+                    }
+                }
+            // the pass's 32 accumulators are folded into the carries HERE: without the pins instruction selection moves the additions
+            // to the epilogue and keeps every pass's accumulators alive (in scratch) until then
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        if (i < 3) asm volatile("" : "+v"(yo[nt][r][0][c]));
+                        if (i > 0) asm volatile("" : "+v"(yo[nt][r][1][c]));
+                    }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < (NP == 4 ? 0 : 2); ++p) {
         int off[12];
 #pragma unroll
         for (int a = 0; a < 3; ++a)
@@ -267,18 +359,21 @@ AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bi
             }
     }
     LDS_FENCE();  // every read of the input planes has returned: the output may overwrite them
+    int le = lane;
+    if constexpr (NP == 4) asm volatile("" : "+v"(le));  // likewise the 32 store addresses: formed here
+    const int kqe = le >> 4, me = le & 15;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const float bv = bias[nt * 16 + m];
+        const float bv = bias[nt * 16 + me];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int tt = 4 * kq + r, y0 = 2 * (tt / TW), x0 = 2 * (tt % TW);  // C layout of 16x16x4: row 4 (lane >> 4) + r, column lane & 15
+            const int tt = 4 * kqe + r, y0 = 2 * (tt / TW), x0 = 2 * (tt % TW);  // C layout of 16x16x4: row 4 (lane >> 4) + r, column lane & 15
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const float v = yo[nt][r][i][c] + bv;
-                    if (tt < NTL && y0 + i < CH && x0 + c < CW) act[(nt * 16 + m) * PS + (y0 + i) * CW + x0 + c] = v > 0.0f ? v : 0.0f;
+                    if (tt < NTL && y0 + i < CH && x0 + c < CW) act[(nt * 16 + me) * PS + (y0 + i) * CW + x0 + c] = v > 0.0f ? v : 0.0f;
                 }
         }
     }
@@ -617,8 +712,8 @@ __global__ __launch_bounds__(256, 2) void k_trunk(const float *__restrict__ in, 
 // and still computes its share of the tiles, which read valid boards' planes alone.  A workgroup wholly beyond the row count leaves
 // before the first barrier.  Sharing the tiles of conv1 / the direct conv2 as well (6x6: 9 for 12) needs three more barriers and
 // measured slower.
-template <int CH, int CW>
-__global__ __launch_bounds__(256, 2) void k_trunk_quad(const float *__restrict__ in, int B, const int *__restrict__ dyn_count, TrunkParams tp, float *__restrict__ feat) {
+template <int CH, int CW, int FORM>
+__global__ __launch_bounds__(256, FORM == 1 ? 4 : FORM == 2 ? 3 : 2) void k_trunk_quad(const float *__restrict__ in, int B, const int *__restrict__ dyn_count, TrunkParams tp, float *__restrict__ feat) {
     using G = TrunkGeom<CH, CW>;
     if (dyn_count) { int c = *dyn_count; B = c < B ? c : B; }  // rows actually filled this step
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -662,7 +757,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_quad(const float *__restrict__
         LDS_FENCE();
     }
     if (has) {  // conv2 32->32, pad 1 (othello.py:371), Winograd form
-        conv2_wino<CH, CW, G::PS, 3>(act, reinterpret_cast<const float4 *>(tp.wu), tp.cb[0], lane);
+        conv2_wino<CH, CW, G::PS, FORM == 1 ? 2 : 3, FORM ? 4 : 2>(act, reinterpret_cast<const float4 *>(tp.wu), tp.cb[0], lane);
         LDS_FENCE();
     }
     __syncthreads();  // conv2 of every board is in LDS
@@ -3504,6 +3599,17 @@ static bool trunk_quad() {
     return (CH == 7 && CW == 6) || g_beside;
 }
 
+// Which k_trunk_quad a QUAD launch runs.  0: conv2 in two passes of eight frequencies (256 registers, two waves per SIMD: a 2048-board
+// launch fills the register files and no wave of another chain is resident beside it).  1: four passes of one frequency row, U one
+// k-step ahead (<= 128 registers, four waves per SIMD).  2: four passes, U two k-steps ahead (<= 136 registers, three waves).  Same bits.
+// Default: 7x6 form 1, 8x8 form 2, each with the LDS request it measured best with (launch_trunk); the legs are in
+// profiles/r19_trunk_regs.txt and DESIGN section 23.  AZ_TRUNK_QUAD_FORM=0 / 1 / 2 forces one form on every QUAD launch for A/B runs.
+static int trunk_quad_form(int CH) {
+    static int v = -2;
+    if (v == -2) { const char *e = getenv("AZ_TRUNK_QUAD_FORM"); v = e ? atoi(e) : -1; }
+    return (v >= 0 && v <= 2) ? v : (CH == 8 ? 2 : 1);
+}
+
 // boards up to which the trunk runs four waves per board (AZ_TRUNK_Q_MAX; 0: never)
 static int trunk_q_max() { static int v = -1; if (v < 0) { const char *e = getenv("AZ_TRUNK_Q_MAX"); v = e ? atoi(e) : 512; } return v; }
 
@@ -3525,21 +3631,29 @@ static int launch_trunk(az_net *n, const float *in, int B, const int *dyn, hipSt
     }
     using G = TrunkGeom<CH, CW>;
     static bool attr_set = false;
-    static int lds_bytes = G::LDS_BYTES;
+    static int lds_bytes = G::LDS_BYTES, lds_lean = G::LDS_BYTES;
     if (!attr_set) {
         // resident blocks per CU = 160 KB / lds_bytes.  Measured on MI355X (4096 boards): 3 or 2 blocks per CU
         // 88 us, 4 blocks 94 us, 1 block 92 us -> pad the request to 3; AZ_TRUNK_BLOCKS_PER_CU overrides.
+        // The four-pass QUAD forms: 8x8 asks for its natural size, 7x6 for the pad.
         const char *e = getenv("AZ_TRUNK_BLOCKS_PER_CU");
-        int want = e ? atoi(e) : 3;
+        const int want = e ? atoi(e) : 3, want_lean = e ? atoi(e) : ((CH == 8 && CW == 8) ? 0 : 3);  // 0: the natural size
         if (want >= 1 && want <= 8 && 160 * 1024 / want > G::LDS_BYTES) lds_bytes = (160 * 1024 / want) & ~15;
+        if (want_lean >= 1 && want_lean <= 8 && 160 * 1024 / want_lean > G::LDS_BYTES) lds_lean = (160 * 1024 / want_lean) & ~15;
         AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk<CH, CW, WINO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        if constexpr (trunk_has_quad<CH, CW, WINO>())
-            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        if constexpr (trunk_has_quad<CH, CW, WINO>()) {
+            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_lean));
+            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_lean));
+        }
         attr_set = true;
     }
     if constexpr (trunk_has_quad<CH, CW, WINO>()) {
         if (trunk_quad<CH, CW>()) {
-            AZ_LAUNCH((k_trunk_quad<CH, CW>), dim3((B + 3) / 4), dim3(256), lds_bytes, st, in, B, dyn, n->tp, n->feat);
+            const int form = trunk_quad_form(CH);
+            if (form == 1) AZ_LAUNCH((k_trunk_quad<CH, CW, 1>), dim3((B + 3) / 4), dim3(256), lds_lean, st, in, B, dyn, n->tp, n->feat);
+            else if (form == 2) AZ_LAUNCH((k_trunk_quad<CH, CW, 2>), dim3((B + 3) / 4), dim3(256), lds_lean, st, in, B, dyn, n->tp, n->feat);
+            else AZ_LAUNCH((k_trunk_quad<CH, CW, 0>), dim3((B + 3) / 4), dim3(256), lds_bytes, st, in, B, dyn, n->tp, n->feat);
             return AZ_OK;
         }
     }
