@@ -2951,15 +2951,10 @@ __global__ __launch_bounds__(256) void k_qdense_small(const float *__restrict__ 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// layers k_dense_frag can run: K in whole 128-k groups of fragments (PF = 8 loads of 16 k), the 16 rows of K + 4 floats within the LDS
-static bool frag_shape(int N, int K) { return N % 64 == 0 && K % 128 == 0 && K <= 2048; }
+#include <atomic>
+#include "az_net_plan.h"  // which kernel serves a stage, and every AZ_* switch of this file (NetTuning)
 
-// AZ_DENSE_I8=1: OthelloNet's fc1 / fc2 in the exact block-fixed-point form (k_q_rows + k_qgemm); the CPU oracle reads the same variable
-static bool use_qdense(int game) {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("AZ_DENSE_I8"); v = (e && atoi(e) == 1) ? 1 : 0; }
-    return v == 1 && game == AZ_OTHELLO;
-}
+static bool use_qdense(int game) { return net_tuning().dense_i8 && game == AZ_OTHELLO; }
 
 struct az_net {
     int game, H, W, CH, CW, A, F1, F2, FIN, NH, max_batch;
@@ -2971,8 +2966,8 @@ struct az_net {
     float *hwq = nullptr;  // head matrix in 16x16x4 B-fragment order [F2/16][NH/16][64 lanes][4] (k_heads2)
     float *fc1wq = nullptr, *fc2wq = nullptr;  // fc1 / fc2 in the same fragment order (k_dense_frag); null where the shapes do not tile
     float *feat, *h1, *h2;
-    // az_net_set_lanes: the activation rows of lanes 1 .. (lane 0 = the three above), lane_rows each.  A forward of lane l runs with
-    // feat / h1 / h2 pointing at lane l's rows for the duration of its launches (forward_impl): the net is driven by one host thread.
+    // az_net_set_lanes: the activation rows of lanes 1 .. (lane 0 = the three above), lane_rows each.  A forward of lane l carries
+    // lane l's rows in its launch context (forward_impl); the fields above never change after az_net_create.
     struct Acts { float *feat, *h1, *h2; };
     std::vector<Acts> lanes;
     int lane_rows = 0;
@@ -2989,20 +2984,19 @@ struct az_net {
     bool committed;
     // live per-stage timing (az_net_profile): HIP events around every stage launch, harvested in batches
     bool prof = false;
-    int last_trunk_two_boards = 0;
     std::vector<hipEvent_t> prof_ev;  // [PROF_SLOTS][4 stages][start, stop]
     std::vector<int> prof_has;        // bit s: stage s of that forward launched a kernel (the fused Connect4 tail: stage 1 only)
-    std::vector<int> prof_kind;       // trunk kernel used by the forward in that slot
+    std::vector<int> prof_slot;       // bits 4 s .. 4 s + 2: plan_slot of stage s of that forward
     int prof_used = 0;
     double prof_empty_ms = 0.0;   // kept for az_net_profile_overhead: the start / stop events of a launch need no correction
-    int last_trunk_q = 0;
-    // k_trunk2, fc1 / fc2 on the tiled GEMMs (k_gemm, k_gemm_solo, k_gemm_solo_t; Connect4Net: the fused tail in the fc1 slot), heads,
-    // k_trunk (one board per wave) | fc1 / fc2 on the small-batch kernels (k_dense_frag, k_dense_small), k_trunk_q: a slot per KERNEL
-    // family, so that a slot's mean is the figure rocprofv3 lists for that kernel
-    double prof_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double prof_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // per plan_slot (az_net_plan.h)
     long long prof_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 #define PROF_SLOTS 2048
+
+static NetDims net_dims(const az_net *n) {
+    return {n->game, n->CH, n->CW, n->FIN, n->F1, n->F2, n->NH, n->A, n->qd_on, n->fc1wq != nullptr, n->fc2wq != nullptr};
+}
 
 #define AZ_TRY(x) do { int _rc = (x); if (_rc != AZ_OK) return _rc; } while (0)
 
@@ -3506,484 +3500,280 @@ extern "C" int az_net_commit_device(az_net *n, void *stream) {
     return AZ_OK;
 }
 
-// conv2 in the Winograd F(2x2,3x3) form (2.25x fewer multiplications; exact to the same 5e-7 as the direct form against the
-// reference's torch forward; bit-equal to its restatement in the oracle, which reads the same switch AZ_WINOGRAD):
-//   * 8x8 planes: ON.  From 4096 boards up both boards of a wave form one 32-row MFMA tile (conv2_wino32) in the
-//     one-wave-per-SIMD variant of k_trunk2: 512 registers hold all 16 frequency accumulators, the LDS the other four waves
-//     would use holds the transformed weights.  MI355X: 473 vs 526 us at 32768 boards, 71 vs 80 us at 4096.  Below 4096
-//     boards k_trunk runs the 16-row form (conv2_wino; same chains, same bits): 21 vs 23 us at 1024 boards.
-//   * 7x6 planes (Connect4): ON, in the same 32-row one-wave-per-SIMD form (12 tiles per board, 24 of the 32 rows of the MFMA tile):
-//     100 vs 105.5 us at 8192 boards, 52.9 vs 54.8 at 4096; equal below 4096 boards (16-row form in k_trunk).  The 16-row form in
-//     the two-waves-per-SIMD kernel had not paid (103 vs 101 us: with 16-row tiles every 32-cycle MFMA needs an operand transformed
-//     by the wave itself and a 256-byte weight fragment -- the instruction stream, not the matrix pipe, is the limit).
-//   * 6x6 planes: never (9 tiles per board would leave the MFMA tile 44 % empty).
-// AZ_WINOGRAD=0 switches everything back to the direct form.
-static bool use_wino(int CH, int CW) {
-    static int mode = -2;
-    if (mode == -2) { const char *e = getenv("AZ_WINOGRAD"); mode = e ? atoi(e) : -1; }
-    if (mode == 0) return false;
-    return (CH == 8 && CW == 8) || (CH == 7 && CW == 6);  // AZ_WINOGRAD=0: direct form everywhere (the oracle follows the same variable)
-}
-
+// What a stage's launches need besides the plan, handed down from forward_impl by argument: two host threads forwarding at once (an
+// arena's two engines, a trainer beside a search) share nothing here.  A stage gets its own copy, so no flag outlives a failed stage.
+struct LaunchCtx {
+    hipStream_t st;
+    int beside;             // az_net_forward_lane(beside = 1): the forward shares the chip with another launch chain (az_net_plan.h)
+    float *feat, *h1, *h2;  // the activation rows of the forward's lane
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // az_net_profile: the stage's event pair; null: plain launches
+    int ev_used = 0, ev_split = 0;                     // a launch carried events | the start event went out with AZ_LAUNCH_FIRST
+};
 // Every forward kernel is launched through AZ_LAUNCH.  Under az_net_profile the launch carries a start and a stop event
 // (hipExtLaunchKernelGGL): they take the dispatch's own begin / end timestamps -- the two numbers rocprofv3 reports a kernel's duration
 // from -- so a slot's mean IS that kernel's average duration, with nothing to calibrate away (events recorded BETWEEN launches measure
 // marker to marker: kernel + 3-5 us of dispatch and marker processing).  Otherwise (and inside a graph capture) it is a plain launch.
-// The state is per host thread: az_net_profile brackets run_stage on the calling thread, and two networks forwarding from two threads
-// (an arena's two engines, a trainer beside a search) must not see each other's events or small-batch bookkeeping.
-static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
-static thread_local int g_ev_used = 0;
-#define AZ_LAUNCH_EV(ev0, ev1, kern, grid, block, lds, st, ...)                                                              \
-    do {                                                                                                                     \
-        if (g_ev_start) { hipExtLaunchKernelGGL(kern, grid, block, lds, st, ev0, ev1, 0, __VA_ARGS__); g_ev_used = 1; }      \
-        else hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);                                                    \
+#define AZ_LAUNCH_EV(c, ev0, ev1, kern, grid, block, lds, ...)                                                                       \
+    do {                                                                                                                             \
+        if ((c).ev_start) { hipExtLaunchKernelGGL(kern, grid, block, lds, (c).st, ev0, ev1, 0, __VA_ARGS__); (c).ev_used = 1; }      \
+        else hipLaunchKernelGGL(kern, grid, block, lds, (c).st, __VA_ARGS__);                                                        \
     } while (0)
-#define AZ_LAUNCH(kern, grid, block, lds, st, ...) AZ_LAUNCH_EV(g_ev_start, g_ev_stop, kern, grid, block, lds, st, __VA_ARGS__)
+#define AZ_LAUNCH(c, kern, grid, block, lds, ...) AZ_LAUNCH_EV(c, (c).ev_start, (c).ev_stop, kern, grid, block, lds, __VA_ARGS__)
 // a stage of TWO launches (k_q_rows + k_qgemm): the first carries the stage's start event, the second its stop event -- the slot then
 // holds first begin -> second end, the stage as the engine pays for it
-static thread_local int g_ev_split = 0;
-#define AZ_LAUNCH_FIRST(kern, grid, block, lds, st, ...)                                                                     \
-    do { AZ_LAUNCH_EV(g_ev_start, nullptr, kern, grid, block, lds, st, __VA_ARGS__); g_ev_split = 1; } while (0)
-#define AZ_LAUNCH_MAYBE_LAST(kern, grid, block, lds, st, ...)                                                                \
-    do { AZ_LAUNCH_EV(g_ev_split ? nullptr : g_ev_start, g_ev_stop, kern, grid, block, lds, st, __VA_ARGS__); g_ev_split = 0; } while (0)
+#define AZ_LAUNCH_FIRST(c, kern, grid, block, lds, ...)                                                                              \
+    do { AZ_LAUNCH_EV(c, (c).ev_start, nullptr, kern, grid, block, lds, __VA_ARGS__); (c).ev_split = 1; } while (0)
+#define AZ_LAUNCH_MAYBE_LAST(c, kern, grid, block, lds, ...)                                                                         \
+    do { AZ_LAUNCH_EV(c, (c).ev_split ? nullptr : (c).ev_start, (c).ev_stop, kern, grid, block, lds, __VA_ARGS__); (c).ev_split = 0; } while (0)
+
+// The dynamic-LDS limit of KERNELS (one kernel, or its RELU / no-RELU pair), raised to `lds` bytes at their first launch and again by a
+// launch that asks for more (k_dense_frag's request grows with K).  Lazy and per kernel on purpose: what runs inside and outside the
+// engine's graph captures stays what it was.
+template <auto... KERNELS>
+static int lds_attr(int lds) {
+    static std::atomic<int> have{0};
+    if (lds <= have.load(std::memory_order_relaxed)) return AZ_OK;
+    for (const void *k : {reinterpret_cast<const void *>(KERNELS)...}) AZ_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    have.store(lds, std::memory_order_relaxed);
+    return AZ_OK;
+}
 
 template <int CH, int CW, bool WINO>
-static int launch_trunk2(az_net *n, const float *in, int B, const int *dyn, hipStream_t st) {
+static int launch_trunk2(az_net *n, LaunchCtx &c, const float *in, int B, const int *dyn) {
     using G = TrunkGeom<CH, CW>;
-    // one workgroup per CU, two boards per wave: two waves per SIMD -- or, for the Winograd conv2 (8x8 and 7x6 planes), ONE wave per
-    // SIMD with 512 registers (all 16 frequency accumulators live) and the transformed weights in the LDS the other four waves would use
-    constexpr int WPB = WINO ? 4 : 8;
+    constexpr int WPB = WINO ? 4 : 8;  // StagePlan::waves
     constexpr int lds_planes = 64 + WPB * 2 * G::WAVE_FLOATS * 4;
     constexpr int lds_bytes = lds_planes + ((WINO && lds_planes + 65536 <= 160 * 1024) ? 65536 : 0);  // + the Winograd U fragments where they fit
     static_assert(lds_bytes <= 160 * 1024, "k_trunk2 workgroup does not fit the CU's LDS");
-    static int n_cu = 0;
+    static std::atomic<int> n_cu{0};
     if (!n_cu) {
         hipDeviceProp_t pr;
         int dev = 0;
-        AZ_HIP(hipGetDevice(&dev));
-        AZ_HIP(hipGetDeviceProperties(&pr, dev));
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk2<CH, CW, WPB, WINO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        AZ_HIP(hipGetDevice(&dev)); AZ_HIP(hipGetDeviceProperties(&pr, dev));
         n_cu = pr.multiProcessorCount;
     }
-    const int pairs = (B + 1) / 2, want = (pairs + 3) / 4;
-    AZ_LAUNCH((k_trunk2<CH, CW, WPB, WINO>), dim3(want < n_cu ? want : n_cu), dim3(64 * WPB), lds_bytes, st, in, B, dyn, n->tp, n->feat);
+    AZ_TRY((lds_attr<&k_trunk2<CH, CW, WPB, WINO>>(lds_bytes)));
+    const int pairs = (B + 1) / 2, want = (pairs + 3) / 4, cus = n_cu;  // one workgroup per CU
+    AZ_LAUNCH(c, (k_trunk2<CH, CW, WPB, WINO>), dim3(want < cus ? want : cus), dim3(64 * WPB), lds_bytes, in, B, dyn, n->tp, c.feat);
     return AZ_OK;
 }
 
-// az_net_forward_lane(beside = 1): the forward shares the chip with another launch chain.  Per host thread, like the event pair above:
-// set around run_stage by forward_impl, read by the launchers that pick a kernel by size.
-static thread_local int g_beside = 0;
-// Thresholds of that regime, measured with two 2048-row chains of OthelloNet side by side (games/s of the headline):
-//   * dense layers: k_dense_frag up to 1024 rows only, and k_gemm's 64 x 64 tile from ONE block per CU up (fc2 at 2048 rows: 256 blocks
-//     instead of 128 of 64 x 128).  4 352 against 3 830 with the lone launch's picks (k_dense_frag for fc2, L2-bound at ~9 TB/s, or the
-//     64 x 128 tile: the same 3 830): the other chain's kernels are the second resident block the lone launch needs two of its own for.
-//   * trunk: k_trunk stays below 4096 boards (k_trunk2 from 2048: 3 652, its one-wave-per-SIMD blocks leave no room for the neighbour).
-// AZ_BESIDE_FRAG_MAX / AZ_BESIDE_TILE (AZ_GEMM_TILE's codes) / AZ_BESIDE_TRUNK2_MIN override, for A/B runs.
-static int beside_env(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-static int beside_trunk2_min() { static int v = -2; if (v == -2) v = beside_env("AZ_BESIDE_TRUNK2_MIN", 4096); return v; }
-static int beside_frag_max() { static int v = -2; if (v == -2) v = beside_env("AZ_BESIDE_FRAG_MAX", 1024); return v; }
-static int beside_tile() { static int v = -2; if (v == -2) v = beside_env("AZ_BESIDE_TILE", 0); return v; }
-
-static bool trunk_v1() { static int v = -1; if (v < 0) { const char *e = getenv("AZ_TRUNK_V1"); v = (e && atoi(e)) ? 1 : 0; } return v == 1; }
-
-// Which form of k_trunk a launch runs: its workgroup's four boards sharing row tiles (QUAD) or every board its own tiles.  The QUAD
-// form exists for the Winograd 8x8 and 7x6 kernels, the planes it was measured on: 7x6 gains alone (4095 boards:
-// 51.6 vs 55.7 us) and beside another chain; 8x8 gains beside another chain (the headline's two groups) and loses ~1 us alone.
-// AZ_TRUNK_QUAD=1 / 0 forces one form on those two kernels for A/B runs; every other k_trunk keeps its own tiles.
-static int trunk_quad_env() { static int v = -2; if (v == -2) { const char *e = getenv("AZ_TRUNK_QUAD"); v = e ? (atoi(e) ? 1 : 0) : -1; } return v; }
 template <int CH, int CW, bool WINO>
-constexpr bool trunk_has_quad() { return WINO && ((CH == 8 && CW == 8) || (CH == 7 && CW == 6)); }
-template <int CH, int CW>
-static bool trunk_quad() {
-    if (trunk_quad_env() >= 0) return trunk_quad_env() == 1;
-    return (CH == 7 && CW == 6) || g_beside;
-}
-
-// Which k_trunk_quad a QUAD launch runs.  0: conv2 in two passes of eight frequencies (256 registers, two waves per SIMD: a 2048-board
-// launch fills the register files and no wave of another chain is resident beside it).  1: four passes of one frequency row, U one
-// k-step ahead (<= 128 registers, four waves per SIMD).  2: four passes, U two k-steps ahead (<= 136 registers, three waves).  Same bits.
-// Default: 7x6 form 1, 8x8 form 2, each with the LDS request it measured best with (launch_trunk); the legs are in
-// profiles/r19_trunk_regs.txt and DESIGN section 23.  AZ_TRUNK_QUAD_FORM=0 / 1 / 2 forces one form on every QUAD launch for A/B runs.
-static int trunk_quad_form(int CH) {
-    static int v = -2;
-    if (v == -2) { const char *e = getenv("AZ_TRUNK_QUAD_FORM"); v = e ? atoi(e) : -1; }
-    return (v >= 0 && v <= 2) ? v : (CH == 8 ? 2 : 1);
-}
-
-// boards up to which the trunk runs four waves per board (AZ_TRUNK_Q_MAX; 0: never)
-static int trunk_q_max() { static int v = -1; if (v < 0) { const char *e = getenv("AZ_TRUNK_Q_MAX"); v = e ? atoi(e) : 512; } return v; }
-
-template <int CH, int CW, bool WINO>
-static int launch_trunk(az_net *n, const float *in, int B, const int *dyn, hipStream_t st) {
-    // two boards per wave on 32x32x2 pays from ~4096 boards up (16384: 325 vs 331 us); below that the one-board-
-    // per-wave kernel fills the chip better (2048: 45 vs 77 us).  AZ_TRUNK_V1=1 forces the latter.
-    n->last_trunk_two_boards = (!trunk_v1() && B >= (g_beside ? beside_trunk2_min() : 4096)) ? 1 : 0;
-    n->last_trunk_q = 0;
-    if (n->last_trunk_two_boards) return launch_trunk2<CH, CW, WINO>(n, in, B, dyn, st);
-    if (B <= trunk_q_max()) {  // few boards: four waves per board (k_trunk_q)
-        n->last_trunk_q = 1;
-        static int nw_env = -1;
-        if (nw_env < 0) { const char *e = getenv("AZ_TRUNK_Q_WAVES"); nw_env = e ? atoi(e) : 0; }
-        const int nw = nw_env ? nw_env : (B <= 256 ? 8 : 4);  // eight waves per board while that leaves a SIMD at most two (11.7 vs 13.2 us; 512 boards: 23.0 vs 18.6)
-        if (nw == 8) AZ_LAUNCH((k_trunk_q<CH, CW, WINO, 8>), dim3((unsigned)B), dim3(512), 0, st, in, B, dyn, n->tp, n->feat);
-        else AZ_LAUNCH((k_trunk_q<CH, CW, WINO, 4>), dim3((unsigned)B), dim3(256), 0, st, in, B, dyn, n->tp, n->feat);
-        return AZ_OK;
-    }
+static int trunk_go(az_net *n, LaunchCtx &c, const StagePlan &p, const float *in, int B, const int *dyn) {
     using G = TrunkGeom<CH, CW>;
-    static bool attr_set = false;
-    static int lds_bytes = G::LDS_BYTES, lds_lean = G::LDS_BYTES;
-    if (!attr_set) {
-        // resident blocks per CU = 160 KB / lds_bytes.  Measured on MI355X (4096 boards): 3 or 2 blocks per CU
-        // 88 us, 4 blocks 94 us, 1 block 92 us -> pad the request to 3; AZ_TRUNK_BLOCKS_PER_CU overrides.
-        // The four-pass QUAD forms: 8x8 asks for its natural size, 7x6 for the pad.
-        const char *e = getenv("AZ_TRUNK_BLOCKS_PER_CU");
-        const int want = e ? atoi(e) : 3, want_lean = e ? atoi(e) : ((CH == 8 && CW == 8) ? 0 : 3);  // 0: the natural size
-        if (want >= 1 && want <= 8 && 160 * 1024 / want > G::LDS_BYTES) lds_bytes = (160 * 1024 / want) & ~15;
-        if (want_lean >= 1 && want_lean <= 8 && 160 * 1024 / want_lean > G::LDS_BYTES) lds_lean = (160 * 1024 / want_lean) & ~15;
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk<CH, CW, WINO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        if constexpr (trunk_has_quad<CH, CW, WINO>()) {
-            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_lean));
-            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk_quad<CH, CW, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_lean));
-        }
-        attr_set = true;
-    }
-    if constexpr (trunk_has_quad<CH, CW, WINO>()) {
-        if (trunk_quad<CH, CW>()) {
-            const int form = trunk_quad_form(CH);
-            if (form == 1) AZ_LAUNCH((k_trunk_quad<CH, CW, 1>), dim3((B + 3) / 4), dim3(256), lds_lean, st, in, B, dyn, n->tp, n->feat);
-            else if (form == 2) AZ_LAUNCH((k_trunk_quad<CH, CW, 2>), dim3((B + 3) / 4), dim3(256), lds_lean, st, in, B, dyn, n->tp, n->feat);
-            else AZ_LAUNCH((k_trunk_quad<CH, CW, 0>), dim3((B + 3) / 4), dim3(256), lds_bytes, st, in, B, dyn, n->tp, n->feat);
+    if constexpr (plane_tuned(CH, CW)) {  // the other planes have k_trunk only
+        if (p.kernel == K_TRUNK2) return launch_trunk2<CH, CW, WINO>(n, c, in, B, dyn);
+        if (p.kernel == K_TRUNK_Q) {
+            if (p.waves == 8) AZ_LAUNCH(c, (k_trunk_q<CH, CW, WINO, 8>), dim3((unsigned)B), dim3(512), 0, in, B, dyn, n->tp, c.feat);
+            else AZ_LAUNCH(c, (k_trunk_q<CH, CW, WINO, 4>), dim3((unsigned)B), dim3(256), 0, in, B, dyn, n->tp, c.feat);
             return AZ_OK;
         }
     }
-    AZ_LAUNCH((k_trunk<CH, CW, WINO>), dim3((B + 3) / 4), dim3(256), lds_bytes, st, in, B, dyn, n->tp, n->feat);
+    const int b = p.lds_blocks, lds = (b >= 1 && b <= 8 && 160 * 1024 / b > G::LDS_BYTES) ? (160 * 1024 / b) & ~15 : G::LDS_BYTES;
+    if constexpr (WINO && plane_wino(CH, CW)) {
+#define QUAD(form) if (p.kernel == K_TRUNK_QUAD && p.quad_form == form) {                                                            \
+        AZ_TRY((lds_attr<&k_trunk_quad<CH, CW, form>>(lds)));                                                                        \
+        AZ_LAUNCH(c, (k_trunk_quad<CH, CW, form>), dim3((B + 3) / 4), dim3(256), lds, in, B, dyn, n->tp, c.feat);                    \
+        return AZ_OK; }
+        QUAD(0) QUAD(1) QUAD(2)
+#undef QUAD
+    }
+    AZ_TRY((lds_attr<&k_trunk<CH, CW, WINO>>(lds)));
+    AZ_LAUNCH(c, (k_trunk<CH, CW, WINO>), dim3((B + 3) / 4), dim3(256), lds, in, B, dyn, n->tp, c.feat);
     return AZ_OK;
 }
 
+// every plane a net can be created for: the tuned three (8x8 and 7x6 in both conv2 forms), the others in the direct form
+static int launch_trunk(az_net *n, LaunchCtx &c, const StagePlan &p, const float *in, int B, const int *dyn) {
+#define PLANE(ch, cw, w) if (n->CH == ch && n->CW == cw && p.wino == w) return trunk_go<ch, cw, w>(n, c, p, in, B, dyn);
+    PLANE(8, 8, true) PLANE(8, 8, false) PLANE(7, 6, true) PLANE(7, 6, false) PLANE(6, 6, false)
+    PLANE(5, 5, false) PLANE(5, 6, false) PLANE(5, 7, false) PLANE(5, 8, false) PLANE(6, 5, false) PLANE(6, 7, false) PLANE(6, 8, false)
+    PLANE(7, 5, false) PLANE(7, 7, false) PLANE(7, 8, false) PLANE(8, 5, false) PLANE(8, 6, false) PLANE(8, 7, false)
+#undef PLANE
+    az_set_error("no conv-trunk kernel instantiated for a %dx%d plane", n->CH, n->CW);
+    return AZ_EINVAL;
+}
+
+struct Dense {  // C[M][N] = act(A[M][K] Bw[K][N] + bias); Bq: Bw in k_dense_frag's fragment order, or null
+    const float *A, *Bw, *Bq, *bias;
+    float *C;
+    int M, N, K;
+    bool relu;
+    const int *dyn;
+};
+
 template <int BM, int BN, int WM, int WN, int KT>
-static int gemm_launch(const float *A, const float *Bw, const float *bias, float *C, int M, int N, int K, bool relu, const int *dyn, hipStream_t st) {
+static int gemm_launch(LaunchCtx &c, const Dense &a) {
     constexpr int lds = gemm_lds_bytes<BM, BN>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm<BM, BN, WM, WN, true, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm<BM, BN, WM, WN, false, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    dim3 grid(N / BN, (M + BM - 1) / BM);
-    if (relu) AZ_LAUNCH((k_gemm<BM, BN, WM, WN, true, KT>), grid, dim3(256), lds, st, A, Bw, bias, C, M, N, K, dyn);
-    else AZ_LAUNCH((k_gemm<BM, BN, WM, WN, false, KT>), grid, dim3(256), lds, st, A, Bw, bias, C, M, N, K, dyn);
+    AZ_TRY((lds_attr<&k_gemm<BM, BN, WM, WN, true, KT>, &k_gemm<BM, BN, WM, WN, false, KT>>(lds)));
+    dim3 grid(a.N / BN, (a.M + BM - 1) / BM);
+    if (a.relu) AZ_LAUNCH(c, (k_gemm<BM, BN, WM, WN, true, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
+    else AZ_LAUNCH(c, (k_gemm<BM, BN, WM, WN, false, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
     return AZ_OK;
 }
 
 // K of the networks' dense layers gets an unrolled instantiation: 512 / 1024 (Othello 8x8), 128 (Othello 6x6),
 // 192 / 64 (Connect4); anything else runs the runtime loop
 template <int BM, int BN, int WM, int WN>
-static int gemm_go(const float *A, const float *Bw, const float *bias, float *C, int M, int N, int K, bool relu, const int *dyn, hipStream_t st) {
-    switch (K) {
-        case 1024: return gemm_launch<BM, BN, WM, WN, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-        case 512: return gemm_launch<BM, BN, WM, WN, 16>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-        case 192: return gemm_launch<BM, BN, WM, WN, 6>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-        case 128: return gemm_launch<BM, BN, WM, WN, 4>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-        case 64: return gemm_launch<BM, BN, WM, WN, 2>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-        default: return gemm_launch<BM, BN, WM, WN, 0>(A, Bw, bias, C, M, N, K, relu, dyn, st);
+static int gemm_go(LaunchCtx &c, const Dense &a) {
+    switch (a.K) {
+        case 1024: return gemm_launch<BM, BN, WM, WN, 32>(c, a);
+        case 512: return gemm_launch<BM, BN, WM, WN, 16>(c, a);
+        case 192: return gemm_launch<BM, BN, WM, WN, 6>(c, a);
+        case 128: return gemm_launch<BM, BN, WM, WN, 4>(c, a);
+        case 64: return gemm_launch<BM, BN, WM, WN, 2>(c, a);
+        default: return gemm_launch<BM, BN, WM, WN, 0>(c, a);
     }
 }
 
 template <int TM, int TN>
-static int solo_t_launch(const float *A, const float *Bw, const float *bias, float *C, int M, int N, int K, bool relu, const int *dyn, hipStream_t st) {
+static int solo_t_launch(LaunchCtx &c, const Dense &a) {
     constexpr int BM = 64 * TM, BN = 64 * TN, lds = 4 * (2 * BM * 33 + 2 * 32 * BN);
-    static bool attr_set = false;
-    if (!attr_set) {
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_solo_t<true, TM, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_solo_t<false, TM, TN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    dim3 grid(N / BN, (M + BM - 1) / BM);
-    if (relu) AZ_LAUNCH((k_gemm_solo_t<true, TM, TN>), grid, dim3(256), lds, st, A, Bw, bias, C, M, N, K, dyn);
-    else AZ_LAUNCH((k_gemm_solo_t<false, TM, TN>), grid, dim3(256), lds, st, A, Bw, bias, C, M, N, K, dyn);
+    AZ_TRY((lds_attr<&k_gemm_solo_t<true, TM, TN>, &k_gemm_solo_t<false, TM, TN>>(lds)));
+    dim3 grid(a.N / BN, (a.M + BM - 1) / BM);
+    if (a.relu) AZ_LAUNCH(c, (k_gemm_solo_t<true, TM, TN>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
+    else AZ_LAUNCH(c, (k_gemm_solo_t<false, TM, TN>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
     return AZ_OK;
 }
 
-// which kernel a dense layer of M rows runs on (one place: launch_gemm dispatches on it, az_net_stage_kernel reports it)
-enum GemmKind { GK_SMALL, GK_FRAG, GK_SOLO, GK_SOLO_T, GK_TILED };
-static int gemm_solo_env() { static int solo = -2; if (solo == -2) { const char *e = getenv("AZ_GEMM_SOLO"); solo = e ? atoi(e) : -1; } return solo; }
-// rows up to which k_dense_frag runs a layer.  Measured on OthelloNet 8x8 (us, k_dense_frag | what ran before: k_dense_small up to 128 / 256
-// rows, k_gemm above): fc1 (K = 512) 6.6 | 8.7 at 1 row, 7.3 | 21.0 at 256, 9.9 | 20.9 at 512, 16.3 | 21.2 at 1024, 22.3 | 21.0 at 1536;
-// fc2 (K = 1024) 11.2 | 15.9 at 1 row, 11.7 | 24.1 at 256, 11.9 | 39.8 at 512, 17.5 | 39.8 at 1024, 28.2 | 40.0 at 1536, 34.5 | 40.0 at 2048,
-// 65 | 37 at 4096 (every 16 rows stream the whole weight matrix from L2: ~9 TB/s from 1024 rows up, the kernel's bound there).
-// AZ_DENSE_FRAG_MAX overrides both limits; 0 switches the kernel off (the kernels of the rounds before).
-static int frag_max_rows(int K) {
-    static int v = -2;
-    if (v == -2) { const char *e = getenv("AZ_DENSE_FRAG_MAX"); v = e ? atoi(e) : -1; }
-    return v >= 0 ? v : (K >= 1024 ? 2048 : 1024);
-}
-static GemmKind gemm_kind(int M, int N, int K, bool have_q = true) {
-    const int fmax = (g_beside && beside_frag_max() < frag_max_rows(K)) ? beside_frag_max() : frag_max_rows(K);
-    if (have_q && M <= fmax && frag_shape(N, K)) return GK_FRAG;  // latency-bound row counts: the shortest accumulation chain
-    // measured crossover against the tiled GEMM (MI355X): K = 512 up to 128 rows (15 vs 21 us), K = 1024 up to 256 rows (28 vs 40 us)
-    if (M <= (K >= 1024 ? 256 : 128) && K % 32 == 0) return GK_SMALL;  // few rows: latency matters, not throughput
-    // large row counts: the one-wave-per-SIMD kernel (256x256 workgroup tiles), from one tile per CU up.  AZ_GEMM_SOLO=0 / 1 forces.
-    const int solo = gemm_solo_env();
-    const long long tiles = (long long)((M + 255) / 256) * (N / 256);
-    if (solo != 0 && N % 256 == 0 && (solo == 1 || tiles >= 256)) return GK_SOLO;
-    // below that: the same scheme on 128x128 tiles from TWO tiles per CU up (fc1 from 8192 rows, fc2 from 16384; AZ_GEMM_SOLO=2
-    // forces it).  Measured against k_gemm: 76 vs 80 us (fc1, 8192 rows), 137 vs 144 (fc2, 16384); with ONE tile per CU it loses
-    // (4096 rows: 42.6 vs 41.4 us, 64x128 tiles 57 vs 42): a 4096-cycle K tile does not carry its barrier and LDS turnaround
-    // without a partner wave, and k_gemm's two blocks per CU are exactly that partner.
-    if (solo != 0 && solo != 1 && N % 128 == 0) {
-        const long long t128 = (long long)((M + 127) / 128) * (N / 128);
-        if (solo == 2 || (solo < 0 && t128 >= 512)) return GK_SOLO_T;
-    }
-    return GK_TILED;
-}
-
-static int frag_go(const float *A, const float *Bq, const float *bias, float *C, int M, int N, int K, bool relu, const int *dyn, hipStream_t st) {
+static int frag_go(LaunchCtx &c, const Dense &a) {
     constexpr int NT = 4;
-    const int lds = 4 * 16 * (K + 4);
-    static int attr_lds = 0;
-    if (lds > attr_lds) {
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dense_frag<true, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dense_frag<false, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_lds = lds;
-    }
-    dim3 grid((unsigned)(N / (16 * NT)), (unsigned)((M + 15) / 16));
-    if (relu) AZ_LAUNCH((k_dense_frag<true, NT>), grid, dim3(64 * NT), lds, st, A, Bq, bias, C, M, N, K, dyn);
-    else AZ_LAUNCH((k_dense_frag<false, NT>), grid, dim3(64 * NT), lds, st, A, Bq, bias, C, M, N, K, dyn);
+    const int lds = 4 * 16 * (a.K + 4);
+    AZ_TRY((lds_attr<&k_dense_frag<true, NT>, &k_dense_frag<false, NT>>(lds)));
+    dim3 grid((unsigned)(a.N / (16 * NT)), (unsigned)((a.M + 15) / 16));
+    if (a.relu) AZ_LAUNCH(c, (k_dense_frag<true, NT>), grid, dim3(64 * NT), lds, a.A, a.Bq, a.bias, a.C, a.M, a.N, a.K, a.dyn);
+    else AZ_LAUNCH(c, (k_dense_frag<false, NT>), grid, dim3(64 * NT), lds, a.A, a.Bq, a.bias, a.C, a.M, a.N, a.K, a.dyn);
     return AZ_OK;
 }
 
-static thread_local int g_last_gemm_small = 0;  // set by launch_gemm when it served the layer with a small-batch kernel (the profiler books those apart)
-
-static int launch_gemm(const float *A, const float *Bw, const float *Bq, const float *bias, float *C, int M, int N, int K, bool relu, const int *dyn, hipStream_t st) {
-    AZ_REQUIRE(K % 32 == 0, AZ_EINVAL, "GEMM K=%d is not a multiple of 32", K);
-    switch (gemm_kind(M, N, K, Bq != nullptr)) {
-        case GK_FRAG: g_last_gemm_small = 1; return frag_go(A, Bq, bias, C, M, N, K, relu, dyn, st);
-        case GK_SMALL: {
-            g_last_gemm_small = 1;
-            dim3 grid((unsigned)((N + 63) / 64), (unsigned)M);
-            if (relu) AZ_LAUNCH((k_dense_small<true>), grid, dim3(64), 0, st, A, Bw, bias, C, M, N, K, dyn);
-            else AZ_LAUNCH((k_dense_small<false>), grid, dim3(64), 0, st, A, Bw, bias, C, M, N, K, dyn);
+// fc1 / fc2 in float32 on the kernel plan_dense chose
+static int launch_dense(LaunchCtx &c, const StagePlan &p, const Dense &a) {
+    AZ_REQUIRE(a.K % 32 == 0, AZ_EINVAL, "GEMM K=%d is not a multiple of 32", a.K);
+    switch (p.kernel) {
+        case K_DENSE_FRAG: return frag_go(c, a);
+        case K_DENSE_SMALL: {
+            dim3 grid((unsigned)((a.N + 63) / 64), (unsigned)a.M);
+            if (a.relu) AZ_LAUNCH(c, (k_dense_small<true>), grid, dim3(64), 0, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
+            else AZ_LAUNCH(c, (k_dense_small<false>), grid, dim3(64), 0, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
             return AZ_OK;
         }
-        case GK_SOLO: {
+        case K_GEMM_SOLO: {
             constexpr int lds = 4 * (2 * 256 * 33 + 2 * 32 * 256);
-            static bool attr_set = false;
-            if (!attr_set) {
-                AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_solo<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_solo<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                attr_set = true;
-            }
-            dim3 grid(N / 256, (M + 255) / 256);
-            if (relu) AZ_LAUNCH((k_gemm_solo<true>), grid, dim3(256), lds, st, A, Bw, bias, C, M, N, K, dyn);
-            else AZ_LAUNCH((k_gemm_solo<false>), grid, dim3(256), lds, st, A, Bw, bias, C, M, N, K, dyn);
+            AZ_TRY((lds_attr<&k_gemm_solo<true>, &k_gemm_solo<false>>(lds)));
+            dim3 grid(a.N / 256, (a.M + 255) / 256);
+            if (a.relu) AZ_LAUNCH(c, (k_gemm_solo<true>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
+            else AZ_LAUNCH(c, (k_gemm_solo<false>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
             return AZ_OK;
         }
-        case GK_SOLO_T: return solo_t_launch<2, 2>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-        default: break;
+        case K_GEMM_SOLO_T: return solo_t_launch<2, 2>(c, a);
+        default: break;  // K_GEMM
     }
-    // pick the largest tile that still gives every CU two resident blocks (512 blocks on 256 CUs):
-    // a block's barrier and LDS-fill phases then overlap the other block's MFMAs
-    const long long mb128 = (M + 127) / 128, mb64 = (M + 63) / 64;
-    static int force = -1;
-    if (force < 0) { const char *e = getenv("AZ_GEMM_TILE"); force = e ? atoi(e) : 0; }
-    const int tile = force ? force : (g_beside ? beside_tile() : 0);
-    if (tile == 1 && N % 128 == 0) return gemm_go<128, 128, 64, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (tile == 2 && N % 64 == 0) return gemm_go<128, 64, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (tile == 3 && N % 64 == 0) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (tile == 4 && N % 128 == 0) return gemm_go<64, 128, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (N % 128 == 0 && mb128 * (N / 128) >= 512) return gemm_go<128, 128, 64, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (N % 64 == 0 && mb128 * (N / 64) >= 512) return gemm_go<128, 64, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (N % 64 == 0 && mb64 * (N / 64) >= (g_beside ? 256 : 512)) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (N % 128 == 0) return gemm_go<64, 128, 32, 64>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (N % 64 == 0) return gemm_go<64, 64, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    if (N % 32 == 0) return gemm_go<128, 32, 32, 32>(A, Bw, bias, C, M, N, K, relu, dyn, st);
-    az_set_error("GEMM N=%d is not a multiple of 32", N);
+#define TILE(tm, tn, wm, wn) if (p.bm == tm && p.bn == tn) return gemm_go<tm, tn, wm, wn>(c, a);
+    TILE(128, 128, 64, 64) TILE(128, 64, 32, 64) TILE(64, 64, 32, 32) TILE(64, 128, 32, 64) TILE(128, 32, 32, 32)
+#undef TILE
+    az_set_error("GEMM N=%d is not a multiple of 32", a.N);
     return AZ_EINVAL;
 }
 
-#define QD_SMALL_MAX 512  // rows up to which the one-launch small-batch kernel serves a fixed-point dense layer
-static int qd_small_max() {  // AZ_QD_SMALL_MAX overrides the row limit (0: never); launch_qdense and az_net_stage_kernel both ask here
-    static int v = -2;
-    if (v == -2) { const char *e = getenv("AZ_QD_SMALL_MAX"); v = e ? atoi(e) : QD_SMALL_MAX; }
-    return v;
-}
-static bool qd_small_serves(int B, int N, int K) { return B <= qd_small_max() && N % 64 == 0 && (K == 128 || K == 512 || K == 1024); }
-
 template <int NWM, int NWN, int WM, int WN>
-static int qgemm_go(az_net *n, int layer, int B, const int *dyn, hipStream_t st) {
+static int qgemm_go(az_net *n, LaunchCtx &c, int layer, int B, const int *dyn) {
     constexpr int lds = qgemm_lds_bytes<NWM, NWN, WM, WN>(), BM = NWM * WM * 32, BN = NWN * WN * 32;
     static_assert(lds <= 160 * 1024, "k_qgemm does not fit the CU's LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_qgemm<NWM, NWN, WM, WN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
+    AZ_TRY((lds_attr<&k_qgemm<NWM, NWN, WM, WN, true>>(lds)));
     const int K = layer == 1 ? n->FIN : n->F1, N = layer == 1 ? n->F1 : n->F2;
-    AZ_LAUNCH_MAYBE_LAST((k_qgemm<NWM, NWN, WM, WN, true>), dim3((unsigned)(N / BN), (unsigned)((B + BM - 1) / BM)), dim3(64 * NWM * NWN), lds, st, n->qd_a,
+    AZ_LAUNCH_MAYBE_LAST(c, (k_qgemm<NWM, NWN, WM, WN, true>), dim3((unsigned)(N / BN), (unsigned)((B + BM - 1) / BM)), dim3(64 * NWM * NWN), lds, n->qd_a,
               n->qd_rows * (size_t)K, n->qd_ea, layer == 1 ? n->qd_w1 : n->qd_w2, (size_t)N * K, layer == 1 ? n->qd_e1 : n->qd_e2, layer == 1 ? n->fc1b : n->fc2b,
-              layer == 1 ? n->h1 : n->h2, B, N, K, dyn);
+              layer == 1 ? c.h1 : c.h2, B, N, K, dyn);
     return AZ_OK;
 }
 
-// fc1 / fc2 in the exact block-fixed-point form: quantise the rows of the layer's input, then the int8 GEMM
-static int launch_qdense(az_net *n, int layer, int B, const int *dyn, hipStream_t st) {
+// fc1 / fc2 in the exact block-fixed-point form: one launch for few rows; else quantise the rows of the layer's input, then the int8 GEMM
+static int launch_qdense(az_net *n, LaunchCtx &c, const StagePlan &p, int layer, int B, const int *dyn) {
     const int K = layer == 1 ? n->FIN : n->F1, N = layer == 1 ? n->F1 : n->F2;
-    if (qd_small_serves(B, N, K)) {
-        const float *x = layer == 1 ? n->feat : n->h1;
+    const float *x = layer == 1 ? c.feat : c.h1;
+    if (p.kernel == K_QDENSE_SMALL) {
         const int8_t *w = layer == 1 ? n->qd_w1 : n->qd_w2;
         const int *e = layer == 1 ? n->qd_e1 : n->qd_e2;
         const float *bias = layer == 1 ? n->fc1b : n->fc2b;
-        float *out = layer == 1 ? n->h1 : n->h2;
+        float *out = layer == 1 ? c.h1 : c.h2;
         const dim3 grid((unsigned)(N / 64), (unsigned)((B + 15) / 16));
-        g_last_gemm_small = 1;
-        if (K == 128) AZ_LAUNCH((k_qdense_small<128, true>), grid, dim3(256), 0, st, x, w, (size_t)N * K, e, bias, out, B, N, dyn);
-        else if (K == 512) AZ_LAUNCH((k_qdense_small<512, true>), grid, dim3(256), 0, st, x, w, (size_t)N * K, e, bias, out, B, N, dyn);
-        else AZ_LAUNCH((k_qdense_small<1024, true>), grid, dim3(256), 0, st, x, w, (size_t)N * K, e, bias, out, B, N, dyn);
+        if (K == 128) AZ_LAUNCH(c, (k_qdense_small<128, true>), grid, dim3(256), 0, x, w, (size_t)N * K, e, bias, out, B, N, dyn);
+        else if (K == 512) AZ_LAUNCH(c, (k_qdense_small<512, true>), grid, dim3(256), 0, x, w, (size_t)N * K, e, bias, out, B, N, dyn);
+        else AZ_LAUNCH(c, (k_qdense_small<1024, true>), grid, dim3(256), 0, x, w, (size_t)N * K, e, bias, out, B, N, dyn);
         return AZ_OK;
     }
-    AZ_LAUNCH_FIRST(k_q_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, layer == 1 ? n->feat : n->h1, B, K, dyn, n->qd_a, n->qd_rows * (size_t)K, n->qd_ea);
-    static int cfg = -1;  // AZ_QG_CFG: tile plan for A/B runs (every plan gives the same bits)
-    if (cfg < 0) { const char *e = getenv("AZ_QG_CFG"); cfg = e ? atoi(e) : 0; }
-    if (cfg == 1) return qgemm_go<2, 2, 1, 2>(n, layer, B, dyn, st);  // 64 x 128, four waves, two workgroups per CU
-    if (cfg == 2) return qgemm_go<2, 2, 1, 1>(n, layer, B, dyn, st);  // 64 x 64, four waves
-    if (cfg == 3) return qgemm_go<4, 2, 1, 1>(n, layer, B, dyn, st);  // 128 x 64, eight waves
-    if (cfg == 4) return qgemm_go<4, 2, 1, 2>(n, layer, B, dyn, st);  // 128 x 128, eight waves
-    if (cfg == 5) return qgemm_go<2, 4, 1, 1>(n, layer, B, dyn, st);  // 64 x 128, eight waves
-    // 128 x 128 tiles from one workgroup per CU up, 64 x 128 below
-    if ((long long)((B + 127) / 128) * (N / 128) >= 256) return qgemm_go<4, 2, 1, 2>(n, layer, B, dyn, st);
-    return qgemm_go<2, 4, 1, 1>(n, layer, B, dyn, st);
+    AZ_LAUNCH_FIRST(c, k_q_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, x, B, K, dyn, n->qd_a, n->qd_rows * (size_t)K, n->qd_ea);
+#define QG(nwm, nwn, wm, wn) if (p.qg[0] == nwm && p.qg[1] == nwn && p.qg[2] == wm && p.qg[3] == wn) return qgemm_go<nwm, nwn, wm, wn>(n, c, layer, B, dyn);
+    QG(2, 2, 1, 2) QG(2, 2, 1, 1) QG(4, 2, 1, 1) QG(4, 2, 1, 2) QG(2, 4, 1, 1)
+#undef QG
+    az_set_error("no k_qgemm for the tile plan <%d,%d,%d,%d>", p.qg[0], p.qg[1], p.qg[2], p.qg[3]);
+    return AZ_EINVAL;
 }
 
 template <int NT>
-static int heads_go(az_net *n, int B, float *probs, float *value, const int *dyn, hipStream_t st) {
+static int heads_go(az_net *n, LaunchCtx &c, int B, float *probs, float *value, const int *dyn) {
     constexpr int lds = heads_lds_bytes<NT>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_heads<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    AZ_LAUNCH((k_heads<NT>), dim3((B + 31) / 32), dim3(256), lds, st, n->h2, n->hw, n->hb, B, n->F2, n->A, probs, value, dyn);
+    AZ_TRY((lds_attr<&k_heads<NT>>(lds)));
+    AZ_LAUNCH(c, (k_heads<NT>), dim3((B + 31) / 32), dim3(256), lds, c.h2, n->hw, n->hb, B, n->F2, n->A, probs, value, dyn);
     return AZ_OK;
 }
 
 template <int NT, int RH>
-static int heads2_go(az_net *n, int B, float *probs, float *value, const int *dyn, hipStream_t st) {
+static int heads2_go(az_net *n, LaunchCtx &c, int B, float *probs, float *value, const int *dyn) {
     constexpr int lds = heads2_lds_bytes<NT, RH, 512>();
     static_assert(lds <= 160 * 1024, "k_heads2 does not fit the CU's LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_heads2<NT, RH, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    AZ_LAUNCH((k_heads2<NT, RH, 512>), dim3((unsigned)((B + 16 * RH - 1) / (16 * RH))), dim3(64 * NT), lds, st, n->h2, n->hwq, n->hb, B, n->A,
-                       probs, value, dyn);
+    AZ_TRY((lds_attr<&k_heads2<NT, RH, 512>>(lds)));
+    AZ_LAUNCH(c, (k_heads2<NT, RH, 512>), dim3((unsigned)((B + 16 * RH - 1) / (16 * RH))), dim3(64 * NT), lds, c.h2, n->hwq, n->hb, B, n->A, probs, value, dyn);
     return AZ_OK;
 }
 
-// rows up to which the row-per-workgroup heads kernel runs: 128 where k_heads2 has no instantiation; never for OthelloNet (F2 = 512), whose
-// k_heads2 is faster at every size (8.6 vs 9.8 us at one row, 9.6 vs 10.3 at 128).  AZ_HEADS_SMALL_MAX forces a limit for A/B runs.
-static int heads_small_max(const az_net *n) {
-    static int v = -2;
-    if (v == -2) { const char *e = getenv("AZ_HEADS_SMALL_MAX"); v = e ? atoi(e) : -1; }
-    if (v >= 0) return v;
-    return (n->F2 == 512 && (n->NH == 80 || n->NH == 48)) ? 0 : 128;
-}
-
-static int launch_heads(az_net *n, int B, float *probs, float *value, const int *dyn, hipStream_t st) {
-    if (B <= heads_small_max(n) && n->NH <= 128 && n->F2 % 32 == 0) {  // few rows: latency, not throughput
-        AZ_LAUNCH(k_heads_small, dim3((unsigned)B), dim3(128), 0, st, n->h2, n->hw, n->hb, B, n->F2, n->A, n->NH, probs, value, dyn);
+static int launch_heads(az_net *n, LaunchCtx &c, const StagePlan &p, int B, float *probs, float *value, const int *dyn) {
+    if (p.kernel == K_HEADS_SMALL) {
+        AZ_LAUNCH(c, k_heads_small, dim3((unsigned)B), dim3(128), 0, c.h2, n->hw, n->hb, B, n->F2, n->A, n->NH, probs, value, dyn);
         return AZ_OK;
     }
-    static int v1 = -1;
-    if (v1 < 0) { const char *e = getenv("AZ_HEADS_V1"); v1 = (e && atoi(e)) ? 1 : 0; }  // the round-1 kernel, for A/B runs
-    static int rh = -1;
-    if (rh < 0) { const char *e = getenv("AZ_HEADS_RH"); rh = e ? atoi(e) : 0; }  // tuning: force 16-row (1) / 32-row (2) blocks
-    if (!v1 && n->F2 == 512) {  // OthelloNet.  Measured (us, 16-row / 32-row blocks; round-1 kernel): 4096 rows 9.9 / 14.5 / 15.5,
-        // 8192: 13.6 / 15.0, 16384: 20.3 / 21.4, 32768: 39.0 / 55.7 / 44.4 -> 16-row blocks (more waves in flight) everywhere
-        const bool two = rh == 2;
-        if (n->NH == 80) return two ? heads2_go<5, 2>(n, B, probs, value, dyn, st) : heads2_go<5, 1>(n, B, probs, value, dyn, st);
-        if (n->NH == 48) return two ? heads2_go<3, 2>(n, B, probs, value, dyn, st) : heads2_go<3, 1>(n, B, probs, value, dyn, st);
-    }
-    switch (n->NH / 16) {
-        case 1: return heads_go<1>(n, B, probs, value, dyn, st);
-        case 3: return heads_go<3>(n, B, probs, value, dyn, st);
-        case 5: return heads_go<5>(n, B, probs, value, dyn, st);
+    if (p.kernel == K_HEADS2 && p.nt == 5) return p.rh == 2 ? heads2_go<5, 2>(n, c, B, probs, value, dyn) : heads2_go<5, 1>(n, c, B, probs, value, dyn);
+    if (p.kernel == K_HEADS2 && p.nt == 3) return p.rh == 2 ? heads2_go<3, 2>(n, c, B, probs, value, dyn) : heads2_go<3, 1>(n, c, B, probs, value, dyn);
+    switch (p.kernel == K_HEADS ? p.nt : 0) {
+        case 1: return heads_go<1>(n, c, B, probs, value, dyn);
+        case 3: return heads_go<3>(n, c, B, probs, value, dyn);
+        case 5: return heads_go<5>(n, c, B, probs, value, dyn);
         default: az_set_error("no heads kernel for padded width %d", n->NH); return AZ_EINVAL;
     }
 }
 
-// AZ_TAIL_V1=1: the fma kernel of the rounds before (k_tail_small) instead of k_tail_mfma, for A/B runs
-static bool tail_v1() { static int v = -1; if (v < 0) { const char *e = getenv("AZ_TAIL_V1"); v = (e && atoi(e)) ? 1 : 0; } return v == 1; }
-
-// fc1 + fc2 + heads as ONE launch where the dense layers are small (Connect4Net); returns false when no instantiation fits
-static bool tail_is_fused(const az_net *n) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("AZ_NO_FUSED_TAIL"); off = (e && atoi(e)) ? 1 : 0; }
-    return !off && n->F1 == 64 && n->F2 == 32 && n->NH == 16 && n->FIN == 192 && n->A == 7;  // Connect4 6x7 (8x8: 131 KB of fc1 weights, not worth restaging)
-}
-
 template <int FIN, int A, int R>
-static int tail_go(az_net *n, int B, float *probs, float *value, const int *dyn, hipStream_t st) {
+static int tail_go(az_net *n, LaunchCtx &c, int B, float *probs, float *value, const int *dyn) {
     constexpr int lds = 4 * tail_lds_floats<FIN, 64, 32, 16, R>();
     static_assert(lds <= 160 * 1024, "k_tail_small does not fit the CU's LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tail_small<FIN, 64, 32, 16, A, R>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    AZ_LAUNCH((k_tail_small<FIN, 64, 32, 16, A, R>), dim3((unsigned)((B + 4 * R - 1) / (4 * R))), dim3(256), lds, st, n->feat, n->fc1w,
+    AZ_TRY((lds_attr<&k_tail_small<FIN, 64, 32, 16, A, R>>(lds)));
+    AZ_LAUNCH(c, (k_tail_small<FIN, 64, 32, 16, A, R>), dim3((unsigned)((B + 4 * R - 1) / (4 * R))), dim3(256), lds, c.feat, n->fc1w,
                        n->fc1b, n->fc2w, n->fc2b, n->hw, n->hb, B, probs, value, dyn);
     return AZ_OK;
 }
 
-static int launch_tail(az_net *n, int B, float *probs, float *value, const int *dyn, hipStream_t st) {
-    if (!tail_v1()) {
-        AZ_LAUNCH((k_tail_mfma<192, 64, 32, 16, 7>), dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, n->feat, n->fc1w, n->fc1b, n->fc2w,
-                           n->fc2b, n->hw, n->hb, B, probs, value, dyn);
-        return AZ_OK;
-    }
-    static int r8 = -1;
-    if (r8 < 0) { const char *e = getenv("AZ_TAIL_R8_FROM"); r8 = e ? atoi(e) : 0x7fffffff; }
-    // 16 rows per workgroup (measured: 9.3 us up to 4096 rows, 12.7 us at 8192; 32 rows per workgroup: 19 us at every size)
-    return B >= r8 ? tail_go<192, 7, 8>(n, B, probs, value, dyn, st) : tail_go<192, 7, 4>(n, B, probs, value, dyn, st);
-}
-
-// the other planes between 5x5 and 8x8: k_trunk (one board per wave, direct form) at every batch size
-template <int CH, int CW>
-static int launch_trunk_plain(az_net *n, const float *in, int B, const int *dyn, hipStream_t st) {
-    using G = TrunkGeom<CH, CW>;
-    static bool attr_set = false;
-    static int lds_bytes = G::LDS_BYTES;
-    if (!attr_set) {
-        if (160 * 1024 / 3 > G::LDS_BYTES) lds_bytes = (160 * 1024 / 3) & ~15;  // three blocks per CU, as launch_trunk
-        AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trunk<CH, CW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
-    n->last_trunk_two_boards = 0;
-    AZ_LAUNCH((k_trunk<CH, CW, false>), dim3((B + 3) / 4), dim3(256), lds_bytes, st, in, B, dyn, n->tp, n->feat);
+// Connect4Net's fc1 + fc2 + heads as one launch
+static int launch_tail(az_net *n, LaunchCtx &c, const StagePlan &p, int B, float *probs, float *value, const int *dyn) {
+    if (p.kernel == K_TAIL_SMALL) return p.tail_r == 8 ? tail_go<192, 7, 8>(n, c, B, probs, value, dyn) : tail_go<192, 7, 4>(n, c, B, probs, value, dyn);
+    AZ_LAUNCH(c, (k_tail_mfma<192, 64, 32, 16, 7>), dim3((unsigned)((B + 15) / 16)), dim3(256), 0, c.feat, n->fc1w, n->fc1b, n->fc2w,
+                       n->fc2b, n->hw, n->hb, B, probs, value, dyn);
     return AZ_OK;
 }
 
-static int launch_trunk_other(az_net *n, const float *in, int B, const int *dyn, hipStream_t st) {
-#define PLANE(ch, cw) if (n->CH == ch && n->CW == cw) return launch_trunk_plain<ch, cw>(n, in, B, dyn, st);
-    PLANE(5, 5) PLANE(5, 6) PLANE(5, 7) PLANE(5, 8) PLANE(6, 5) PLANE(6, 7) PLANE(6, 8) PLANE(7, 5) PLANE(7, 7) PLANE(7, 8) PLANE(8, 5) PLANE(8, 6) PLANE(8, 7)
-#undef PLANE
-    az_set_error("no conv-trunk kernel instantiated for a %dx%d plane", n->CH, n->CW);
-    return AZ_EINVAL;
-}
-
-static int run_stage(az_net *n, int stage, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, hipStream_t st) {
-    if (stage >= 1 && tail_is_fused(n)) return stage == 1 ? launch_tail(n, B, d_probs, d_value, dyn, st) : AZ_OK;  // stages 2, 3 ran inside stage 1
-    switch (stage) {
-        case 0:
-            if (n->CH == 8 && n->CW == 8) return use_wino(8, 8) ? launch_trunk<8, 8, true>(n, d_input, B, dyn, st) : launch_trunk<8, 8, false>(n, d_input, B, dyn, st);
-            if (n->CH == 6 && n->CW == 6) return launch_trunk<6, 6, false>(n, d_input, B, dyn, st);
-            if (n->CH == 7 && n->CW == 6) return use_wino(7, 6) ? launch_trunk<7, 6, true>(n, d_input, B, dyn, st) : launch_trunk<7, 6, false>(n, d_input, B, dyn, st);
-            return launch_trunk_other(n, d_input, B, dyn, st);
-        case 1: return n->qd_on ? launch_qdense(n, 1, B, dyn, st) : launch_gemm(n->feat, n->fc1w, n->fc1wq, n->fc1b, n->h1, B, n->F1, n->FIN, true, dyn, st);
-        case 2: return n->qd_on ? launch_qdense(n, 2, B, dyn, st) : launch_gemm(n->h1, n->fc2w, n->fc2wq, n->fc2b, n->h2, B, n->F2, n->F1, true, dyn, st);
-        default: return launch_heads(n, B, d_probs, d_value, dyn, st);
+// one stage of the forward: plan it, launch the plan.  *slot: where az_net_profile books the stage
+static int run_stage(az_net *n, LaunchCtx &c, int stage, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, int *slot = nullptr) {
+    const StagePlan p = plan_stage(net_dims(n), net_tuning(), stage, B, c.beside);
+    if (slot) *slot = plan_slot(p);
+    switch (p.kernel) {
+        case K_NONE: return AZ_OK;  // the stage ran inside an earlier one's launch
+        case K_MLP: AZ_LAUNCH(c, k_mlp, dim3((B + 63) / 64), dim3(64), 0, d_input, B, dyn, n->mlp_dev, d_probs, d_value); return AZ_OK;
+        case K_TRUNK: case K_TRUNK_QUAD: case K_TRUNK_Q: case K_TRUNK2: return launch_trunk(n, c, p, d_input, B, dyn);
+        case K_TAIL_MFMA: case K_TAIL_SMALL: return launch_tail(n, c, p, B, d_probs, d_value, dyn);
+        case K_QDENSE_SMALL: case K_QGEMM: return launch_qdense(n, c, p, stage, B, dyn);
+        case K_HEADS_SMALL: case K_HEADS: case K_HEADS2: return launch_heads(n, c, p, B, d_probs, d_value, dyn);
+        default:  // K_DENSE_FRAG, K_DENSE_SMALL, K_GEMM, K_GEMM_SOLO, K_GEMM_SOLO_T
+            return launch_dense(c, p, stage == 1 ? Dense{c.feat, n->fc1w, n->fc1wq, n->fc1b, c.h1, B, n->F1, n->FIN, true, dyn}
+                                                 : Dense{c.h1, n->fc2w, n->fc2wq, n->fc2b, c.h2, B, n->F2, n->F1, true, dyn});
     }
 }
 
@@ -3999,11 +3789,7 @@ static int prof_harvest(az_net *n) {
             if (!(n->prof_has[i] & (1 << s))) continue;
             float ms = 0.0f;
             AZ_HIP(hipEventElapsedTime(&ms, n->prof_ev[((size_t)i * 4 + s) * 2], n->prof_ev[((size_t)i * 4 + s) * 2 + 1]));
-            const int kind = n->prof_kind[i];  // bit 0: k_trunk2, bit 1: k_trunk_q, bit 2 / 3: fc1 / fc2 on a small-batch kernel
-            int slot = s;
-            if (s == 0) slot = (kind & 1) ? 0 : ((kind & 2) ? 7 : 4);
-            else if (s == 1 && (kind & 4)) slot = 5;
-            else if (s == 2 && (kind & 8)) slot = 6;
+            const int slot = (n->prof_slot[i] >> (4 * s)) & 7;
             n->prof_ms[slot] += ms;
             n->prof_n[slot] += 1;
         }
@@ -4017,7 +3803,7 @@ extern "C" int az_net_profile(az_net *n, int enable) {
     AZ_REQUIRE(n, AZ_EINVAL, "null net");
     if (enable && n->prof_ev.empty()) {
         n->prof_ev.resize((size_t)PROF_SLOTS * 8);
-        n->prof_kind.assign(PROF_SLOTS, 0);
+        n->prof_slot.assign(PROF_SLOTS, 0);
         n->prof_has.assign(PROF_SLOTS, 0);
         for (auto &e : n->prof_ev) AZ_HIP(hipEventCreate(&e));
     }
@@ -4045,51 +3831,35 @@ extern "C" int az_net_profile_read(az_net *n, double *ms_total, int64_t *launche
     return AZ_OK;
 }
 
-static int forward_lane0(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream);
-
-// the forward on the activation rows of `lane`; beside: see g_beside
+// the forward on the activation rows of `lane`; beside: see LaunchCtx
 static int forward_impl(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream, int lane = 0, int beside = 0) {
     AZ_REQUIRE(n && d_input && d_probs && d_value, AZ_EINVAL, "null argument");
     const bool mlp = n->game == AZ_TICTACTOE;  // no activation rows: a lane is a name only
     const int n_lanes = mlp ? n->mlp_lanes : (int)n->lanes.size() + 1;
     AZ_REQUIRE(lane >= 0 && lane < n_lanes, AZ_EINVAL, "lane %d of %d (az_net_set_lanes)", lane, n_lanes);
     AZ_REQUIRE(lane == 0 || mlp || B <= n->lane_rows, AZ_EINVAL, "batch %d beyond the %d rows of lane %d", B, n->lane_rows, lane);
-    const az_net::Acts own = {n->feat, n->h1, n->h2};
-    if (lane > 0 && !mlp) { const az_net::Acts &a = n->lanes[lane - 1]; n->feat = a.feat; n->h1 = a.h1; n->h2 = a.h2; }
-    g_beside = beside;
-    const int rc = forward_lane0(n, d_input, B, dyn, d_probs, d_value, stream);
-    g_beside = 0;
-    n->feat = own.feat; n->h1 = own.h1; n->h2 = own.h2;
-    return rc;
-}
-
-static int forward_lane0(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream) {
     AZ_REQUIRE(n->committed, AZ_ESTATE, "az_net_commit has not been called since the last az_net_set_tensor");
     AZ_REQUIRE(B > 0 && B <= n->max_batch, AZ_EINVAL, "batch %d outside (0, max_batch=%d]", B, n->max_batch);
-    hipStream_t st = (hipStream_t)stream;
-    if (n->game == AZ_TICTACTOE) {
-        hipLaunchKernelGGL(k_mlp, dim3((B + 63) / 64), dim3(64), 0, st, d_input, B, dyn, n->mlp_dev, d_probs, d_value);
-        return AZ_OK;
-    }
-    if (!n->prof) {
-        for (int s = 0; s < 4; ++s) AZ_TRY(run_stage(n, s, d_input, B, dyn, d_probs, d_value, st));
+    const az_net::Acts rows = (lane > 0 && !mlp) ? n->lanes[lane - 1] : az_net::Acts{n->feat, n->h1, n->h2};
+    const LaunchCtx lane_ctx = {(hipStream_t)stream, beside, rows.feat, rows.h1, rows.h2};
+    if (!n->prof || mlp) {  // k_mlp is not profiled
+        LaunchCtx c = lane_ctx;
+        for (int s = 0; s < 4; ++s) AZ_TRY(run_stage(n, c, s, d_input, B, dyn, d_probs, d_value));
         return AZ_OK;
     }
     if (n->prof_used == PROF_SLOTS) AZ_TRY(prof_harvest(n));
     hipEvent_t *ev = n->prof_ev.data() + (size_t)n->prof_used * 8;
-    int kind = 0, has = 0, rc = AZ_OK;
-    for (int s = 0; s < 4 && rc == AZ_OK; ++s) {
-        g_last_gemm_small = 0;
-        g_ev_start = ev[2 * s]; g_ev_stop = ev[2 * s + 1]; g_ev_used = 0;
-        rc = run_stage(n, s, d_input, B, dyn, d_probs, d_value, st);
-        g_ev_start = g_ev_stop = nullptr;
-        if (g_ev_used) has |= 1 << s;
-        if (s == 0) kind |= n->last_trunk_two_boards ? 1 : (n->last_trunk_q ? 2 : 0);
-        if ((s == 1 || s == 2) && g_last_gemm_small) kind |= s == 1 ? 4 : 8;
+    int slots = 0, has = 0;
+    for (int s = 0; s < 4; ++s) {
+        LaunchCtx c = lane_ctx;
+        c.ev_start = ev[2 * s]; c.ev_stop = ev[2 * s + 1];
+        int slot = 0;
+        AZ_TRY(run_stage(n, c, s, d_input, B, dyn, d_probs, d_value, &slot));
+        if (c.ev_used) has |= 1 << s;
+        slots |= slot << (4 * s);
     }
-    AZ_TRY(rc);
     n->prof_has[n->prof_used] = has;
-    n->prof_kind[n->prof_used++] = kind;
+    n->prof_slot[n->prof_used++] = slots;
     return AZ_OK;
 }
 
@@ -4146,10 +3916,11 @@ extern "C" int az_net_time_stage(az_net *n, int stage, int B, int iters, void *s
     AZ_HIP(hipMemsetAsync(in, 0, (size_t)B * n->H * n->W * sizeof(float), st));
     hipEvent_t e0, e1;
     AZ_HIP(hipEventCreate(&e0)); AZ_HIP(hipEventCreate(&e1));
+    LaunchCtx c = {st, 0, n->feat, n->h1, n->h2};  // a lone launch on lane 0
     int rc = AZ_OK;
     for (int it = -2; it < iters && rc == AZ_OK; ++it) {  // two untimed warm-up launches
         if (it == 0) (void)hipEventRecord(e0, st);
-        rc = stage < 0 ? az_net_forward(n, in, B, pr, va, st) : run_stage(n, stage, in, B, nullptr, pr, va, st);
+        rc = stage < 0 ? az_net_forward(n, in, B, pr, va, st) : run_stage(n, c, stage, in, B, nullptr, pr, va);
     }
     (void)hipEventRecord(e1, st);
     (void)hipEventSynchronize(e1);
@@ -4161,30 +3932,11 @@ extern "C" int az_net_time_stage(az_net *n, int stage, int B, int iters, void *s
     return rc;
 }
 
-// Name of the kernel stage `stage` (0 trunk, 1 fc1, 2 fc2, 3 heads) launches for a batch of B boards: what rocprofv3 lists the
-// launch under (template arguments abbreviated).  bench.py labels its roofline object with it.
+// Name of the kernel family stage `stage` (0 trunk, 1 fc1, 2 fc2, 3 heads) of a lone launch of B boards runs on: the plan's, so what
+// rocprofv3 lists the launch under (template arguments abbreviated).  bench.py labels its roofline object with it.
 extern "C" int az_net_stage_kernel(const az_net *n, int stage, int B, char *buf, int cap) {
     AZ_REQUIRE(n && buf && cap > 0 && stage >= 0 && stage <= 3 && B > 0, AZ_EINVAL, "bad arguments");
-    const char *name = "";
-    if (n->game == AZ_TICTACTOE) name = "k_mlp";
-    else if (stage >= 1 && tail_is_fused(n)) name = tail_v1() ? "k_tail_small" : "k_tail_mfma";
-    else if (stage == 0) {
-        const bool tuned = (n->CH == 8 && n->CW == 8) || (n->CH == 6 && n->CW == 6) || (n->CH == 7 && n->CW == 6);
-        name = (tuned && !trunk_v1() && B >= 4096) ? (use_wino(n->CH, n->CW) ? "k_trunk2<Winograd conv2>" : "k_trunk2") : ((tuned && B <= trunk_q_max()) ? "k_trunk_q" : "k_trunk");
-    }
-    else if (stage == 3) name = (B <= heads_small_max(n) && n->NH <= 128 && n->F2 % 32 == 0) ? "k_heads_small" : (n->F2 == 512 ? "k_heads2" : "k_heads");
-    else if (n->qd_on) name = qd_small_serves(B, stage == 1 ? n->F1 : n->F2, stage == 1 ? n->FIN : n->F1) ? "k_qdense_small" : "k_q_rows + k_qgemm";
-    else {
-        const int N = stage == 1 ? n->F1 : n->F2, K = stage == 1 ? n->FIN : n->F1;
-        switch (gemm_kind(B, N, K, (stage == 1 ? n->fc1wq : n->fc2wq) != nullptr)) {
-            case GK_SMALL: name = "k_dense_small"; break;
-            case GK_FRAG: name = "k_dense_frag"; break;
-            case GK_SOLO: name = "k_gemm_solo"; break;
-            case GK_SOLO_T: name = "k_gemm_solo_t"; break;
-            default: name = "k_gemm"; break;
-        }
-    }
-    snprintf(buf, (size_t)cap, "%s", name);
+    snprintf(buf, (size_t)cap, "%s", plan_family_name(plan_stage(net_dims(n), net_tuning(), stage, B, 0)));
     return AZ_OK;
 }
 

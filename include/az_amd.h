@@ -133,7 +133,7 @@ int64_t az_net_flops_per_board(const az_net *net);
 /* times `iters` back-to-back launches of one forward stage with HIP events on `stream`;
  * stage: 0 conv trunk, 1 fc1, 2 fc2, 3 heads, -1 whole forward.  *ms_per_launch out. */
 int az_net_time_stage(az_net *net, int stage, int B, int iters, void *stream, float *ms_per_launch);
-/* name of the kernel that stage (0..3) launches for a batch of B boards, as rocprofv3 lists it (template arguments abbreviated) */
+/* name of the kernel family of the plan for stage (0..3) of a lone launch of B boards, as rocprofv3 lists it (template arguments abbreviated) */
 int az_net_stage_kernel(const az_net *net, int stage, int B, char *buf, int cap);
 /* Live measurement (the idiom of timers.py:53-76 applied per kernel): while enabled, every forward brackets its stage
  * launches with a start and a stop event each (hipExtLaunchKernelGGL).  ms_total[8] / launches[8], one slot per kernel family so that a slot's mean is the

@@ -2,7 +2,7 @@
 as 2 groups from 4096 to 8191 slots and Connect4 6x7 as 4 groups from 8192 slots; every group forwards on its own lane of the az_net
 with beside = 1.  A run replays captured graphs, whose launch sizes must not change: below 4096 rows a chain's network launch keeps
 the chain's full width for the whole run and only the device row count falls as games end; from 4096 rows the cap follows the live
-slots in steps of 512 (do_search: cap_q).  The kernels per shape (az_net.hip: gemm_kind, launch_gemm, launch_trunk, trunk_quad):
+slots in steps of 512 (do_search: cap_q).  The kernels per shape (az_net_plan.h: plan_trunk, plan_dense):
 
   othello8, 2112 slots   2 x 1056: k_trunk_quad, k_gemm<64,64> (fc1) and k_gemm<64,128> (fc2), just above k_dense_frag's beside limit;
                          4 x 528 (lanes 2 and 3 in use): k_trunk_quad + k_dense_frag;  1 x 2112: k_trunk, k_gemm<64,64> twice

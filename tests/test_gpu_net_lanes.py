@@ -1,6 +1,6 @@
 """GPU: the lanes of one az_net (az_net_set_lanes / az_net_forward_lane) at the sizes a grouped az_engine_run puts on
-them.  A slot group forwards on its own lane with beside = 1, and beside changes the kernel picks by the launch's size (az_net.hip:
-g_beside, gemm_kind, launch_gemm, launch_trunk, trunk_quad).  OthelloNet 8x8, rows B of the launch, lone launch | beside:
+them.  A slot group forwards on its own lane with beside = 1, and beside changes the kernel picks by the launch's size
+(az_net_plan.h: plan_trunk, plan_dense; pinned without a GPU in test_net_plan_host.py).  OthelloNet 8x8, rows B of the launch, lone launch | beside:
 
   trunk   B <= 512 k_trunk_q | k_trunk_q;  513 .. 4095 k_trunk | k_trunk_quad;  from 4096 k_trunk2 | k_trunk2
   fc1     (K = 512, N = 1024)  B <= 1024 k_dense_frag | k_dense_frag;  1025 .. 3968 k_gemm<64,64> | k_gemm<64,64>;
@@ -15,8 +15,8 @@ are the thresholds read, not asserted (a kernel trace of the beside forwards at 
 Every kernel of a layer keeps each output element's k-ordered chain, so every comparison here is bit equality with the CPU oracle:
 600 boards per network evaluated once, larger batches built from them by index.
 
-One host thread drives the net throughout.  forward_impl points n->feat / h1 / h2 at the lane's rows for the duration of the call, so
-two host threads on one az_net are not a supported use and are not tested."""
+One host thread drives the net throughout: az_net_forward_lane's contract (include/az_amd.h) is lanes on different streams issued from
+one host thread, and two host threads on one az_net are not tested."""
 import ctypes as C
 
 import numpy as np
@@ -143,6 +143,32 @@ def test_four_forwards_in_flight(name, R, counts):
     for r in range(ROUNDS):
         for lane in range(4):
             expect(outs[r][lane], op, ov, idx[lane], counts[lane], (name, R, "round", r, "lane", lane))
+
+
+def test_beside_reaches_the_launch_and_the_profile_slot():
+    """beside travels from az_net_forward_lane to the stage's plan, and the plan's slot to az_net_profile: at 2048 rows a lone forward
+    books fc2 under "small fc2" (k_dense_frag), a beside one under "k_gemm fc2" (the 64x64 tile); both book the trunk under "k_trunk"
+    (k_trunk | k_trunk_quad) and fc1 under "k_gemm fc1".  Same bits from both, and they are the oracle's."""
+    game, gid, H, W, A, n = TAGS["othello8"]
+    from test_gpu_net import nets
+    fx, sd, onet, other = nets("othello8")
+    other.close()
+    _, x, op, ov, _ = ctx("othello8")
+    hnet = E.HipNet(gid, H, W, sd, max_batch=2048)
+    idx = index_map(2048)
+    xx = x[idx].contiguous()
+    c = torch.tensor([2048], dtype=torch.int32, device="cuda")
+    hnet.profile(True)
+    lone = hnet.forward(xx)
+    counts = {k: v[1] for k, v in hnet.profile_read().items()}
+    assert counts == {"k_trunk2": 0, "k_gemm fc1": 1, "k_gemm fc2": 0, "k_heads": 1, "k_trunk": 1, "small fc1": 0, "small fc2": 1, "k_trunk_q": 0}, counts
+    beside = outputs(2048, A)
+    launch(hnet, 0, 1, xx, c, *beside)
+    counts = {k: v[1] for k, v in hnet.profile_read().items()}
+    assert counts == {"k_trunk2": 0, "k_gemm fc1": 2, "k_gemm fc2": 1, "k_heads": 2, "k_trunk": 2, "small fc1": 0, "small fc2": 1, "k_trunk_q": 0}, counts
+    assert torch.equal(lone[0], beside[0]) and torch.equal(lone[1].reshape(-1), beside[1])
+    expect(beside, op, ov, idx, 2048, "beside, profiled")
+    hnet.close()
 
 
 def test_set_lanes_bookkeeping():

@@ -95,7 +95,7 @@ def test_row_independence(tag):
 
 @pytest.mark.parametrize("H,W", [(7, 7), (6, 8)])
 def test_untuned_plane(H, W):
-    """the planes of launch_trunk_other run k_trunk (every board its own tiles) at every size: 7x7 and 8x6 at 5 and 6 boards -- a full
+    """the planes plane_tuned leaves out run k_trunk (every board its own tiles) at every size: 7x7 and 8x6 at 5 and 6 boards -- a full
     workgroup and one of 1 and 2 boards"""
     from alphazero_amd.games.connect4 import Connect4Net
     torch.manual_seed(10 * H + W)
