@@ -68,6 +68,7 @@ SYMBOLS = [
     "az_engine_set_gumbel", "az_engine_gumbel_considered", "az_engine_set_gumbel_batch", "az_gumbel_locksteps",
     "az_engine_set_gumbel_full", "az_engine_root_value",
     "az_engine_set_playout_cap", "az_engine_playout_cap_stats", "az_playout_cap_full",
+    "az_engine_set_forced_playouts", "az_engine_forced_playouts_stats", "az_forced_playout", "az_forced_prune",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
     "az_trainer_steps", "az_trainer_check", "az_trainer_debug", "az_trainer_buffer",
 ]
@@ -142,6 +143,10 @@ def lib():
     L.az_engine_set_playout_cap.argtypes = [vp, i32, C.c_double]
     L.az_engine_playout_cap_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.az_playout_cap_full.argtypes = [C.c_uint32, C.c_uint32, i32, C.c_double]
+    L.az_engine_set_forced_playouts.argtypes = [vp, C.c_double]
+    L.az_engine_forced_playouts_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.az_forced_playout.argtypes = [i32, C.c_double, i32, C.c_double]
+    L.az_forced_prune.argtypes = [i32, vp, vp, vp, i32, C.c_double, vp]
     L.az_augment_count.argtypes = [C.c_int, vp, i64, C.POINTER(i64), vp]
     L.az_augment.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.az_engine_root_children.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]

@@ -6,6 +6,9 @@
 // az_engine_set_leaf_batch walks K simulations per game and lock-step with virtual loss -- k_step_multi below, another search.)
 // (Opt-in, default off: az_engine_set_playout_cap searches most plies with a few simulations and records the fully searched ones only --
 // k_step_cap below, k_step with a per-slot simulation budget.)
+// (Opt-in, default off: az_engine_set_forced_playouts gives every visited root child of a fully searched ply at least sqrt(k P N_root)
+// playouts and takes the ones PUCT would not have spent out of the policy target again -- k_step_forced below, forced_playout /
+// forced_pruned and move_policy.)
 // (Opt-in, default off: az_engine_set_gumbel replaces the root's PUCT pick by Sequential Halving over actions sampled with Gumbel
 // noise and reads the root out by the completed Q-values -- k_step_gumbel below, another search again; az_engine_set_gumbel_batch
 // walks up to K simulations of a Sequential Halving phase per game and lock-step -- k_step_gumbel_multi.)
@@ -60,6 +63,7 @@
 
 enum { CTR_SAMPLES = 0, CTR_GAMES_DONE, CTR_NET_EVALS, CTR_NEXT_GAME, CTR_TOTAL_GAMES, CTR_FIRST_ID, CTR_PLIES,
        CTR_FULL_PLIES, CTR_FAST_PLIES,  // az_engine_set_playout_cap: the plies k_move played after a full / a fast search (counted while the mode is on)
+       CTR_FORCED_PICKS, CTR_PRUNED,    // az_engine_set_forced_playouts: root selections with a forced child / playouts pruned from the recorded targets
        CTR_COUNT };
 // entries beyond CTR_COUNT live as long as the engine (k_reset_all clears [0, CTR_COUNT) only)
 enum { CTR_COLLISIONS = CTR_COUNT, CTR_ALLOC };
@@ -122,6 +126,10 @@ struct EngDev {
     int cap_nfast;
     double cap_pfull;
     int *budget;
+    // az_engine_set_forced_playouts (k_step_forced, move_policy): kforced = KataGo's k (0: off); fpicks [G] = the slot's root selections
+    // with a forced child since its last move (k_move folds them into ctr[], as evals).  Null unless the mode is on: then no kernel touches it.
+    double kforced;
+    int *fpicks;
 };
 #define CAP_FULL 0x7fffffff  // the budget of a full ply: every simulation of any search call, and the mark root noise asks for
 
@@ -316,6 +324,52 @@ AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int d
 }
 
 // ---------------------------------------------------------------------------------------------
+// Forced playouts and policy target pruning (az_engine_set_forced_playouts; KataGo: Wu 2019, section 3.2).
+// Every operation is one IEEE double operation in the order written (-ffp-contract=off), sqrt the correctly rounded one of PUCT.
+//   switch      k > 0 on (KataGo: 2), k = 0 off; finite and in [0, 64].
+//   forced ply  a ply of a slot this engine searches, the mode on, that is full in the playout cap's sense: every ply with the cap
+//               off, the plies whose coin playout_cap_full(seed, game id, ply, p_full) says full with it on.
+//   selection   at depth 0 of the walk on a forced ply only.  R.N = the root's visit count as PUCT's square root takes it there.
+//               Child c is FORCED iff c.N > 0 && (double)c.N * (double)c.N < (k * c.P) * (double)R.N  (c.P the stored prior, root
+//               noise included; no square root).  A forced child's key is +inf, every other child keeps its PUCT key, and
+//               choose_max_grp runs unchanged: several forced children are an ordinary tie (AZ_TIE_RANDOM: the AZ_P_TIE_SELECT
+//               draw of that (ply, sim, depth 0); AZ_TIE_LOWEST: the lowest index).  A fresh root has R.N = 0: nothing is forced.
+//               A root inherited through k_reroot applies the rule to the counts it inherited.  Below the root nothing changes.
+//   pruning     wherever move_policy runs on a forced ply at a temperature other than 0.  c* = the child with the greatest N
+//               (lowest index among equals, no draw); sq = sqrt((double)R.N); star = c*.Q + (c*.P * sq) / (double)(1 + c*.N).
+//               N' = N for c* and for children with N = 0.  Every other child:
+//                 nf = (int)sqrt((k * c.P) * (double)R.N);  gap = star - c.Q;
+//                 need = c.N if gap <= 0.0; else want = (c.P * sq) / gap - 1.0, need = c.N if want >= (double)c.N,
+//                 else (int)floor(want) + 1;
+//                 N' = min(c.N, max(c.N - nf, need, 0));  if N' < c.N && N' <= 1 then N' = 0.
+//               The temperature formula takes N' in place of N for the recorded pi and the move drawn from it (the same
+//               AZ_P_MOVE_SAMPLE draw).  Temperature 0 (fair_max on the raw counts, one-hot pi), the visits rows and the Gumbel
+//               branch do not change.
+//   counters    forced_picks = the root selections in which at least one child was forced (counted per slot in fpicks[g], folded by
+//               k_move once per ply); pruned_playouts = the sum of N - N' over the plies k_move recorded.  Both 0 with the mode off.
+// The two rules as host-callable arithmetic (az_forced_playout / az_forced_prune are these on the host):
+// ---------------------------------------------------------------------------------------------
+AZ_HD bool forced_playout(int n, double p, int root_n, double k) {
+    return n > 0 && (double)n * (double)n < (k * p) * (double)root_n;
+}
+// the pruned count of a child that is not c*: sq and star as above
+AZ_HD int forced_pruned(int n, double q, double p, int root_n, double sq, double star, double k) {
+    if (n == 0) return 0;
+    const int nf = (int)sqrt((k * p) * (double)root_n);
+    const double gap = star - q;
+    int need = n;
+    if (!(gap <= 0.0)) {
+        const double want = (p * sq) / gap - 1.0;
+        need = want >= (double)n ? n : (int)floor(want) + 1;
+    }
+    int m = n - nf;
+    m = need > m ? need : m;
+    m = m < 0 ? 0 : m;
+    m = m < n ? m : n;
+    return (m < n && m <= 1) ? 0 : m;
+}
+
+// ---------------------------------------------------------------------------------------------
 // PUCT selection (mcts.py:44-46, 137) for k_step and k_step_multi.  k_step is walker j = 0 of a lock-step of one: no virtual count.
 // leaf_batch = K > 1 (az_engine_set_leaf_batch): K simulations per slot and lock-step, kept apart by virtual loss.
 // The reference searches strictly one simulation after the other (mcts.py:127-171 select_node, 197-223 back_propagate,
@@ -330,8 +384,11 @@ AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int d
 // Virtual counts are never stored in a node: lane d of the group keeps the d-th node of every earlier walker's path (vpath), and a
 // child at depth d + 1 is compared with path_i[d + 1] fetched from lane d + 1 by shuffle.
 // ---------------------------------------------------------------------------------------------
+// FORCED (az_engine_set_forced_playouts; the k_step_forced kernels only): with kf > 0 -- the root of a forced ply -- a child that
+// forced_playout names takes the key +inf, and *forced_pick is raised when there was one; everything behind the keys is unchanged.
+template <bool FORCED = false>
 AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
-                           int ply, int sim, int depth, int sub, Node &chosen) {
+                           int ply, int sim, int depth, int sub, Node &chosen, double kf = 0.0, bool *forced_pick = nullptr) {
     const int fc = parent.first;
     int vp = 0, vc[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -346,14 +403,17 @@ AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node 
     }
     const double sq = sqrt((double)(parent.N + vp));
     Scored s;
+    bool forced = false;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         Node c;
         if (load_child_grp(pool, parent, r, sub, s, c)) {
             const double q = vc[r] == 0 ? c.Q : ((double)c.N * c.Q - (double)vc[r]) / (double)(c.N + vc[r]);
             s.key[r] = q + (c.P * sq) / (double)(1 + c.N + vc[r]);
+            if (FORCED && kf > 0.0 && forced_playout(c.N, c.P, parent.N + vp, kf)) { s.key[r] = __builtin_inf(); forced = true; }
         }
     }
+    if (FORCED && kf > 0.0 && grp_ballot(forced) != 0) *forced_pick = true;  // kf is uniform over the group
     // every lane votes, and NaN scores (a diverged network) are an error: no key equals the maximum
     return fc + choose_max_grp(E, E.game_id[g], ply, sim, depth, s, 4 * LPG, ERR_INTERNAL, sub, chosen);
 }
@@ -372,8 +432,10 @@ AZ_D int pick_child_gumbel_grp(const EngDev &E, int g, const Node *pool, const N
 
 // select_node's descent (mcts.py:127-171) of walker j, from wk (the root, or wherever wk stands) to its leaf.  GUMBEL: the children
 // are scored by pick_child_gumbel_grp instead of PUCT (the full Gumbel kernels only; every other kernel takes the default).
-template <bool GUMBEL = false>
-AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], int j, int ply, int sim, int sub, Walk &wk) {
+// FORCED: the selection at depth 0 applies the forced-playout rule with kf (0: not a forced ply); below the root nothing changes.
+template <bool GUMBEL = false, bool FORCED = false>
+AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], int j, int ply, int sim, int sub, Walk &wk,
+                   double kf = 0.0, bool *forced_pick = nullptr) {
     for (;;) {
         bool fresh = false;
         if (!(wk.cur.flags & F_EXPANDED)) {
@@ -385,7 +447,8 @@ AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], 
         }
         Node ch;
         const int c = GUMBEL ? pick_child_gumbel_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch)
-                             : pick_child_vl_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch);
+                             : pick_child_vl_grp<FORCED>(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch,
+                                                         FORCED && wk.plen == 1 ? kf : 0.0, forced_pick);
         wk.node = c; wk.cur = ch;
         if (sub == wk.plen) wk.my_path = c;
         ++wk.plen;
@@ -533,6 +596,7 @@ AZ_D void reset_slot(const EngDev &E, int g, u32 game_id) {
     E.root_p1[g] = b.p1; E.root_m1[g] = b.m1; E.root_player[g] = (int8_t)b.player;
     E.root[g] = 0; E.n_nodes[g] = 1; E.ply[g] = 0; E.game_id[g] = game_id; E.active[g] = 1;
     E.leaf_status[g] = LS_NONE; E.evals[g] = 0; E.side[g] = 0; E.gmask[g] = 0;
+    if (E.fpicks) E.fpicks[g] = 0;
     store_node(pool_of(E, g), fresh_node(0, -1, 0.0, 0));
 }
 
@@ -613,7 +677,10 @@ __device__ unsigned long long az_step_probe[4096 * 8];
 // wrote the budget: CAP_FULL on a full ply, n_fast on a fast one) and takes root noise on a full ply only.  A slot past its budget
 // stays an inert group for the SELECT half -- no walk, no row, leaf_status LS_NONE, so the next BACKUP does nothing for it -- and
 // still reaches every barrier of alloc_rows_block; it is NOT deactivated.  CAP false is the kernel as it always was.
-template <bool BACKUP, bool SELECT, bool CAP>
+// FORCED (az_engine_set_forced_playouts, k_step_forced / k_step_cap_forced): on a full ply (budget == CAP_FULL) the root's selection
+// is walk_grp's forced one with k = kforced, and the group's first lane counts the selections that had a forced child in fpicks[g],
+// with the pending-leaf stores.  FORCED false is the kernel as it was.
+template <bool BACKUP, bool SELECT, bool CAP, bool FORCED>
 AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
@@ -647,6 +714,7 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
     BB b = {E.root_p1[gs], E.root_m1[gs], E.root_player[gs]};
     int node = E.root[gs];
     const int budget = CAP ? E.budget[gs] : CAP_FULL;  // with the loads above: no round trip of its own
+    const int fpicks = (FORCED && SELECT) ? E.fpicks[gs] : 0;
     Node fwd;
     bool have_root = false;
     PSTAMP(1)
@@ -691,6 +759,7 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
     int status = LS_NONE, w = 0;
     Walk wk = {b, Node(), node, 1, sub == 0 ? node : -1, false};
     const bool walks = active && (!CAP || sim < budget);  // uniform over the game's group
+    bool forced_pick = false;
     if (walks) {
         if (have_root) wk.cur = fwd; else wk.cur = load_node(pool + node);
         const bool noise_ply = !CAP || budget == CAP_FULL;  // a fast ply takes no root noise and leaves F_NOISED clear
@@ -701,7 +770,8 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
         }
         PSTAMP(4)
         const int no_walkers[MLB] = {};  // walker j = 0: nobody walked before it in this lock-step, every virtual count is 0
-        walk_grp(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
+        if (FORCED) walk_grp<false, true>(E, g, pool, no_walkers, 0, ply, sim, sub, wk, budget == CAP_FULL ? E.kforced : 0.0, &forced_pick);
+        else walk_grp(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
         PSTAMP(5)
         E.path[(size_t)g * LPG + sub] = wk.my_path;
         if (sub == 0) { E.path_len[g] = wk.plen; if (wk.plen > LPG) atomicMax(E.max_path, wk.plen); }
@@ -716,6 +786,7 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
         if (walks) {
             E.leaf[g] = wk.node; E.leaf_p1[g] = wk.b.p1; E.leaf_m1[g] = wk.b.m1; E.leaf_player[g] = (int8_t)wk.b.player;
             E.leaf_winner[g] = (int8_t)w;
+            if (FORCED && forced_pick) E.fpicks[g] = fpicks + 1;
         }
         E.leaf_status[g] = (int8_t)status;
     }
@@ -731,9 +802,14 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
 
 // the plain search's lock-step, under the name and with the code it always had, and the playout cap's
 template <bool BACKUP, bool SELECT>
-__global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, false>(E, sim, g0, g1); }
+__global__ __launch_bounds__(256) void k_step(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, false, false>(E, sim, g0, g1); }
 template <bool BACKUP, bool SELECT>
-__global__ __launch_bounds__(256) void k_step_cap(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, true>(E, sim, g0, g1); }
+__global__ __launch_bounds__(256) void k_step_cap(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, true, false>(E, sim, g0, g1); }
+// and the two of az_engine_set_forced_playouts: the same lock-steps with the forced root selection, without and with the playout cap
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_forced(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, false, true>(E, sim, g0, g1); }
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_cap_forced(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, true, true>(E, sim, g0, g1); }
 
 // One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
 // SELECT of kt walkers.  Lane j of the game's group owns walker j's pending words (loaded / stored coalesced, handed round by
@@ -1530,7 +1606,24 @@ AZ_D int gumbel_move_policy(const EngDev &E, const Node *pool, int fc, int nc, u
     return pick;
 }
 
-AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc, double temp, u32 gid, int ply, u64 gmask, float *pi) {
+// Is (gid, ply) a forced ply of az_engine_set_forced_playouts?  Its k, or 0: the mode on, and the ply full under the playout cap.
+// k_root_readout and k_player_moves ask here; k_move has drawn the coin already and passes its own `fast`.
+AZ_D double forced_ply_k(const EngDev &E, u32 gid, int ply) {
+    return (E.kforced > 0.0 && (E.cap_nfast == 0 || playout_cap_full(E.seed, gid, ply, E.cap_pfull))) ? E.kforced : 0.0;
+}
+
+// the count the temperature formula takes for child i: the raw N, or on a forced ply (kf > 0) the pruned one (no per-thread array:
+// the second pass over the children computes it again)
+AZ_D int policy_count(const Node *pool, int fc, int i, double kf, int root_n, int cstar, double sq, double star) {
+    const int n = pool[fc + i].N;
+    if (!(kf > 0.0) || i == cstar) return n;
+    return forced_pruned(n, pool[fc + i].Q, pool[fc + i].P, root_n, sq, star, kf);
+}
+
+// kf: forced_ply_k of the ply (0: raw counts, the function as it always was); *pruned (when given): the sum of N - N' over the children.
+AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc, double temp, u32 gid, int ply, u64 gmask, float *pi,
+                     double kf = 0.0, int *pruned = nullptr) {
+    if (pruned) *pruned = 0;
     if (E.gm > 0) return gumbel_move_policy(E, pool, fc, nc, gmask, gid, ply, E.nval ? nval_of(E, pool) + root : nullptr, pi);
     if (temp == 0.0) {  // fair_max by N
         int best = -1, cnt = 0, first = 0;
@@ -1549,11 +1642,24 @@ AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc
         return pick;
     }
     const double inv_temp = 1.0 / temp;
+    // policy target pruning (the contract above forced_playout): c*, sq and star once, then N' wherever a count is read
+    int root_n = 0, cstar = 0;
+    double sq = 0.0, star = 0.0;
+    if (kf > 0.0) {
+        root_n = pool[root].N;
+        for (int i = 1; i < nc; ++i) if (pool[fc + i].N > pool[fc + cstar].N) cstar = i;
+        sq = sqrt((double)root_n);
+        star = pool[fc + cstar].Q + (pool[fc + cstar].P * sq) / (double)(1 + pool[fc + cstar].N);
+    }
     double sum = 0.0;
+    int cut = 0;
     for (int i = 0; i < nc; ++i) {
-        double n = (double)pool[fc + i].N;
+        const int ni = policy_count(pool, fc, i, kf, root_n, cstar, sq, star);
+        cut += pool[fc + i].N - ni;
+        double n = (double)ni;
         sum += (temp == 1.0) ? n : az_det_pow(n, inv_temp);
     }
+    if (pruned) *pruned = cut;
     double u = 2.0, cum = 0.0;
     if (nc > 1) {
         Philox4 r = az_philox(E.seed, gid, (u32)ply, 0xFFFFu, AZ_P_MOVE_SAMPLE, 0);
@@ -1561,7 +1667,7 @@ AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc
     }
     int chosen = 0, last = 0; bool found = false;
     for (int i = 0; i < nc; ++i) {
-        double n = (double)pool[fc + i].N;
+        double n = (double)policy_count(pool, fc, i, kf, root_n, cstar, sq, star);
         double p = ((temp == 1.0) ? n : az_det_pow(n, inv_temp)) / sum;
         if (pi) pi[pool[fc + i].act] = (float)p;
         if (p > 0.0) last = i;
@@ -1600,7 +1706,8 @@ __global__ void k_move(EngDev E, int g0, int g1) {
     int *vis = si >= 0 ? E.o_visits + (size_t)si * E.A : nullptr;
     if (si >= 0) for (int a = 0; a < E.A; ++a) { pi[a] = 0.0f; vis[a] = 0; }
 
-    const int chosen = fc + move_policy(E, pool, root, fc, nc, temp, gid, ply, E.gmask[g], pi);
+    int pruned = 0;  // az_engine_set_forced_playouts: the playouts a forced ply's target lost (0 with the mode off, on a fast ply, at temperature 0)
+    const int chosen = fc + move_policy(E, pool, root, fc, nc, temp, gid, ply, E.gmask[g], pi, fast ? 0.0 : E.kforced, &pruned);
     E.gmask[g] = 0;  // the candidates belong to the root that is left here
     int action = pool[chosen].act;
     if (si >= 0) {
@@ -1621,6 +1728,11 @@ __global__ void k_move(EngDev E, int g0, int g1) {
     if (E.cap_nfast > 0) atomicAdd(&E.ctr[fast ? CTR_FAST_PLIES : CTR_FULL_PLIES], 1ULL);
     atomicAdd(&E.ctr[CTR_NET_EVALS], (unsigned long long)E.evals[g]);
     E.evals[g] = 0;
+    if (E.fpicks) {  // the forced root selections of this ply's searches, and what pruning took from the target it recorded
+        if (E.fpicks[g]) atomicAdd(&E.ctr[CTR_FORCED_PICKS], (unsigned long long)E.fpicks[g]);
+        E.fpicks[g] = 0;
+        if (si >= 0 && pruned) atomicAdd(&E.ctr[CTR_PRUNED], (unsigned long long)pruned);
+    }
     atomicMax(E.max_nodes, E.n_nodes[g]);
     int w = 0;
     if (az_status(gd, b, &w)) {  // trainer.py:235, 262-265
@@ -1772,7 +1884,7 @@ __global__ void k_player_moves(EngDev E, double temp, int *actions) {
     const Node *pool = pool_of(E, g);
     const int root = E.root[g], fc = pool[root].first, nc = pool[root].nch;
     if (nc == 0 || !(pool[root].flags & F_EXPANDED)) return;
-    actions[g] = pool[fc + move_policy(E, pool, root, fc, nc, temp, E.game_id[g], E.ply[g], E.gmask[g], nullptr)].act;
+    actions[g] = pool[fc + move_policy(E, pool, root, fc, nc, temp, E.game_id[g], E.ply[g], E.gmask[g], nullptr, forced_ply_k(E, E.game_id[g], E.ply[g]))].act;
 }
 
 // Root readout for slots [0, n) in one launch: everything Player.get_move returns (players.py:158-191: the move, get_action_probs,
@@ -1839,7 +1951,7 @@ __global__ __launch_bounds__(256) void k_root_readout(EngDev E, int n, const dou
         if (served && (o.pi || o.action)) {
             const int ply = E.ply[g];
             const double temp = temps ? temps[g] : linear_temp(ply, E.tmax, E.tmin);
-            act = pool[fc + move_policy(E, pool, E.root[g], fc, nc, temp, E.game_id[g], ply, E.gmask[g], o.pi ? o.pi + (size_t)g * A : nullptr)].act;
+            act = pool[fc + move_policy(E, pool, E.root[g], fc, nc, temp, E.game_id[g], ply, E.gmask[g], o.pi ? o.pi + (size_t)g * A : nullptr, forced_ply_k(E, E.game_id[g], ply))].act;
         }
         if (o.action) o.action[g] = act;
         if (o.root_N) o.root_N[g] = served ? rn.N : 0;
@@ -2098,6 +2210,9 @@ struct az_engine {
     // az_engine_set_playout_cap: the per-slot budgets, [G], allocated when the mode first goes on; in force (d.budget == cap_budget,
     // d.cap_nfast > 0) only while it is on, else d.budget is null
     int *cap_budget = nullptr;
+    // az_engine_set_forced_playouts: the per-slot counts of forced root selections, [G], allocated when the mode first goes on; in
+    // force (d.fpicks == forced_picks, d.kforced > 0) only while it is on, else d.fpicks is null
+    int *forced_picks = nullptr;
     int groups_req = 0;
     bool groups_env = false;
     hipStream_t gstream[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2194,6 +2309,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.gm = 0; d.g_cvisit = 0.0; d.g_cscale = 0.0; d.g_scale = 0.0;
     d.nval = nullptr;
     d.cap_nfast = 0; d.cap_pfull = 1.0; d.budget = nullptr;
+    d.kforced = 0.0; d.fpicks = nullptr;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2388,6 +2504,20 @@ static int enqueue_search(az_engine *e, const Chain &c, int n_sim, int cap) {
         return AZ_OK;
     }
 #undef GUMBEL_LAUNCH
+    if (d.kforced > 0.0) {  // forced playouts: k_step's launch sequence with k_step_forced, or k_step_cap's with k_step_cap_forced
+#define FORCED_LAUNCH(B, S, ...) do { \
+        if (d.budget) hipLaunchKernelGGL((k_step_cap_forced<B, S>), gg, gb, 0, c.st, __VA_ARGS__); \
+        else hipLaunchKernelGGL((k_step_forced<B, S>), gg, gb, 0, c.st, __VA_ARGS__); } while (0)
+        for (int s = 0; s < n_sim; ++s) {
+            if (s == 0) FORCED_LAUNCH(false, true, d, s, c.g0, c.g1);
+            else FORCED_LAUNCH(true, true, d, s, c.g0, c.g1);
+            AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
+        }
+        FORCED_LAUNCH(true, false, d, n_sim, c.g0, c.g1);
+#undef FORCED_LAUNCH
+        AZ_HIP(hipGetLastError());
+        return AZ_OK;
+    }
     if (d.budget) {  // the playout cap: k_step's launch sequence with k_step_cap (a slot past its budget idles: no walk, no row)
         for (int s = 0; s < n_sim; ++s) {
             if (s == 0) hipLaunchKernelGGL((k_step_cap<false, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
@@ -2426,7 +2556,8 @@ static int do_search(az_engine *e, int n_sim, const Chain *grp = nullptr) {
     int cap = (ab > 0 && ab < W ? ab : W) * d.K;
     // graph replay needs launch parameters that do not change from search to search: the Philox counter base must be 0
     // (one search per root, as in self-play and the arena), no per-launch event recording, and a quantised batch cap
-    const bool graphable = e->graphs_ok && d.sim_base == 0 && !(e->net && az_net_profiling(e->net)) && e->cfg.evaluator != AZ_EVAL_EXTERNAL;
+    const bool graphable = e->graphs_ok && d.sim_base == 0 && !(e->net && az_net_profiling(e->net)) && e->cfg.evaluator != AZ_EVAL_EXTERNAL &&
+                           n_sim < (1 << 29);  // the graph key's mode bits 61 .. 63 lie above the simulations
     // the quantised cap of the graph path also when the search runs as plain launches under az_net_profile: the profiled step then
     // launches the kernels the timed (graph-replayed) steps launch (an exact cap of 4095 -- one game of 4096 over, as happens from
     // ply ~11 on: Othello has early wipe-outs -- would hand the trunk to the one-board-per-wave kernel for the rest of the wave)
@@ -2435,8 +2566,10 @@ static int do_search(az_engine *e, int n_sim, const Chain *grp = nullptr) {
     cap = cap_q;
     // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31).  A change
     // of K (either setter) drops every graph.  The full Gumbel kernels are other kernels again (bit 31; cap < 2^31), and so are the
-    // playout cap's (bit 62; its n_fast and p_full travel in the launch arguments: the setter drops every graph when they change).
-    const az_engine::GraphKey key(((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)(d.budget != nullptr) << 62) | ((unsigned long long)n_sim << 32) |
+    // playout cap's (bit 62; its n_fast and p_full travel in the launch arguments: the setter drops every graph when they change),
+    // and the forced-playout kernels (bit 61, n_sim < 2^29 where a graph is kept; k travels in the launch arguments as well).
+    const az_engine::GraphKey key(((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)(d.budget != nullptr) << 62) |
+                                      ((unsigned long long)(d.kforced > 0.0) << 61) | ((unsigned long long)n_sim << 32) |
                                       ((unsigned long long)(d.nval != nullptr) << 31) | (unsigned)cap,
                                   ((unsigned long long)c.g0 << 32) | (unsigned)c.g1);
     auto it = e->graphs.find(key);
@@ -3077,6 +3210,7 @@ extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
     AZ_REQUIRE(mask == 0 || e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with leaf_batch %d > 1 (az_engine_set_leaf_batch)", e->leaf_batch);
     AZ_REQUIRE(mask == 0 || e->gumbel_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with gumbel_batch %d > 1 (az_engine_set_gumbel_batch)", e->gumbel_batch);
     AZ_REQUIRE(mask == 0 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_symmetry: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the plain search only; switch it off first", d.cap_nfast);
+    AZ_REQUIRE(mask == 0 || d.kforced == 0.0, AZ_EINVAL, "az_engine_set_symmetry: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served in the plain search only; switch them off first", d.kforced);
     AZ_REQUIRE((long long)n * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "%d symmetries of %d slots are %lld rows, the network's max_batch is %d", n, d.G, (long long)n * d.G, az_net_max_batch(e->net));
     if (mask == e->sym_mask) return AZ_OK;
@@ -3100,6 +3234,7 @@ extern "C" int az_engine_set_symmetry_random(az_engine *e, int32_t mask) {
     AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
     AZ_REQUIRE(mask == 0 || e->sym_mask == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the engine averages over a symmetry mask (az_engine_set_symmetry, mask 0x%x); switch the ensemble off first", (unsigned)e->sym_mask);
     AZ_REQUIRE(mask == 0 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the plain search only; switch it off first", d.cap_nfast);
+    AZ_REQUIRE(mask == 0 || d.kforced == 0.0, AZ_EINVAL, "az_engine_set_symmetry_random: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served in the plain search only; switch them off first", d.kforced);
     AZ_REQUIRE((long long)d.K * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", d.K, d.G, (long long)d.K * d.G, az_net_max_batch(e->net));
     if (mask == e->symr_mask) return AZ_OK;
@@ -3159,6 +3294,7 @@ extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
     AZ_REQUIRE(e->sym_mask == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the engine evaluates over a symmetry mask (0x%x); the ensemble does not combine with leaf_batch", e->sym_mask);
     AZ_REQUIRE(k == 1 || d.gm == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the Gumbel root search is on (az_engine_set_gumbel, m = %d) and searches one leaf per lock-step; switch it off first", d.gm);
     AZ_REQUIRE(k == 1 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served at one leaf per lock-step only; switch it off first", d.cap_nfast);
+    AZ_REQUIRE(k == 1 || d.kforced == 0.0, AZ_EINVAL, "az_engine_set_leaf_batch: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served at one leaf per lock-step only; switch them off first", d.kforced);
     const long long rows = (long long)k * d.G;
     if (e->cfg.evaluator == AZ_EVAL_NET)
         AZ_REQUIRE(rows <= az_net_max_batch(e->net), AZ_EINVAL, "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", k, d.G,
@@ -3218,6 +3354,7 @@ extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, dou
         AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_gumbel: an AZ_EVAL_EXTERNAL engine searches with the PUCT root only");
         AZ_REQUIRE(e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_gumbel: leaf_batch %d > 1 is in force (az_engine_set_leaf_batch); the Gumbel root search takes one leaf per lock-step", e->leaf_batch);
         AZ_REQUIRE(d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_gumbel: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the PUCT search only; switch it off first", d.cap_nfast);
+        AZ_REQUIRE(d.kforced == 0.0, AZ_EINVAL, "az_engine_set_gumbel: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served in the PUCT search only; switch them off first", d.kforced);
     }
     if (m > 0 && e->gumbel_batch > 1 && e->cfg.evaluator == AZ_EVAL_NET)
         AZ_REQUIRE((long long)e->gumbel_batch * d.G <= az_net_max_batch(e->net), AZ_EINVAL, "az_engine_set_gumbel: gumbel_batch %d of %d slots are %lld rows, the network's max_batch is %d",
@@ -3366,4 +3503,57 @@ extern "C" int az_engine_playout_cap_stats(az_engine *e, int64_t *full_plies, in
 
 extern "C" int az_playout_cap_full(uint32_t seed, uint32_t game_id, int32_t ply, double p_full) {
     return playout_cap_full(seed, game_id, ply, p_full) ? 1 : 0;
+}
+
+// ---- forced playouts and policy target pruning (k_step_forced, move_policy) -------------------------------------
+// the modes the plain PUCT search of a network / fake engine excludes are the playout cap's: cap_unserved names them
+extern "C" int az_engine_set_forced_playouts(az_engine *e, double k) {
+    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_set_forced_playouts");
+    AZ_NOT_IN_CALLBACK(e, "az_engine_set_forced_playouts");
+    EngDev &d = e->d;
+    AZ_REQUIRE(k >= 0.0 && k <= 64.0, AZ_EINVAL, "az_engine_set_forced_playouts: k must be finite and in [0, 64] (0 = off), got %g", k);
+    if (k > 0.0) {
+        const char *why = cap_unserved(e);
+        AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_forced_playouts: forced playouts are not served for %s", why);
+    }
+    if (k == d.kforced) return AZ_OK;
+    AZ_TRY(enter(e));
+    if (k > 0.0 && !e->forced_picks) AZ_TRY(dev_alloc(e, &e->forced_picks, (size_t)d.G));
+    // a count left by searches that were never followed by a move must not reach a later ply's fold
+    if (k > 0.0 && d.kforced == 0.0) AZ_HIP(hipMemsetAsync(e->forced_picks, 0, sizeof(int) * (size_t)d.G, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    d.kforced = k > 0.0 ? k : 0.0;
+    d.fpicks = k > 0.0 ? e->forced_picks : nullptr;
+    // other kernels, and k is a launch argument: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_forced_playouts_stats(az_engine *e, int64_t *forced_picks, int64_t *pruned_playouts) {
+    AZ_REQUIRE(e && forced_picks && pruned_playouts, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_forced_playouts_stats");
+    AZ_USABLE(e, "az_engine_forced_playouts_stats");
+    AZ_TRY(enter(e));
+    AZ_TRY(fetch_counters(e));
+    *forced_picks = (int64_t)e->h_ctr[CTR_FORCED_PICKS];
+    *pruned_playouts = (int64_t)e->h_ctr[CTR_PRUNED];
+    return AZ_OK;
+}
+
+extern "C" int az_forced_playout(int32_t n, double p, int32_t root_n, double k) {
+    return (k > 0.0 && forced_playout(n, p, root_n, k)) ? 1 : 0;
+}
+
+extern "C" int az_forced_prune(int32_t n_children, const int32_t *N, const double *Q, const double *P, int32_t root_n, double k, int32_t *out_N) {
+    AZ_REQUIRE(n_children >= 0 && (n_children == 0 || (N && Q && P && out_N)), AZ_EINVAL, "az_forced_prune: null argument or a negative count");
+    AZ_REQUIRE(k >= 0.0 && k <= 64.0, AZ_EINVAL, "az_forced_prune: k must be finite and in [0, 64], got %g", k);
+    int cstar = 0;
+    for (int i = 1; i < n_children; ++i) if (N[i] > N[cstar]) cstar = i;
+    if (n_children == 0) return AZ_OK;
+    const double sq = sqrt((double)root_n);
+    const double star = Q[cstar] + (P[cstar] * sq) / (double)(1 + N[cstar]);
+    for (int i = 0; i < n_children; ++i)
+        out_N[i] = (!(k > 0.0) || i == cstar) ? N[i] : forced_pruned(N[i], Q[i], P[i], root_n, sq, star, k);
+    return AZ_OK;
 }

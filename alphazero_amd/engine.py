@@ -400,6 +400,41 @@ class SelfPlayEngine:
         """the playout cap's coin of (seed, game id, ply): True = a full ply (az_playout_cap_full: host code, the kernels' arithmetic)"""
         return bool(lib().az_playout_cap_full(int(seed) & 0xFFFFFFFF, int(game_id) & 0xFFFFFFFF, int(ply), float(p_full)))
 
+    def set_forced_playouts(self, k):
+        """forced playouts and policy target pruning (az_engine_set_forced_playouts): None = off, or k in (0, 64]
+        (KataGo: 2) -- on a fully searched ply every visited root child gets at least sqrt(k P N_root) playouts, and the recorded
+        policy (and the move drawn from it) leaves out the forced playouts PUCT would not have spent.  Plain search of EVAL_NET /
+        EVAL_FAKE engines, with the playout cap or without; any other mode is a ValueError that names it."""
+        from .forced_playouts import parse
+        k = parse(k)
+        check(lib().az_engine_set_forced_playouts(self.h, 0.0 if k is None else k))
+
+    def forced_playouts_stats(self):
+        """{"forced_picks", "pruned_playouts"}: the root selections with a forced child (folded in when the ply's move is played) and
+        the playouts pruned from the recorded policy targets since the last run() / set_roots(); both 0 with the mode off"""
+        picks, pruned = C.c_int64(), C.c_int64()
+        check(lib().az_engine_forced_playouts_stats(self.h, C.byref(picks), C.byref(pruned)))
+        return {"forced_picks": picks.value, "pruned_playouts": pruned.value}
+
+    @staticmethod
+    def forced_playout(n, p, root_n, k):
+        """the forced test of a root child with n visits and prior p under a root of root_n visits: True = forced (az_forced_playout:
+        host code, the kernels' arithmetic)"""
+        return bool(lib().az_forced_playout(int(n), float(p), int(root_n), float(k)))
+
+    @staticmethod
+    def forced_prune(N, Q, P, root_n, k):
+        """the pruned visit counts (int32 array) of a root's children given in child order (az_forced_prune: host code, the kernels'
+        arithmetic)"""
+        N = np.ascontiguousarray(N, np.int32)
+        Q = np.ascontiguousarray(Q, np.float64)
+        P = np.ascontiguousarray(P, np.float64)
+        if not (N.ndim == Q.ndim == P.ndim == 1 and len(N) == len(Q) == len(P)):
+            raise ValueError("forced_prune: N, Q and P are one-dimensional and of one length")
+        out = np.empty_like(N)
+        check(lib().az_forced_prune(len(N), N.ctypes.data, Q.ctypes.data, P.ctypes.data, int(root_n), float(k), out.ctypes.data))
+        return out
+
     def set_gumbel(self, gumbel):
         """the Gumbel root search (az_engine_set_gumbel; alphazero_amd.gumbel.parse: None = off, an int m or a dict of m, c_visit,
         c_scale, gumbel_scale): Sequential Halving over m root actions sampled with Gumbel noise, the move and the policy target

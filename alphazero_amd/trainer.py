@@ -62,8 +62,8 @@ class AlphaZeroTrainer:
     DEFAULT_EXP_NAME = "alphazero-undefined"
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
-                 selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, selfplay_playout_cap=None, eval_search=None,
-                 eval_opening_plies=None):
+                 selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, selfplay_playout_cap=None, selfplay_forced_playouts=None,
+                 eval_search=None, eval_opening_plies=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -106,6 +106,11 @@ class AlphaZeroTrainer:
         # engines never take it.  The plain PUCT wave only: the engine serves it without the Gumbel search and the symmetry modes.
         self.selfplay_playout_cap = selfplay_playout_cap
         self._check_selfplay_playout_cap()
+        # forced playouts and policy target pruning of that wave: None (off) or KataGo's k in (0, 64] -- the fully
+        # searched plies explore every visited root child to sqrt(k P N) playouts and record the pruned policy.  The self-play engine
+        # alone, with selfplay_playout_cap or without; not with the Gumbel search or the symmetry modes.
+        self.selfplay_forced_playouts = selfplay_forced_playouts
+        self._check_selfplay_forced_playouts()
         # the search the evaluation arena plays with (BatchedArena's `search`): None (the visit-based PUCT arena), "selfplay" (the modes
         # of the self-play wave above) or a dict of arena.SEARCH_KEYS; it goes to player 1 and, with eval_opponent "previous", to the
         # opponent too.  eval_opening_plies: BatchedArena's `opening_plies`, the seeded opening that makes the rounds different games.
@@ -135,6 +140,17 @@ class AlphaZeroTrainer:
             raise ValueError(f"selfplay_playout_cap={self.selfplay_playout_cap!r} does not combine with selfplay_symmetry={self.selfplay_symmetry!r}: "
                              f"the playout cap is served in the plain PUCT search only")
         return cap
+
+    def _check_selfplay_forced_playouts(self):
+        from .forced_playouts import parse
+        k = parse(self.selfplay_forced_playouts, "selfplay_forced_playouts")
+        if k is not None and self.selfplay_gumbel is not None:
+            raise ValueError(f"selfplay_forced_playouts={self.selfplay_forced_playouts!r} does not combine with selfplay_gumbel={self.selfplay_gumbel!r}: "
+                             f"forced playouts are served in the plain PUCT search only")
+        if k is not None and self.selfplay_symmetry is not None:
+            raise ValueError(f"selfplay_forced_playouts={self.selfplay_forced_playouts!r} does not combine with selfplay_symmetry={self.selfplay_symmetry!r}: "
+                             f"forced playouts are served in the plain PUCT search only")
+        return k
 
     def _check_selfplay_symmetry(self):
         from .symmetry import parse
@@ -213,6 +229,7 @@ class AlphaZeroTrainer:
         slots = max(1, min(self.engine_slots, c.episodes))
         sym = self._check_selfplay_symmetry()
         cap = self._check_selfplay_playout_cap()
+        forced = self._check_selfplay_forced_playouts()
         from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full
         gb = check_gumbel_batch(self.selfplay_gumbel_batch, self.selfplay_gumbel)
         gf = check_gumbel_full(self.selfplay_gumbel_full, self.selfplay_gumbel)
@@ -248,6 +265,9 @@ class AlphaZeroTrainer:
         if cap is None and getattr(self._engine, "_playout_cap", None) is not None:  # off before the modes it excludes come on
             self._engine.set_playout_cap(None)
             self._engine._playout_cap = None
+        if forced is None and getattr(self._engine, "_forced_playouts", None) is not None:
+            self._engine.set_forced_playouts(None)
+            self._engine._forced_playouts = None
         if external:  # a fresh evaluator for the network of this wave (update_network replaces self.nn)
             self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
         elif sym is not None or self._engine._sym_mode is not None:
@@ -268,6 +288,9 @@ class AlphaZeroTrainer:
         if cap != getattr(self._engine, "_playout_cap", None):  # ValueError for a network routed to the external evaluator, n_fast >= simulations
             self._engine.set_playout_cap(cap)
             self._engine._playout_cap = cap
+        if forced != getattr(self._engine, "_forced_playouts", None):  # ValueError for a network routed to the external evaluator
+            self._engine.set_forced_playouts(forced)
+            self._engine._forced_playouts = forced
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

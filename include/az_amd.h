@@ -459,6 +459,51 @@ int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full);
 int az_engine_playout_cap_stats(az_engine *e, int64_t *full_plies, int64_t *fast_plies);
 int az_playout_cap_full(uint32_t seed, uint32_t game_id, int32_t ply, double p_full);
 
+/* Forced playouts and policy target pruning (KataGo: Wu 2019, "Accelerating Self-Play Learning in Go", section 3.2): on a fully
+ * searched ply every root child that has been visited at all receives at least sqrt(k P(c) N_root) playouts, so that a move the
+ * noise proposed is explored far enough to be refuted or confirmed; when the ply's policy is read, the forced playouts PUCT would
+ * not have spent are subtracted again and a child left with a single playout is removed, so that the recorded target -- and the move
+ * drawn from it -- describe what the search believes.  The reference has no counterpart.  Opt-in: k = 0 (the default) is off, when
+ * no launch, kernel, allocation or output bit differs from an engine that never had it on.  Every operation below is one IEEE double
+ * operation in the order written (the library is built with -ffp-contract=off); sqrt is the correctly rounded one.  Contract:
+ *   switch      k > 0 on (KataGo: k = 2), k = 0 off; k finite and in [0, 64], anything else AZ_EINVAL.
+ *   forced ply  a ply of a slot this engine searches, the mode on, that is full in the playout cap's sense: every ply with the cap
+ *               off, with it on the plies whose coin az_playout_cap_full(seed, game id, ply, p_full) says full.  Fast plies take
+ *               no forced playouts and no pruning.
+ *   selection   at depth 0 of a simulation's walk on a forced ply only.  R.N = the root's visit count as PUCT's square root takes
+ *               it at that selection.  Child c is FORCED iff c.N > 0 && (double)c.N * (double)c.N < (k * c.P) * (double)R.N, with
+ *               c.P the stored prior, root noise included (no square root is taken).  A forced child's key is +inf, every other
+ *               child keeps its PUCT key, and the maximum is chosen as ever: several forced children are an ordinary tie
+ *               (AZ_TIE_RANDOM: the AZ_P_TIE_SELECT draw of that (ply, simulation, depth 0); AZ_TIE_LOWEST: the lowest index).
+ *               A fresh root has R.N = 0, so nothing is forced; a root inherited from the ply before applies the rule to the counts
+ *               it inherited.  Below the root nothing changes.
+ *   pruning     wherever the root's policy is read on a forced ply at a temperature other than 0 (az_engine_run / _advance,
+ *               az_engine_root_readout, az_engine_player_moves).  c* = the child with the greatest N (lowest child index among
+ *               equals, no draw); sq = sqrt((double)R.N); star = c*.Q + (c*.P * sq) / (double)(1 + c*.N).  The pruned count N'
+ *               equals N for c* and for children with N = 0.  For every other child:
+ *                 nf = (int)sqrt((k * c.P) * (double)R.N);  gap = star - c.Q;
+ *                 need = c.N if gap <= 0.0; otherwise want = (c.P * sq) / gap - 1.0, and need = c.N if want >= (double)c.N,
+ *                 else (int)floor(want) + 1;
+ *                 N' = min(c.N, max(c.N - nf, need, 0));  if N' < c.N && N' <= 1 then N' = 0.
+ *               The temperature formula (n at temperature 1, az_det_pow otherwise) takes N' in place of N for the recorded pi and
+ *               for the move drawn from it, with the same AZ_P_MOVE_SAMPLE draw.  At temperature 0 nothing changes (the most
+ *               visited child by the raw counts, pi one-hot).  The visits rows stay the raw counts.
+ *   counters    az_engine_forced_playouts_stats: forced_picks = the root selections in which at least one child was forced, folded
+ *               in once per ply when the move is played; pruned_playouts = the sum of N - N' over the recorded plies.  Since the
+ *               last az_engine_run / az_engine_set_roots; both 0 with the mode off.  az_engine_stats is unchanged.
+ * A readout's pi and action stay bit-equal to what az_engine_advance records and plays under the mode.
+ * Served: the plain PUCT search of AZ_EVAL_NET / AZ_EVAL_FAKE engines through az_engine_run (1, 2 or 4 slot groups), az_engine_search,
+ * _search_begin / _end, az_engine_advance and az_engine_root_readout, with the playout cap on or off.  Not served (AZ_EINVAL naming
+ * the mode; and while the mode is on the setters of those modes refuse, naming forced playouts): leaf_batch > 1, the Gumbel search,
+ * either symmetry mode, AZ_EVAL_ROLLOUT, AZ_EVAL_EXTERNAL.  AZ_ESTATE while a search is open.  A change of k drops the cached
+ * search graphs.
+ * az_forced_playout: the forced test as pure host code, 1 = forced (0 also for k <= 0); az_forced_prune: the pruned counts of a
+ * root's n_children children (N, Q, P in child order) into out_N, AZ_OK or AZ_EINVAL; k = 0 copies N.  The kernels' arithmetic. */
+int az_engine_set_forced_playouts(az_engine *e, double k);
+int az_engine_forced_playouts_stats(az_engine *e, int64_t *forced_picks, int64_t *pruned_playouts);
+int az_forced_playout(int32_t n, double p, int32_t root_n, double k);
+int az_forced_prune(int32_t n_children, const int32_t *N, const double *Q, const double *P, int32_t root_n, double k, int32_t *out_N);
+
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
  * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves
