@@ -2156,6 +2156,9 @@ __global__ __launch_bounds__(256) void k_sym_pick(EngDev E, int mask, int n, int
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+#include "az_search_plan.h"  // the launch sequence of a search as a value, the batch caps, the slot groups' ranges and measured rule
+static_assert(GPB == AZ_SLOT_BLOCK, "a slot group is whole blocks of the step kernels");
+
 struct az_engine {
     az_engine_cfg cfg;
     EngDev d;
@@ -2171,11 +2174,9 @@ struct az_engine {
     hipStream_t user_stream = nullptr;
     bool search_open = false;  // between az_engine_search_begin and _end
     hipEvent_t ev_in = nullptr;
-    // One search = 1 + 5 n_sim kernel launches: captured once per (n_sim, batch cap) as a HIP graph and replayed
-    // (a slot group's graph: the key's second word holds its slot range, g0 << 32 | g1)
-    typedef std::pair<unsigned long long, unsigned long long> GraphKey;
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    std::map<GraphKey, int> graph_seen;
+    // One search = 1 + 5 n_sim kernel launches: captured once per (kernel family, n_sim, batch cap, slot range) as a HIP graph and replayed
+    std::map<SearchKey, hipGraphExec_t> graphs;
+    std::map<SearchKey, int> graph_seen;
     bool graphs_ok = true;
     long long graph_replays = 0;
     int *scr_a = nullptr, *scr_b = nullptr;  // [G] int scratch of the arena entry points (moves in/out, status, scores)
@@ -2273,6 +2274,8 @@ static inline dim3 grid_for(int n, int bs) { return dim3((unsigned)((n + bs - 1)
 #define AZ_NOT_IN_CALLBACK(e, who) AZ_REQUIRE(!(e)->in_callback, AZ_ESTATE, who ": called from inside the engine's own evaluator")
 #define AZ_USABLE(e, who) do { AZ_NOT_IN_CALLBACK(e, who); \
     AZ_REQUIRE(!(e)->unevaluated, AZ_ESTATE, who ": an evaluation failed and left unevaluated leaves in the trees; az_engine_set_roots or az_engine_run resets the slots"); } while (0)
+// how every az_engine_set_* of a search mode opens
+#define AZ_SETTER(e, who) do { AZ_REQUIRE(e, AZ_EINVAL, "null engine"); AZ_NO_OPEN_SEARCH(e, who); AZ_NOT_IN_CALLBACK(e, who); } while (0)
 
 extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *stream, az_engine **out) {
     AZ_REQUIRE(cfg && out, AZ_EINVAL, "null argument");
@@ -2427,113 +2430,54 @@ static int forward(az_engine *e, const Chain &c, const int *cnt, int cap, int st
     return az_sym_reduce(&d.gd, e->sym_mask, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
 }
 
-// Lmax(n, m, K) of the Gumbel mode with K walkers (the contract above k_step_gumbel_multi; gumbel.locksteps in Python): the longest
-// per-slot plan of any m0 in 1 .. m.  A pure function of its arguments: the launch sequence of a search captures as a graph.
-static int gumbel_locksteps(int n, int m, int K) {
-    int best = 0;
-    for (int m0 = 1; m0 <= m; ++m0) {
-        int L = 0, mp = m0, end = 0, steps = 0;
-        for (int b = m0 - 1; b > 0; b >>= 1) ++L;  // ceil(log2 m0)
-        for (int s = 0; s < n;) {
-            while (end <= s) {  // the phase that holds s
-                if (m0 == 1) { end = n; break; }
-                int v = n / (L * mp);
-                end += mp * (v < 1 ? 1 : v);
-                mp = mp / 2 < 2 ? 2 : mp / 2;
-            }
-            const int stop = end < n ? end : n;
-            s += stop - s < K ? stop - s : K;
-            ++steps;
-        }
-        best = steps > best ? steps : best;
+static SearchMode search_mode(const EngDev &d) { return SearchMode{d.rollout != 0, d.gm, d.K, d.nval != nullptr, d.budget != nullptr, d.kforced > 0.0}; }
+
+// The one place that names the step kernels: launch `a` of the plan on chain c.  Each family is instantiated for three (backup, select)
+// pairs -- the first step, the later ones, the last backup; never <false, false> -- and the two Gumbel families for `full` on and off.
+// (the kernels without a slot range -- rollout, K walkers -- run as the whole engine's chain only: g0 = 0, g1 = G)
+template <bool B, bool S>
+static void launch_step_as(const SearchPlan &p, const Chain &c, int n_sim, const StepArgs &a) {
+    const EngDev &d = c.d;
+    const dim3 gg((unsigned)((c.g1 - c.g0 + GPB - 1) / GPB)), gb(256);
+    switch (p.family) {
+        case SF_ROLLOUT: hipLaunchKernelGGL(k_rollout_step, gg, gb, 0, c.st, d, a.t); break;
+        case SF_STEP: hipLaunchKernelGGL((k_step<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
+        case SF_STEP_CAP: hipLaunchKernelGGL((k_step_cap<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
+        case SF_STEP_FORCED: hipLaunchKernelGGL((k_step_forced<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
+        case SF_STEP_CAP_FORCED: hipLaunchKernelGGL((k_step_cap_forced<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
+        case SF_STEP_MULTI: hipLaunchKernelGGL((k_step_multi<B, S>), gg, gb, 0, c.st, d, a.t, a.kb, a.kt); break;
+        case SF_STEP_GUMBEL:
+            if (p.full) hipLaunchKernelGGL((k_step_gumbel<B, S, true>), gg, gb, 0, c.st, d, a.t, n_sim, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step_gumbel<B, S, false>), gg, gb, 0, c.st, d, a.t, n_sim, c.g0, c.g1);
+            break;
+        case SF_STEP_GUMBEL_MULTI:
+            if (p.full) hipLaunchKernelGGL((k_step_gumbel_multi<B, S, true>), gg, gb, 0, c.st, d, a.t, n_sim);
+            else hipLaunchKernelGGL((k_step_gumbel_multi<B, S, false>), gg, gb, 0, c.st, d, a.t, n_sim);
+            break;
     }
-    return best;
+}
+static void launch_step(const SearchPlan &p, const Chain &c, int n_sim, const StepArgs &a) {
+    if (!a.backup) launch_step_as<false, true>(p, c, n_sim, a);
+    else if (a.select) launch_step_as<true, true>(p, c, n_sim, a);
+    else launch_step_as<true, false>(p, c, n_sim, a);
 }
 
-// MCT.search for every active slot: one root-prior pass (mcts.py:231-233; empty unless a slot holds a
-// fresh root), then n_sim lock-steps of [backup+select -> network].
+// MCT.search for every active slot: one root-prior pass (mcts.py:231-233; empty unless a slot holds a fresh root), then the plan's
+// lock-steps of [backup+select -> network] and the last backup.
 // the raw launch sequence of one search; `cap` bounds the network batch (leaf rows are compact: count <= searching slots)
-static int enqueue_search(az_engine *e, const Chain &c, int n_sim, int cap) {
+static int enqueue_search(az_engine *e, const Chain &c, const SearchPlan &p, int n_sim, int cap) {
     const EngDev &d = c.d;
-    // (the kernels without a slot range -- rollout, K walkers -- run as the whole engine's chain only: g0 = 0, g1 = G)
-    dim3 gg((unsigned)((c.g1 - c.g0 + GPB - 1) / GPB)), gb(256);
-    if (d.rollout) {  // no network: one launch per simulation
-        for (int s = 0; s < n_sim; ++s) hipLaunchKernelGGL(k_rollout_step, gg, gb, 0, c.st, d, s);
-        AZ_HIP(hipGetLastError());
-        return AZ_OK;
+    if (p.root_pass) {
+        const dim3 gg((unsigned)((c.g1 - c.g0 + GPB - 1) / GPB)), gb(256);
+        hipLaunchKernelGGL(k_root_prep, gg, gb, 0, c.st, d, c.g0, c.g1);
+        AZ_TRY(forward(e, c, d.batch_cnt + 2, cap, -1));
+        hipLaunchKernelGGL(k_root_init, gg, gb, 0, c.st, d, c.g0, c.g1);
     }
-    hipLaunchKernelGGL(k_root_prep, gg, gb, 0, c.st, d, c.g0, c.g1);
-    AZ_TRY(forward(e, c, d.batch_cnt + 2, cap, -1));
-    hipLaunchKernelGGL(k_root_init, gg, gb, 0, c.st, d, c.g0, c.g1);
-    // az_engine_set_gumbel_full in force: the other instantiation of the two Gumbel kernels (no run-time branch inside the walk)
-    const bool full = d.nval != nullptr;
-#define GUMBEL_LAUNCH(kern, B, S, ...) do { \
-        if (full) hipLaunchKernelGGL((kern<B, S, true>), gg, gb, 0, c.st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((kern<B, S, false>), gg, gb, 0, c.st, __VA_ARGS__); } while (0)
-    if (d.gm > 0 && d.K > 1) {  // Sequential Halving with K walkers: Lmax lock-steps, cut per slot by its own cursor, then the last backup
-        const int L = gumbel_locksteps(n_sim, d.gm, d.K);
-        for (int t = 0; t < L; ++t) {
-            if (t == 0) GUMBEL_LAUNCH(k_step_gumbel_multi, false, true, d, t, n_sim);
-            else GUMBEL_LAUNCH(k_step_gumbel_multi, true, true, d, t, n_sim);
-            AZ_TRY(forward(e, c, d.batch_cnt + (t & 1), cap, t, d.K));
-        }
-        GUMBEL_LAUNCH(k_step_gumbel_multi, true, false, d, L, n_sim);
-        AZ_HIP(hipGetLastError());
-        return AZ_OK;
+    for (int t = 0; t < p.launches; ++t) {
+        const StepArgs a = plan_step(p, n_sim, d.K, t);
+        launch_step(p, c, n_sim, a);
+        if (a.select) AZ_TRY(forward(e, c, d.batch_cnt + a.ctr, cap, a.t, a.kt));
     }
-    if (d.K > 1) {  // ceil(n_sim / K) lock-steps of up to K walkers per slot (k_step_multi), then the backup of the last ones
-        const int K = d.K, L = (n_sim + K - 1) / K;
-        for (int t = 0; t < L; ++t) {
-            const int kt = n_sim - t * K < K ? n_sim - t * K : K;
-            if (t == 0) hipLaunchKernelGGL((k_step_multi<false, true>), gg, gb, 0, c.st, d, t, 0, kt);
-            else hipLaunchKernelGGL((k_step_multi<true, true>), gg, gb, 0, c.st, d, t, K, kt);
-            AZ_TRY(forward(e, c, d.batch_cnt + (t & 1), cap, t, kt));
-        }
-        hipLaunchKernelGGL((k_step_multi<true, false>), gg, gb, 0, c.st, d, L, n_sim - (L - 1) * K, 0);
-        AZ_HIP(hipGetLastError());
-        return AZ_OK;
-    }
-    if (d.gm > 0) {  // the Gumbel root search: k_step's launch sequence with k_step_gumbel
-        for (int s = 0; s < n_sim; ++s) {
-            if (s == 0) GUMBEL_LAUNCH(k_step_gumbel, false, true, d, s, n_sim, c.g0, c.g1);
-            else GUMBEL_LAUNCH(k_step_gumbel, true, true, d, s, n_sim, c.g0, c.g1);
-            AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
-        }
-        GUMBEL_LAUNCH(k_step_gumbel, true, false, d, n_sim, n_sim, c.g0, c.g1);
-        AZ_HIP(hipGetLastError());
-        return AZ_OK;
-    }
-#undef GUMBEL_LAUNCH
-    if (d.kforced > 0.0) {  // forced playouts: k_step's launch sequence with k_step_forced, or k_step_cap's with k_step_cap_forced
-#define FORCED_LAUNCH(B, S, ...) do { \
-        if (d.budget) hipLaunchKernelGGL((k_step_cap_forced<B, S>), gg, gb, 0, c.st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((k_step_forced<B, S>), gg, gb, 0, c.st, __VA_ARGS__); } while (0)
-        for (int s = 0; s < n_sim; ++s) {
-            if (s == 0) FORCED_LAUNCH(false, true, d, s, c.g0, c.g1);
-            else FORCED_LAUNCH(true, true, d, s, c.g0, c.g1);
-            AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
-        }
-        FORCED_LAUNCH(true, false, d, n_sim, c.g0, c.g1);
-#undef FORCED_LAUNCH
-        AZ_HIP(hipGetLastError());
-        return AZ_OK;
-    }
-    if (d.budget) {  // the playout cap: k_step's launch sequence with k_step_cap (a slot past its budget idles: no walk, no row)
-        for (int s = 0; s < n_sim; ++s) {
-            if (s == 0) hipLaunchKernelGGL((k_step_cap<false, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
-            else hipLaunchKernelGGL((k_step_cap<true, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
-            AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
-        }
-        hipLaunchKernelGGL((k_step_cap<true, false>), gg, gb, 0, c.st, d, n_sim, c.g0, c.g1);
-        AZ_HIP(hipGetLastError());
-        return AZ_OK;
-    }
-    for (int s = 0; s < n_sim; ++s) {
-        if (s == 0) hipLaunchKernelGGL((k_step<false, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
-        else hipLaunchKernelGGL((k_step<true, true>), gg, gb, 0, c.st, d, s, c.g0, c.g1);
-        AZ_TRY(forward(e, c, d.batch_cnt + (s & 1), cap, s));
-    }
-    hipLaunchKernelGGL((k_step<true, false>), gg, gb, 0, c.st, d, n_sim, c.g0, c.g1);
     AZ_HIP(hipGetLastError());
     return AZ_OK;
 }
@@ -2548,51 +2492,43 @@ static int do_search(az_engine *e, int n_sim, const Chain *grp = nullptr) {
     const Chain whole = whole_chain(e);
     const Chain &c = grp ? *grp : whole;
     const EngDev &d = c.d;
-    e->lockstep_iters[c.idx] += d.rollout ? n_sim : ((d.gm > 0 && d.K > 1) ? gumbel_locksteps(n_sim, d.gm, d.K) : (n_sim + d.K - 1) / d.K) + 1;
+    const SearchPlan plan = plan_search(search_mode(d), n_sim);
+    e->lockstep_iters[c.idx] += plan.launches;
     // network rows: every searching slot brings up to K leaves per lock-step (K = 1 unless az_engine_set_leaf_batch / _set_gumbel_batch)
-    const int W = c.g1 - c.g0, R = W * d.K;
     // (a group takes its own live count, not active_bound: the shared counters behind that are moving while another group plays its ply)
-    const int ab = grp ? grp->live : e->active_bound;
-    int cap = (ab > 0 && ab < W ? ab : W) * d.K;
+    const int W = c.g1 - c.g0;
+    int cap = search_batch_cap(W, d.K, grp ? grp->live : e->active_bound);
     // graph replay needs launch parameters that do not change from search to search: the Philox counter base must be 0
     // (one search per root, as in self-play and the arena), no per-launch event recording, and a quantised batch cap
-    const bool graphable = e->graphs_ok && d.sim_base == 0 && !(e->net && az_net_profiling(e->net)) && e->cfg.evaluator != AZ_EVAL_EXTERNAL &&
-                           n_sim < (1 << 29);  // the graph key's mode bits 61 .. 63 lie above the simulations
+    const bool profiled = e->net && az_net_profiling(e->net);
+    const bool graphable = e->graphs_ok && d.sim_base == 0 && !profiled && e->cfg.evaluator != AZ_EVAL_EXTERNAL;
     // the quantised cap of the graph path also when the search runs as plain launches under az_net_profile: the profiled step then
-    // launches the kernels the timed (graph-replayed) steps launch (an exact cap of 4095 -- one game of 4096 over, as happens from
-    // ply ~11 on: Othello has early wipe-outs -- would hand the trunk to the one-board-per-wave kernel for the rest of the wave)
-    const int cap_q = (R >= 4096 && cap < 4096) ? (cap + 511) / 512 * 512 : R;  // below 4096 rows the network picks other kernels
-    if (!graphable) return enqueue_search(e, c, n_sim, (e->net && az_net_profiling(e->net) && d.sim_base == 0) ? cap_q : cap);
-    cap = cap_q;
-    // the Gumbel mode launches other kernels: a graph of the plain search is never replayed for it (bit 63; n_sim < 2^31).  A change
-    // of K (either setter) drops every graph.  The full Gumbel kernels are other kernels again (bit 31; cap < 2^31), and so are the
-    // playout cap's (bit 62; its n_fast and p_full travel in the launch arguments: the setter drops every graph when they change),
-    // and the forced-playout kernels (bit 61, n_sim < 2^29 where a graph is kept; k travels in the launch arguments as well).
-    const az_engine::GraphKey key(((unsigned long long)(d.gm > 0) << 63) | ((unsigned long long)(d.budget != nullptr) << 62) |
-                                      ((unsigned long long)(d.kforced > 0.0) << 61) | ((unsigned long long)n_sim << 32) |
-                                      ((unsigned long long)(d.nval != nullptr) << 31) | (unsigned)cap,
-                                  ((unsigned long long)c.g0 << 32) | (unsigned)c.g1);
+    // launches the kernels the timed (graph-replayed) steps launch
+    if (graphable || (profiled && d.sim_base == 0)) cap = quantised_cap(W * d.K, cap);
+    if (!graphable) return enqueue_search(e, c, plan, n_sim, cap);
+    // another family, or the full instantiation of a Gumbel one, launches other kernels: the key keeps their graphs apart
+    const SearchKey key = search_key(plan, n_sim, cap, c.g0, c.g1);
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) {
         AZ_HIP(hipGraphLaunch(it->second, c.st));
         e->graph_replays++;
         return AZ_OK;
     }
-    if (e->graph_seen[key]++ == 0) return enqueue_search(e, c, n_sim, cap);  // first time: plain launches (kernel attributes get set)
+    if (e->graph_seen[key]++ == 0) return enqueue_search(e, c, plan, n_sim, cap);  // first time: plain launches (kernel attributes get set)
     hipGraph_t g = nullptr;
     hipGraphExec_t ex = nullptr;
     if (hipStreamBeginCapture(c.st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
         e->graphs_ok = false;
-        return enqueue_search(e, c, n_sim, cap);
+        return enqueue_search(e, c, plan, n_sim, cap);
     }
-    const int rc = enqueue_search(e, c, n_sim, cap);  // recorded, not executed
+    const int rc = enqueue_search(e, c, plan, n_sim, cap);  // recorded, not executed
     const hipError_t er = hipStreamEndCapture(c.st, &g);
     if (rc != AZ_OK || er != hipSuccess || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
         (void)hipGetLastError();
         if (g) (void)hipGraphDestroy(g);
         e->graphs_ok = false;
-        return enqueue_search(e, c, n_sim, cap);
+        return enqueue_search(e, c, plan, n_sim, cap);
     }
     (void)hipGraphDestroy(g);
     e->graphs[key] = ex;
@@ -2650,48 +2586,43 @@ static int check_err(az_engine *e, int idx) {
     return AZ_OK;
 }
 
-// ---- slot groups (az_engine_set_groups) ---------------------------------------------------------------------------------------
-// the mode of this engine that the grouped run does not serve, or null
-static const char *groups_unserved(const az_engine *e) {
-    if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return "an AZ_EVAL_EXTERNAL engine (external evaluator: its export buffers are per engine)";
-    if (e->cfg.evaluator == AZ_EVAL_ROLLOUT) return "a rollout engine (AZ_EVAL_ROLLOUT: no network to overlap with)";
-    if (e->sym_mask != 0) return "the symmetry ensemble (az_engine_set_symmetry: the twins' rows are per engine)";
-    if (e->symr_mask != 0) return "the random symmetry mode (az_engine_set_symmetry_random: the twins' rows are per engine)";
+// ---- the modes served in the plain search only: slot groups, the playout cap, forced playouts -----------------------------------------
+// The mode of this engine that leaves the plain PUCT search of a network or fake engine, or null.  Slot groups, the playout cap and
+// forced playouts are served in that search only: their kernels are k_step's family, one leaf per slot and lock-step.  (For the groups
+// besides: the external evaluator's export buffers and the symmetry modes' twin rows are per engine, a rollout engine has no network to
+// overlap with, and the kernels of leaf_batch > 1 and of the Gumbel search take no slot range.)
+static const char *beyond_plain_search(const az_engine *e) {
+    if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return "an AZ_EVAL_EXTERNAL engine (external evaluator)";
+    if (e->cfg.evaluator == AZ_EVAL_ROLLOUT) return "a rollout engine (AZ_EVAL_ROLLOUT)";
+    if (e->sym_mask != 0) return "the symmetry ensemble (az_engine_set_symmetry)";
+    if (e->symr_mask != 0) return "the random symmetry mode (az_engine_set_symmetry_random)";
     if (e->leaf_batch > 1) return "leaf_batch > 1 (az_engine_set_leaf_batch)";
     if (e->d.gm > 0) return "the Gumbel search (az_engine_set_gumbel)";
     return nullptr;
 }
 
-// The measured rule (profiles/r14_groups.txt): the groups az_engine_run plays with where nothing was asked for.  A
-// shape has n > 1 only where the worst of three grouped runs beat the best of three runs of the build before by more than that
-// build's own spread; every shape that was not measured plays as one group.
-static int groups_auto(const az_engine *e) {
-    const az_engine_cfg &c = e->cfg;
-    const int G = e->d.G;
-    if (c.evaluator != AZ_EVAL_NET) return 1;  // the fake evaluator has no network kernels to run beside
-    if (c.game == AZ_OTHELLO && c.H == 8) {
-        if (G >= 4096 && G < 8192) return 2;  // 4096 slots: 2 x 2048 +4.5 %; 4 x 1024 loses (-14 %)
-        if (G >= 32768) return 2;             // 32768 slots: 2 x 16384 +1.3 %
-        return 1;                             // 512 slots: +0.4 %, not worth a second chain; 8192 .. 32767: not measured
-    }
-    if (c.game == AZ_CONNECT4 && c.H == 6 && c.W == 7) return G >= 8192 ? 4 : 1;  // 8192 slots: 4 x 2048 +9.4 %, 2 x 4096 +0.2 %
-    return 1;
+// the other way round: what the setter `who` of such a mode answers while the playout cap or forced playouts are on (`where`: what
+// the mode would leave)
+static int refuse_beside_cap_or_forced(const az_engine *e, const char *who, const char *where) {
+    const EngDev &d = e->d;
+    AZ_REQUIRE(d.cap_nfast == 0, AZ_EINVAL, "%s: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served %s only; switch it off first", who, d.cap_nfast, where);
+    AZ_REQUIRE(d.kforced == 0.0, AZ_EINVAL, "%s: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served %s only; switch them off first", who, d.kforced, where);
+    return AZ_OK;
 }
 
+// ---- slot groups (az_engine_set_groups) ---------------------------------------------------------------------------------------
 // groups of the next az_engine_run: the request (auto: the rule) where the mode is served and every group holds a block of slots
 static int groups_in_force(const az_engine *e) {
-    if (groups_unserved(e)) return 1;
+    if (beyond_plain_search(e)) return 1;
     if (e->net && az_net_profiling(e->net)) return 1;  // the profiled run is today's launch sequence: full-width, un-overlapped kernels
-    int n = e->groups_req > 0 ? e->groups_req : groups_auto(e);
-    return e->d.G > GPB ? n : 1;  // a group is whole blocks of slots (trailing groups may be empty: 40 slots in 4 groups are 16, 16, 8, 0)
+    const int n = e->groups_req > 0 ? e->groups_req : groups_auto(e->cfg.evaluator, e->cfg.game, e->cfg.H, e->cfg.W, e->d.G);
+    return e->d.G > GPB ? n : 1;  // a group is whole blocks of slots (group_range)
 }
 
 extern "C" int az_engine_set_groups(az_engine *e, int32_t n) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_groups");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_groups");
+    AZ_SETTER(e, "az_engine_set_groups");
     AZ_REQUIRE(n == 0 || n == 1 || n == 2 || n == 4, AZ_EINVAL, "az_engine_set_groups: %d groups (0 = auto, 1, 2 or 4)", n);
-    const char *why = groups_unserved(e);
+    const char *why = beyond_plain_search(e);
     AZ_REQUIRE(n <= 1 || !why, AZ_EINVAL, "az_engine_set_groups: %d slot groups are not served for %s", n, why);
     AZ_REQUIRE(n <= 1 || e->d.G > GPB, AZ_EINVAL, "az_engine_set_groups: %d groups of %d slots: a group is whole blocks of %d slots, this engine is less than a block to split", n, e->d.G, GPB);
     if (n == e->groups_req && !e->groups_env) return AZ_OK;
@@ -2711,9 +2642,8 @@ extern "C" int az_engine_groups(az_engine *e, int32_t *n) {
 // group i of n: slots [g0, g1) in whole blocks, the group's stream, rows [g0, g1) of the network batch, counters 4 i .. and live word i
 static int make_chain(az_engine *e, int i, int n, Chain *c) {
     const EngDev &d = e->d;
-    const int blocks = (d.G + GPB - 1) / GPB, per = (blocks + n - 1) / n;
-    int g0 = i * per * GPB, g1 = (i + 1) * per * GPB;
-    g0 = g0 < d.G ? g0 : d.G; g1 = g1 < d.G ? g1 : d.G;
+    int g0 = 0, g1 = 0;
+    group_range(d.G, i, n, &g0, &g1);
     if (i > 0 && !e->gstream[i]) {  // from the other priority pool (az_engine_pair): streams of one priority may share a hardware queue
         int least = 0, greatest = 0;
         AZ_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -2793,8 +2723,8 @@ extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_gam
     AZ_TRY(reset_external(e));
     for (int i = 0; i < AZ_MAX_GROUPS; ++i) e->lockstep_iters[i] = 0;
     const int n_groups = groups_in_force(e);
-    if (e->groups_req > 1 && !e->groups_env && n_groups == 1 && groups_unserved(e)) {
-        az_set_error("az_engine_run: %d slot groups were asked for (az_engine_set_groups) and are not served for %s", e->groups_req, groups_unserved(e));
+    if (e->groups_req > 1 && !e->groups_env && n_groups == 1 && beyond_plain_search(e)) {
+        az_set_error("az_engine_run: %d slot groups were asked for (az_engine_set_groups) and are not served for %s", e->groups_req, beyond_plain_search(e));
         return AZ_EINVAL;
     }
     hipLaunchKernelGGL(k_reset_all, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, (u32)first_game_id, (int)n_games);
@@ -3075,10 +3005,7 @@ extern "C" int az_engine_grow_pools(az_engine *e, int32_t node_capacity) {
     }
     d.C = node_capacity;
     e->cfg.node_capacity = node_capacity;
-    // captured searches hold the old pool pointer and capacity by value
-    for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
-    e->graphs.clear();
-    e->graph_seen.clear();
+    drop_graphs(e);  // captured searches hold the old pool pointer and capacity by value
     return AZ_OK;
 }
 
@@ -3198,9 +3125,7 @@ static void drop_graphs(az_engine *e) {
 }
 
 extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_symmetry");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_symmetry");
+    AZ_SETTER(e, "az_engine_set_symmetry");
     EngDev &d = e->d;
     AZ_REQUIRE(e->cfg.evaluator == AZ_EVAL_NET, AZ_EINVAL, "az_engine_set_symmetry needs an engine created with evaluator = AZ_EVAL_NET (this one: %d)",
                e->cfg.evaluator);
@@ -3209,8 +3134,7 @@ extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
     AZ_REQUIRE(mask == 0 || e->symr_mask == 0, AZ_EINVAL, "az_engine_set_symmetry: the engine draws one symmetry per evaluation (az_engine_set_symmetry_random, mask 0x%x); switch that mode off first", (unsigned)e->symr_mask);
     AZ_REQUIRE(mask == 0 || e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with leaf_batch %d > 1 (az_engine_set_leaf_batch)", e->leaf_batch);
     AZ_REQUIRE(mask == 0 || e->gumbel_batch == 1, AZ_EINVAL, "az_engine_set_symmetry: the symmetry ensemble does not combine with gumbel_batch %d > 1 (az_engine_set_gumbel_batch)", e->gumbel_batch);
-    AZ_REQUIRE(mask == 0 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_symmetry: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the plain search only; switch it off first", d.cap_nfast);
-    AZ_REQUIRE(mask == 0 || d.kforced == 0.0, AZ_EINVAL, "az_engine_set_symmetry: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served in the plain search only; switch them off first", d.kforced);
+    if (mask != 0) AZ_TRY(refuse_beside_cap_or_forced(e, "az_engine_set_symmetry", "in the plain search"));
     AZ_REQUIRE((long long)n * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "%d symmetries of %d slots are %lld rows, the network's max_batch is %d", n, d.G, (long long)n * d.G, az_net_max_batch(e->net));
     if (mask == e->sym_mask) return AZ_OK;
@@ -3224,17 +3148,14 @@ extern "C" int az_engine_set_symmetry(az_engine *e, int32_t mask) {
 
 // one member of `mask`, drawn per evaluation (k_sym_pick above): the rows of the plain search, so it composes with leaf_batch
 extern "C" int az_engine_set_symmetry_random(az_engine *e, int32_t mask) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_symmetry_random");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_symmetry_random");
+    AZ_SETTER(e, "az_engine_set_symmetry_random");
     EngDev &d = e->d;
     AZ_REQUIRE(e->cfg.evaluator == AZ_EVAL_NET, AZ_EINVAL, "az_engine_set_symmetry_random needs an engine created with evaluator = AZ_EVAL_NET (this one: %d)",
                e->cfg.evaluator);
     int n = 0;
     AZ_TRY(az_sym_resolve(&d.gd, mask, &mask, &n));
     AZ_REQUIRE(mask == 0 || e->sym_mask == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the engine averages over a symmetry mask (az_engine_set_symmetry, mask 0x%x); switch the ensemble off first", (unsigned)e->sym_mask);
-    AZ_REQUIRE(mask == 0 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_symmetry_random: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the plain search only; switch it off first", d.cap_nfast);
-    AZ_REQUIRE(mask == 0 || d.kforced == 0.0, AZ_EINVAL, "az_engine_set_symmetry_random: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served in the plain search only; switch them off first", d.kforced);
+    if (mask != 0) AZ_TRY(refuse_beside_cap_or_forced(e, "az_engine_set_symmetry_random", "in the plain search"));
     AZ_REQUIRE((long long)d.K * d.G <= az_net_max_batch(e->net), AZ_EINVAL,
                "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", d.K, d.G, (long long)d.K * d.G, az_net_max_batch(e->net));
     if (mask == e->symr_mask) return AZ_OK;
@@ -3284,17 +3205,14 @@ static int set_walkers(az_engine *e, int k) {
 }
 
 extern "C" int az_engine_set_leaf_batch(az_engine *e, int32_t k) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_leaf_batch");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_leaf_batch");
+    AZ_SETTER(e, "az_engine_set_leaf_batch");
     EngDev &d = e->d;
     AZ_REQUIRE(k >= 1 && k <= AZ_MAX_LEAF_BATCH, AZ_EINVAL, "leaf_batch must be in [1, %d], got %d", AZ_MAX_LEAF_BATCH, k);
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_leaf_batch: an AZ_EVAL_EXTERNAL engine searches one leaf per lock-step (external evaluator)");
     AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_ROLLOUT, AZ_EINVAL, "az_engine_set_leaf_batch: a rollout engine (AZ_EVAL_ROLLOUT) evaluates no leaf with a network");
     AZ_REQUIRE(e->sym_mask == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the engine evaluates over a symmetry mask (0x%x); the ensemble does not combine with leaf_batch", e->sym_mask);
     AZ_REQUIRE(k == 1 || d.gm == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the Gumbel root search is on (az_engine_set_gumbel, m = %d) and searches one leaf per lock-step; switch it off first", d.gm);
-    AZ_REQUIRE(k == 1 || d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_leaf_batch: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served at one leaf per lock-step only; switch it off first", d.cap_nfast);
-    AZ_REQUIRE(k == 1 || d.kforced == 0.0, AZ_EINVAL, "az_engine_set_leaf_batch: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served at one leaf per lock-step only; switch them off first", d.kforced);
+    if (k > 1) AZ_TRY(refuse_beside_cap_or_forced(e, "az_engine_set_leaf_batch", "at one leaf per lock-step"));
     const long long rows = (long long)k * d.G;
     if (e->cfg.evaluator == AZ_EVAL_NET)
         AZ_REQUIRE(rows <= az_net_max_batch(e->net), AZ_EINVAL, "leaf_batch %d of %d slots are %lld rows, the network's max_batch is %d", k, d.G,
@@ -3340,9 +3258,7 @@ static int full_needs_fresh_roots(az_engine *e, const char *who) {
 }
 
 extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, double c_scale, double gumbel_scale) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_gumbel");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_gumbel");
+    AZ_SETTER(e, "az_engine_set_gumbel");
     EngDev &d = e->d;
     AZ_REQUIRE(m >= 0 && m <= AZ_MAX_GUMBEL, AZ_EINVAL, "az_engine_set_gumbel: m must be in [0, %d], got %d", AZ_MAX_GUMBEL, m);
     if (m == 0 && d.gm == 0) return AZ_OK;
@@ -3353,8 +3269,7 @@ extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, dou
         AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_ROLLOUT, AZ_EINVAL, "az_engine_set_gumbel: a rollout engine (AZ_EVAL_ROLLOUT) has no priors to sample the root's actions from");
         AZ_REQUIRE(e->cfg.evaluator != AZ_EVAL_EXTERNAL, AZ_EINVAL, "az_engine_set_gumbel: an AZ_EVAL_EXTERNAL engine searches with the PUCT root only");
         AZ_REQUIRE(e->leaf_batch == 1, AZ_EINVAL, "az_engine_set_gumbel: leaf_batch %d > 1 is in force (az_engine_set_leaf_batch); the Gumbel root search takes one leaf per lock-step", e->leaf_batch);
-        AZ_REQUIRE(d.cap_nfast == 0, AZ_EINVAL, "az_engine_set_gumbel: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served in the PUCT search only; switch it off first", d.cap_nfast);
-        AZ_REQUIRE(d.kforced == 0.0, AZ_EINVAL, "az_engine_set_gumbel: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served in the PUCT search only; switch them off first", d.kforced);
+        AZ_TRY(refuse_beside_cap_or_forced(e, "az_engine_set_gumbel", "in the PUCT search"));
     }
     if (m > 0 && e->gumbel_batch > 1 && e->cfg.evaluator == AZ_EVAL_NET)
         AZ_REQUIRE((long long)e->gumbel_batch * d.G <= az_net_max_batch(e->net), AZ_EINVAL, "az_engine_set_gumbel: gumbel_batch %d of %d slots are %lld rows, the network's max_batch is %d",
@@ -3374,9 +3289,7 @@ extern "C" int az_engine_set_gumbel(az_engine *e, int32_t m, double c_visit, dou
 
 // several Sequential Halving leaves per slot and lock-step (k_step_gumbel_multi): accepted with the mode on or off, in force while it is on
 extern "C" int az_engine_set_gumbel_batch(az_engine *e, int32_t k) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_gumbel_batch");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_gumbel_batch");
+    AZ_SETTER(e, "az_engine_set_gumbel_batch");
     EngDev &d = e->d;
     AZ_REQUIRE(k >= 1 && k <= AZ_MAX_LEAF_BATCH, AZ_EINVAL, "gumbel_batch must be in [1, %d], got %d", AZ_MAX_LEAF_BATCH, k);
     AZ_REQUIRE(k == 1 || e->sym_mask == 0, AZ_EINVAL, "az_engine_set_gumbel_batch: the engine evaluates over a symmetry mask (az_engine_set_symmetry, 0x%x); the ensemble does not combine with gumbel_batch", (unsigned)e->sym_mask);
@@ -3411,9 +3324,7 @@ extern "C" int az_engine_gumbel_considered(az_engine *e, int32_t slot, uint64_t 
 // the paper's v_mix and deterministic non-root selection on top of the Gumbel mode: accepted with the mode on or
 // off, in force while it is on
 extern "C" int az_engine_set_gumbel_full(az_engine *e, int32_t on) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_gumbel_full");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_gumbel_full");
+    AZ_SETTER(e, "az_engine_set_gumbel_full");
     EngDev &d = e->d;
     AZ_REQUIRE(on == 0 || on == 1, AZ_EINVAL, "gumbel_full must be 0 or 1, got %d", on);
     if (on == e->gumbel_full) return AZ_OK;
@@ -3455,28 +3366,15 @@ extern "C" int az_engine_root_value(az_engine *e, int32_t slot, float *v) {
 }
 
 // ---- playout cap randomization (k_step_cap, k_root_prep, k_move) -----------------------------------------------
-// the mode of this engine that the playout cap is not served in, or null (the style of groups_unserved)
-static const char *cap_unserved(const az_engine *e) {
-    if (e->cfg.evaluator == AZ_EVAL_EXTERNAL) return "an AZ_EVAL_EXTERNAL engine (external evaluator)";
-    if (e->cfg.evaluator == AZ_EVAL_ROLLOUT) return "a rollout engine (AZ_EVAL_ROLLOUT)";
-    if (e->sym_mask != 0) return "the symmetry ensemble (az_engine_set_symmetry)";
-    if (e->symr_mask != 0) return "the random symmetry mode (az_engine_set_symmetry_random)";
-    if (e->leaf_batch > 1) return "leaf_batch > 1 (az_engine_set_leaf_batch)";
-    if (e->d.gm > 0) return "the Gumbel search (az_engine_set_gumbel)";
-    return nullptr;
-}
-
 extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_playout_cap");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_playout_cap");
+    AZ_SETTER(e, "az_engine_set_playout_cap");
     EngDev &d = e->d;
     if (n_fast == 0) {  // off: p_full is not looked at
         if (d.cap_nfast == 0) return AZ_OK;
     } else {
         AZ_REQUIRE(n_fast >= 1 && n_fast < e->cfg.n_sim, AZ_EINVAL, "az_engine_set_playout_cap: n_fast must be in [1, n_sim = %d) (0 = off), got %d", e->cfg.n_sim, n_fast);
         AZ_REQUIRE(p_full > 0.0 && p_full <= 1.0, AZ_EINVAL, "az_engine_set_playout_cap: p_full must be in (0, 1], got %g", p_full);
-        const char *why = cap_unserved(e);
+        const char *why = beyond_plain_search(e);
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_playout_cap: the playout cap is not served for %s", why);
         if (n_fast == d.cap_nfast && p_full == d.cap_pfull) return AZ_OK;
     }
@@ -3506,15 +3404,12 @@ extern "C" int az_playout_cap_full(uint32_t seed, uint32_t game_id, int32_t ply,
 }
 
 // ---- forced playouts and policy target pruning (k_step_forced, move_policy) -------------------------------------
-// the modes the plain PUCT search of a network / fake engine excludes are the playout cap's: cap_unserved names them
 extern "C" int az_engine_set_forced_playouts(az_engine *e, double k) {
-    AZ_REQUIRE(e, AZ_EINVAL, "null engine");
-    AZ_NO_OPEN_SEARCH(e, "az_engine_set_forced_playouts");
-    AZ_NOT_IN_CALLBACK(e, "az_engine_set_forced_playouts");
+    AZ_SETTER(e, "az_engine_set_forced_playouts");
     EngDev &d = e->d;
     AZ_REQUIRE(k >= 0.0 && k <= 64.0, AZ_EINVAL, "az_engine_set_forced_playouts: k must be finite and in [0, 64] (0 = off), got %g", k);
     if (k > 0.0) {
-        const char *why = cap_unserved(e);
+        const char *why = beyond_plain_search(e);
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_forced_playouts: forced playouts are not served for %s", why);
     }
     if (k == d.kforced) return AZ_OK;

@@ -1,0 +1,127 @@
+// The launch sequence of one search, decided once per search as a value: which step kernel family an engine's mode launches, how many
+// lock-steps, and every launch's arguments.  az_engine.hip enqueues from the plan (enqueue_search, launch_step), counts lock-steps
+// from it and keys its captured graphs by it; tests/search_plan_table.cpp prints it without a GPU.  With it the host arithmetic that
+// sizes a search's network batch and splits the slots into groups.  Plain C++17, no HIP.
+#pragma once
+#include <tuple>
+
+#include "../../include/az_amd.h"
+
+#define AZ_SLOT_BLOCK 16  // games per 256-thread block of the step kernels (az_engine.hip: GPB): a slot group is whole blocks
+
+// what a plan depends on (az_engine.hip: search_mode fills it from a chain's device view)
+struct SearchMode {
+    bool rollout;  // AZ_EVAL_ROLLOUT: no network
+    int gm;        // the Gumbel root search's m (0: off)
+    int K;         // walkers per slot and lock-step in force
+    bool full;     // the Gumbel mode keeps the network's values (az_engine_set_gumbel_full in force)
+    bool cap;      // the playout cap's budgets are in force
+    bool forced;   // forced playouts are on
+};
+
+// the kernel family of a search's lock-steps
+enum SearchFamily { SF_ROLLOUT, SF_STEP, SF_STEP_CAP, SF_STEP_FORCED, SF_STEP_CAP_FORCED, SF_STEP_MULTI, SF_STEP_GUMBEL, SF_STEP_GUMBEL_MULTI };
+
+inline const char *search_family_name(SearchFamily f) {
+    static const char *const name[] = {"k_rollout_step", "k_step", "k_step_cap", "k_step_forced", "k_step_cap_forced", "k_step_multi", "k_step_gumbel", "k_step_gumbel_multi"};
+    return name[f];
+}
+
+// Lmax(n, m, K) of the Gumbel mode with K walkers (the contract above k_step_gumbel_multi; gumbel.locksteps in Python): the longest
+// per-slot plan of any m0 in 1 .. m.  A pure function of its arguments: the launch sequence of a search captures as a graph.
+inline int gumbel_locksteps(int n, int m, int K) {
+    int best = 0;
+    for (int m0 = 1; m0 <= m; ++m0) {
+        int L = 0, mp = m0, end = 0, steps = 0;
+        for (int b = m0 - 1; b > 0; b >>= 1) ++L;  // ceil(log2 m0)
+        for (int s = 0; s < n;) {
+            while (end <= s) {  // the phase that holds s
+                if (m0 == 1) { end = n; break; }
+                int v = n / (L * mp);
+                end += mp * (v < 1 ? 1 : v);
+                mp = mp / 2 < 2 ? 2 : mp / 2;
+            }
+            const int stop = end < n ? end : n;
+            s += stop - s < K ? stop - s : K;
+            ++steps;
+        }
+        best = steps > best ? steps : best;
+    }
+    return best;
+}
+
+// One search: the root-prior pass (k_root_prep, the network, k_root_init; empty unless a slot holds a fresh root), then L lock-steps
+// of [backup + select -> network] and the last backup.  A rollout engine has no network: n_sim launches of k_rollout_step, nothing else.
+struct SearchPlan {
+    SearchFamily family;
+    bool full;       // the <.., true> instantiation of the two Gumbel families (no run-time branch inside the walk)
+    bool root_pass;  // false only for rollout
+    int L;           // lock-steps that are followed by a forward
+    int launches;    // step-kernel launches: what one search adds to the engine's lockstep_iters
+};
+
+inline SearchPlan plan_search(const SearchMode &m, int n_sim) {
+    SearchPlan p = {SF_STEP, m.full, true, n_sim, 0};
+    if (m.rollout) { p.family = SF_ROLLOUT; p.root_pass = false; p.L = 0; p.launches = n_sim; return p; }  // one launch per simulation
+    if (m.gm > 0 && m.K > 1) { p.family = SF_STEP_GUMBEL_MULTI; p.L = gumbel_locksteps(n_sim, m.gm, m.K); }  // Sequential Halving with K walkers: cut per slot by its own cursor
+    else if (m.K > 1) { p.family = SF_STEP_MULTI; p.L = (n_sim + m.K - 1) / m.K; }  // up to K walkers per slot and lock-step
+    else if (m.gm > 0) p.family = SF_STEP_GUMBEL;
+    else if (m.forced) p.family = m.cap ? SF_STEP_CAP_FORCED : SF_STEP_FORCED;
+    else if (m.cap) p.family = SF_STEP_CAP;  // a slot past its budget idles: no walk, no row
+    p.launches = p.L + 1;
+    return p;
+}
+
+// Launch t of the plan's `launches` (t = L: the last backup; rollout: simulation t, nothing else set).  The families with a slot range
+// take (t, g0, g1) -- the Gumbel one (t, n_sim, g0, g1) -- with the chain's g0 / g1; k_step_multi takes (t, kb, kt),
+// k_step_gumbel_multi (t, n_sim).  Where `select` is set the network follows on the rows counted in batch counter `ctr`, as lock-step
+// t, with kt leaves per slot (0: one).
+struct StepArgs {
+    bool backup, select;  // the kernel's template pair: t > 0, t < L
+    int t;                // the simulation / lock-step index: the kernel's first argument and the forward's step
+    int kb, kt;           // k_step_multi: walkers to back up, walkers to send out; kt also the forward's
+    int ctr;
+};
+
+inline StepArgs plan_step(const SearchPlan &p, int n_sim, int K, int t) {
+    StepArgs a = {t > 0, t < p.L, t, 0, 0, t & 1};
+    const int left = n_sim - t * K;  // k_step_multi: simulations not yet sent out
+    if (p.family == SF_STEP_MULTI) { a.kb = t == 0 ? 0 : (a.select ? K : left + K); a.kt = a.select ? (left < K ? left : K) : 0; }
+    if (p.family == SF_STEP_GUMBEL_MULTI) a.kt = a.select ? K : 0;
+    return a;
+}
+
+// network rows of a search over W slots, up to K leaves each per lock-step; `active` bounds the slots still searching (0: not known)
+inline int search_batch_cap(int W, int K, int active) { return (active > 0 && active < W ? active : W) * K; }
+
+// The cap a captured search is launched with, of R = W * K rows: launch parameters must not change from search to search, so the cap
+// moves in steps of 512 rows -- and only from 4096 rows on, below which the network picks other kernels (an exact cap of 4095 --
+// one game of 4096 over, as happens from ply ~11 on: Othello has early wipe-outs -- would hand the trunk to the one-board-per-wave
+// kernel for the rest of the wave).
+inline int quantised_cap(int R, int cap) { return (R >= 4096 && cap < 4096) ? (cap + 511) / 512 * 512 : R; }
+
+// group i of n over G slots: [g0, g1) in whole blocks (trailing groups may be empty: 40 slots in 4 groups are 16, 16, 8, 0)
+inline void group_range(int G, int i, int n, int *g0, int *g1) {
+    const int blocks = (G + AZ_SLOT_BLOCK - 1) / AZ_SLOT_BLOCK, per = (blocks + n - 1) / n;
+    const int a = i * per * AZ_SLOT_BLOCK, b = (i + 1) * per * AZ_SLOT_BLOCK;
+    *g0 = a < G ? a : G; *g1 = b < G ? b : G;
+}
+
+// The measured rule (profiles/r14_groups.txt): the groups az_engine_run plays with where nothing was asked for.  A
+// shape has n > 1 only where the worst of three grouped runs beat the best of three runs of the build before by more than that
+// build's own spread; every shape that was not measured plays as one group.
+inline int groups_auto(int evaluator, int game, int H, int W, int G) {
+    if (evaluator != AZ_EVAL_NET) return 1;  // the fake evaluator has no network kernels to run beside
+    if (game == AZ_GAME_OTHELLO && H == 8) {
+        if (G >= 4096 && G < 8192) return 2;  // 4096 slots: 2 x 2048 +4.5 %; 4 x 1024 loses (-14 %)
+        if (G >= 32768) return 2;             // 32768 slots: 2 x 16384 +1.3 %
+        return 1;                             // 512 slots: +0.4 %, not worth a second chain; 8192 .. 32767: not measured
+    }
+    if (game == AZ_GAME_CONNECT4 && H == 6 && W == 7) return G >= 8192 ? 4 : 1;  // 8192 slots: 4 x 2048 +9.4 %, 2 x 4096 +0.2 %
+    return 1;
+}
+
+// What a captured search is keyed by.  (What else travels in the launch arguments -- K, m, the playout cap's n_fast and p_full, forced
+// playouts' k, the pools -- drops every graph when it changes: az_engine.hip, drop_graphs.)
+typedef std::tuple<int, bool, int, int, int, int> SearchKey;
+inline SearchKey search_key(const SearchPlan &p, int n_sim, int cap, int g0, int g1) { return SearchKey((int)p.family, p.full, n_sim, cap, g0, g1); }
