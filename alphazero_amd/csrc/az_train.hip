@@ -33,6 +33,11 @@
 //   k_conv1_bwd       boards                       conv1 weight partials -- only where d.F1B is off (workgroups sharing a board; batch > 128, where
 //                                                  its launch also carries fc1's weight-gradient tiles)
 //   k_update          elements                     conv weights / biases / BN2d affine: reduce partials + SGD; running stats; loss log; ++step
+// Row-split steps (batch > 128) add four launches on (16 columns, row block): k_fc_fin behind each k_fc_fwd (merge the row blocks'
+// column statistics -> BN1d, ReLU, dropout) and k_bn1d_bwd_fin behind k_heads_bwd and k_fc_dgrad (add the blocks' backward sums -> dz);
+// fc1's weight-gradient tiles then ride with k_conv1_bwd and k_conv_bwd (l = 3) stands where k_mix2 stood.  Which of these a step
+// launches, on which grid, in which template configuration and with how much LDS is decided in az_train_plan.h (plan_train_step); the
+// host half below carries the plan out.
 // (rocprofv3 on a replayed step, profiles/r05_train_othello8_64_fold.txt: consecutive kernels follow each other with no gap; what a launch
 // costs is inside its own duration -- 5-6 us for k_update / k_conv1_fwd, which do next to nothing -- so a launch is worth removing only when
 // its work fits into a neighbour for less than that.  conv1's backward did (7.3 us gone, +0.8 per k_conv_bwd, +0.7 in k_update); conv1's
@@ -47,6 +52,7 @@
 
 #include "az_device.h"
 #include "az_host.h"
+#include "az_train_plan.h"  // TPB, MAXB, NRBMAX, LDP, TT_LD, the LDS sizes and UPD_*: defined there, shared with the host's plan
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -64,12 +70,9 @@ __device__ unsigned long long az_tprobe[32 * 16];
 #endif
 
 #define NCH 32
-#define LDP 36        // LDS row stride of a 32-channel row: 36 = 4 mod 32 -> the 16 x 4 (row, k) lanes of an A fragment hit every bank twice
-#define TPB 256
 #define BN_EPS 1e-5
 #define BN_MOM 0.1
 #define FPART 65      // forward statistics partial: n, mean[32], M2[32]
-#define MAXB 512
 
 struct Hyper {        // device-resident so that a captured step never goes stale
     float lr, momentum, wd, drop_p;
@@ -103,14 +106,13 @@ struct TDims {
     int CH, CW, P1, H3, W3, P3, H4, W4, P4, FIN, F1, F2, A, NH, NHP;
     int B;    // batch size (multiple of 16, <= MAXB)
     int NB;   // workgroups of the per-board kernels = statistic partials per layer (<= 256)
-    int S;    // workgroups that share a board (4 up to 64 boards, 2 up to 128, else 1): position tiles / taps are dealt out among them
+    int S;    // workgroups that share a board (1; AZ_TRAIN_SPLIT raises it to 2 or 4 while B * S <= 256): position tiles / taps are dealt out among them
     int NRB;  // row blocks of the dense kernels: 1 = a workgroup sees ALL rows of its 16 columns (batch <= 128); above, the rows are split
               // into NRB blocks of RB so that the whole chip works, and the batch statistics go through per-block partials (k_fc_fin, k_bn1d_bwd_fin)
     int RB;   // rows per row block (multiple of 16)
     int F1B;  // 1: conv1's weight gradient is folded into conv2's backward (per-board moment partials, combined by k_update): no k_conv1_bwd launch
 };
 #define C1P 640       // conv1 partial in the folded form: A[9][32] | C[9][32] | sum xhat [32] | Bx[9] (see conv_bwd_body, l = 1)
-#define NRBMAX 8
 
 struct TPtr {
     PSet p, m;
@@ -329,8 +331,7 @@ __global__ __launch_bounds__(TPB) void k_conv1_fwd(TDims d, TPtr q) {
 // LDS: wl[288][LDP] weights (row tap*32+ic, column oc) | ain[(Hin+2 pad)(Win+2 pad)][LDP] input activation with a zero halo | pl[64][LDP]
 // | red[4 waves][16][LDP].  A board is shared by S workgroups (position tiles dealt round robin) and a tile's K by the four waves of
 // its workgroup: at 64 boards all 256 CUs work, and a layer with a single tile (conv4) no longer leaves three waves idle.
-#define CONV_FWD_LDS_FLOATS (288 * LDP + 100 * LDP + 64 * LDP + 64 * LDP + 4 * 32 + 64)
-#define CONV_FWD_LDS_BYTES (CONV_FWD_LDS_FLOATS * 4 + 8 * 32 * 3 * 8)
+// (CONV_FWD_LDS_BYTES, az_train_plan.h: these floats, then the double scratch)
 __global__ __launch_bounds__(TPB) void k_conv_fwd(TDims d, TPtr q, int l /* 1..3 */) {
     extern __shared__ __align__(16) float lds[];
     float *wl = lds, *ain = wl + 288 * LDP, *pl = ain + 100 * LDP, *red = pl + 64 * LDP, *s_scale = red + 64 * LDP, *s_shift = s_scale + 32,
@@ -471,8 +472,7 @@ __global__ __launch_bounds__(TPB) void k_conv_fwd(TDims d, TPtr q, int l /* 1..3
 // local to it; its NW waves split K, their partial sums meet in LDS.  At batch 64 every wave would otherwise walk K in a dozen
 // dependent round trips to L2 (measured: 1.2 us per 16-deep step), so (a) NW grows as the batch shrinks (16 waves at <= 64 rows), and
 // (b) a wave loads PF steps' worth of fragments before it issues their MFMAs.
-//   batch <= 64: RTM 4, NW 16, PF 1 | <= 128: 8, 8, 1 | <= 256: 16, 4, 1 | <= 512: 32, 4, one buffer    (red[NW][B][16] <= 128 KB)
-static inline int fc_lds_bytes(int NW, int B) { return (NW * B * 16 + 4 * 32) * 4 + 768 * 8; }
+//   batch <= 64: RTM 4, NW 16, PF 1 | <= 128: 8, 8, 1 | <= 256: 16, 4, 1 | <= 512: 32, 4, one buffer    (az_train_plan.h: dense_config, fc_lds_bytes)
 
 // acc[rt] += A[16 rt + m][k] Bt[n][k] over k in [kbeg, kend): both operands k-contiguous, a lane loads four consecutive k as one float4
 // and feeds them to four MFMAs (the k index inside a step of 16 is 4 kq + i for A and B alike: the products pair up, only the
@@ -1152,8 +1152,6 @@ AZ_D void fc_wgrad_tile(const TDims &d, const TPtr &q, const Hyper &hp, int laye
             }
 }
 
-static inline int fc_wgrad_blocks(int N, int K, int NW) { return ((N / 32) * (K / 32) + NW - 1) / NW; }
-
 // The same tile with its K (the batch rows) split over FOUR waves: wave (tile, ks) multiplies rows [ks B/4, (ks+1) B/4), the four
 // partial tiles meet in LDS (part[wave][32 x 32]) and wave ks = 0 adds them in order and updates.  At batch 512 one wave walking all
 // rows is sixteen dependent trips of eight MFMA steps; a quarter each is four.  Every wave of the workgroup must call (one barrier).
@@ -1282,8 +1280,7 @@ __global__ __launch_bounds__(NW * 64) void k_mix1(TDims d, TPtr q, int nw) {
 //   weight gradient dW[tap][ic][oc] += sum_p a_{l-1}[p + tap - pad][ic] dz[p][oc]                (M = ic, N = oc, K = positions), one
 //                   (ic tile, oc tile) pair per wave, nine accumulators that live across the workgroup's boards
 // LDS: wl[288][LDP] | dzp[<=100][LDP] dz with a zero halo of 2 - pad | ap[<=100][LDP] a_{l-1} with a zero halo of pad | xh[64][LDP] | dpl[64][LDP]
-#define CONV_BWD_LDS_FLOATS (288 * LDP + 100 * LDP + 100 * LDP + 64 * LDP + 64 * LDP + 10 * 32 + 192 + 64 * LDP + 128 + 64)
-#define CONV_BWD_LDS_BYTES (CONV_BWD_LDS_FLOATS * 4 + 2048 * 8)
+// | the vectors and d0p / xin carved below (CONV_BWD_LDS_BYTES, az_train_plan.h)
 AZ_D void conv_bwd_body(const TDims &d, const TPtr &q, int l, int bidx, int nblocks, float *lds) {
     float *wl = lds, *dzp = wl + 288 * LDP, *ap = dzp + 100 * LDP, *xh = ap + 100 * LDP, *dpl = xh + 64 * LDP;
     float *k1 = dpl + 64 * LDP, *sh_o = k1 + 32, *mean_o = sh_o + 32, *inv_o = mean_o + 32, *k2 = inv_o + 32, *k3 = k2 + 32;
@@ -1543,8 +1540,7 @@ __global__ __launch_bounds__(TPB) void k_mix2(TDims d, TPtr q, int nw) {
 // Row-split path (batch > 128): the workgroups behind the first NB are fc1's weight-gradient tiles (one 32 x 32 tile each, K = the batch
 // rows split over the four waves).  In k_mix2 they share a launch with conv4's backward, whose 107 KB of LDS allow ONE workgroup per CU:
 // 128 tile workgroups of sixteen dependent trips queued with 256 board workgroups for 1.5 rounds; here they need 23 KB and run beside
-// the conv1 workgroups.  (W1 was last read by k_mix1's data gradient and is next read by the following step's forward.)
-#define CONV1_WG_LDS_BYTES (4 * 1024 * 4 + 4 * 32 * 4 + 768 * 8)
+// the conv1 workgroups (CONV1_WG_LDS_BYTES).  (W1 was last read by k_mix1's data gradient and is next read by the following step's forward.)
 __global__ __launch_bounds__(TPB) void k_conv1_bwd(TDims d, TPtr q) {
     if ((int)blockIdx.x >= d.NB) {
         extern __shared__ __align__(16) float wg_lds[];
@@ -1631,12 +1627,7 @@ __global__ __launch_bounds__(TPB) void k_conv1_bwd(TDims d, TPtr q) {
 // ---------------------------------------------------------------------------------------------------------------- update
 // one thread per element of conv1..4 weights / biases and of the four BatchNorm2d affine pairs: reduce the per-workgroup partials in a
 // fixed order, momentum SGD.  The last workgroup also moves the BatchNorm2d running statistics, writes the step's losses and advances
-// the step counter, the permutation offset and the loss slot.
-#define UPD_W1 288
-#define UPD_W (288 + 3 * 9216)
-#define UPD_B (UPD_W + 4 * 32)
-#define UPD_G (UPD_B + 4 * 32)
-#define UPD_ALL (UPD_G + 4 * 32)
+// the step counter, the permutation offset and the loss slot.  (Element ranges UPD_*: az_train_plan.h, which sizes the grid from them.)
 __global__ __launch_bounds__(TPB) void k_update(TDims d, TPtr q) {
     __shared__ float s_mean[32], s_var[32];
     __shared__ double scr[1280];
@@ -1799,7 +1790,6 @@ __global__ __launch_bounds__(TPB) void k_update(TDims d, TPtr q) {
 #define TT_WV 306
 #define TT_BV 315
 #define TT_N 316
-#define TT_LD 12
 struct TttPtr {
     float *p, *m;         // parameters / momentum [316]
     float *rs;            // running statistics: rm1[9] rv1[9] rm2[9] rv2[9]
@@ -1998,7 +1988,6 @@ __global__ __launch_bounds__(TPB) void k_ttt_step(TttPtr q, int B) {
         q.hp->step = hp.step + 1; q.hp->perm_off = hp.perm_off + B; q.hp->loss_off = hp.loss_off + 1;
     }
 }
-static inline int ttt_lds_bytes(int B) { return (320 + 8 * B * TT_LD + 320 + 64) * 4 + (512 + 16 * 5) * 8; }
 
 // ================================================================================================================ host side
 // torch layout <-> the step's layout.  kind 0: copy; 1: conv weight [oc][ic][3][3] <-> [tap][ic][oc] (a = input channels);
@@ -2030,9 +2019,10 @@ struct az_trainer {
     std::map<std::string, TensorRef> tensors;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    hipGraphExec_t graph = nullptr, graph_k = nullptr;  // one step / graph_steps consecutive steps
-    int graph_steps = 8;
-    bool graphs_ok = true, attrs_set = false;
+    hipGraphExec_t graph = nullptr, graph_k = nullptr;  // one step / train_tuning().graph_steps consecutive steps
+    bool graphs_ok = true;  // train_tuning().graph, until a capture fails
+    TrainShape shape = {};
+    TrainPlan plan = {}, attr_plan = {};  // of the current az_trainer_steps call; the one whose kernels last had their attributes set (none: no launch)
     long long steps_done = 0;
     // what the captured graph was recorded with
     const void *g_state = nullptr, *g_pi = nullptr, *g_z = nullptr, *g_perm = nullptr, *g_lp = nullptr, *g_lv = nullptr;
@@ -2060,55 +2050,26 @@ static int palloc(az_trainer *t, float **p, float **m, size_t n, const std::stri
     return AZ_OK;
 }
 
-extern "C" int az_trainer_create(int game, int H, int W, int max_batch, az_trainer **out) {
-    AZ_REQUIRE(out, AZ_EINVAL, "null argument");
-    AZ_REQUIRE(game == AZ_OTHELLO || game == AZ_CONNECT4 || game == AZ_TICTACTOE, AZ_EINVAL, "unknown game %d", game);
-    if (game == AZ_TICTACTOE) {
-        AZ_REQUIRE(H == 3 && W == 3, AZ_EINVAL, "TicTacToe board is 3x3");
-        AZ_REQUIRE(max_batch >= 2 && max_batch <= 256, AZ_EINVAL, "TicTacToeNet training step: batch size in [2, 256], got %d", max_batch);
-        az_trainer *t = new az_trainer();
-        t->game = game; t->H = H; t->W = W; t->max_batch = max_batch;
-        memset(&t->d, 0, sizeof t->d); memset(&t->q, 0, sizeof t->q); memset(&t->tq, 0, sizeof t->tq);
-        t->d.B = max_batch;
-        // no workspace class: k_ttt_step keeps every activation and gradient in LDS
-        int rc = palloc(t, &t->tq.p, &t->tq.m, 320, "all");
-        if (rc == AZ_OK) rc = talloc(t, &t->tq.rs, 36, "rs", AZ_TBUF_RUNNING_STAT);
-        if (rc == AZ_OK) rc = talloc(t, &t->tq.hp, 1, "hyper", AZ_TBUF_HYPER);
-        if (rc == AZ_OK && (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
-                            hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming) != hipSuccess ||
-                            hipEventCreateWithFlags(&t->ev_out, hipEventDisableTiming) != hipSuccess)) { az_set_error("could not create the trainer's stream"); rc = AZ_EHIP; }
-        if (rc != AZ_OK) { az_trainer_destroy(t); return rc; }
-        t->q.hp = t->tq.hp;
-        { const char *g = getenv("AZ_TRAIN_GRAPH"); if (g && atoi(g) == 0) t->graphs_ok = false; }
-        { const char *g = getenv("AZ_TRAIN_GRAPH_STEPS"); if (g && atoi(g) >= 1 && atoi(g) <= 64) t->graph_steps = atoi(g); }
-        auto reg = [&](const char *name, float *p, long long n) { t->tensors[name] = TensorRef{p, n, 0, 0}; };
-        float *P = t->tq.p, *R = t->tq.rs;  // state-dict names of tictactoe.py:296-306
-        reg("fc1.weight", P + TT_W1, 81); reg("fc1.bias", P + TT_B1, 9); reg("bn1.weight", P + TT_G1, 9); reg("bn1.bias", P + TT_BE1, 9);
-        reg("fc2.weight", P + TT_W2, 81); reg("fc2.bias", P + TT_B2, 9); reg("bn2.weight", P + TT_G2, 9); reg("bn2.bias", P + TT_BE2, 9);
-        reg("fc_probs.weight", P + TT_WP, 81); reg("fc_probs.bias", P + TT_BP, 9); reg("fc_value.weight", P + TT_WV, 9); reg("fc_value.bias", P + TT_BV, 1);
-        reg("bn1.running_mean", R, 9); reg("bn1.running_var", R + 9, 9); reg("bn2.running_mean", R + 18, 9); reg("bn2.running_var", R + 27, 9);
-        *out = t;
-        return AZ_OK;
-    }
-    AZ_REQUIRE(max_batch >= 16 && max_batch <= MAXB && max_batch % 16 == 0, AZ_EINVAL, "batch size must be a multiple of 16 in [16, %d], got %d", MAXB, max_batch);
-    TDims d;
-    memset(&d, 0, sizeof d);
-    if (game == AZ_OTHELLO) {
-        AZ_REQUIRE(H == W && H >= 6 && H <= 8 && H % 2 == 0, AZ_EINVAL, "OthelloNet training step: board 6x6 or 8x8, got %dx%d", H, W);
-        d.CH = H; d.CW = W; d.F1 = 1024; d.F2 = 512; d.A = H * W + 1;
-    } else {
-        AZ_REQUIRE(H >= 5 && H <= 8 && W >= 5 && W <= 8, AZ_EINVAL, "Connect4Net training step: board between 5x5 and 8x8, got %dx%d", W, H);
-        d.CH = W; d.CW = H; d.F1 = 64; d.F2 = 32; d.A = W;  // input.view(-1, 1, width, height) (connect4.py:399)
-    }
-    d.P1 = d.CH * d.CW; d.H3 = d.CH - 2; d.W3 = d.CW - 2; d.P3 = d.H3 * d.W3; d.H4 = d.CH - 4; d.W4 = d.CW - 4; d.P4 = d.H4 * d.W4;
-    d.FIN = 32 * d.P4; d.NH = d.A + 1; d.NHP = (d.NH + 15) / 16 * 16;
-    AZ_REQUIRE(d.NHP == 16 || d.NHP == 48 || d.NHP == 80, AZ_EINVAL, "no heads kernel for %d outputs", d.NH);
-    d.B = max_batch; d.S = 1; d.NB = max_batch < 256 ? max_batch : 256; d.NRB = 1; d.RB = max_batch;
-    az_trainer *t = new az_trainer();
-    t->game = game; t->H = H; t->W = W; t->max_batch = max_batch; t->d = d;
-    memset(&t->q, 0, sizeof t->q);
+// TicTacToeNet's allocations and state-dict names (tictactoe.py:296-306).  No workspace class: k_ttt_step keeps every activation and gradient in LDS
+static int ttt_buffers(az_trainer *t) {
+    AZ_TRY(palloc(t, &t->tq.p, &t->tq.m, 320, "all"));
+    AZ_TRY(talloc(t, &t->tq.rs, 36, "rs", AZ_TBUF_RUNNING_STAT));
+    AZ_TRY(talloc(t, &t->tq.hp, 1, "hyper", AZ_TBUF_HYPER));
+    t->q.hp = t->tq.hp;
+    auto reg = [&](const char *name, float *p, long long n) { t->tensors[name] = TensorRef{p, n, 0, 0}; };
+    float *P = t->tq.p, *R = t->tq.rs;
+    reg("fc1.weight", P + TT_W1, 81); reg("fc1.bias", P + TT_B1, 9); reg("bn1.weight", P + TT_G1, 9); reg("bn1.bias", P + TT_BE1, 9);
+    reg("fc2.weight", P + TT_W2, 81); reg("fc2.bias", P + TT_B2, 9); reg("bn2.weight", P + TT_G2, 9); reg("bn2.bias", P + TT_BE2, 9);
+    reg("fc_probs.weight", P + TT_WP, 81); reg("fc_probs.bias", P + TT_BP, 9); reg("fc_value.weight", P + TT_WV, 9); reg("fc_value.bias", P + TT_BV, 1);
+    reg("bn1.running_mean", R, 9); reg("bn1.running_var", R + 9, 9); reg("bn2.running_mean", R + 18, 9); reg("bn2.running_var", R + 27, 9);
+    return AZ_OK;
+}
+
+// the conv nets' allocations and their names in the reference's state dict (othello.py:341-368, connect4.py:370-389)
+static int net_buffers(az_trainer *t) {
+    const TDims &d = t->d;
     int rc = AZ_OK;
-    const size_t B = (size_t)max_batch, NBmax = 256;
+    const size_t B = (size_t)t->max_batch, NBmax = 256;
     const auto nm = [](const char *s, int l) { return s + std::to_string(l + 1); };
 #define WS(p, n, name) if (rc == AZ_OK) rc = talloc(t, &t->q.p, (n), name, AZ_TBUF_WORKSPACE)
 #define RS(p, n, name) if (rc == AZ_OK) rc = talloc(t, &t->q.p, (n), name, AZ_TBUF_RUNNING_STAT)
@@ -2138,16 +2099,7 @@ extern "C" int az_trainer_create(int game, int H, int W, int max_batch, az_train
 #undef WS
 #undef RS
 #undef PA
-    if (rc == AZ_OK && (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
-                        hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&t->ev_out, hipEventDisableTiming) != hipSuccess)) {
-        az_set_error("could not create the trainer's stream");
-        rc = AZ_EHIP;
-    }
-    if (rc != AZ_OK) { az_trainer_destroy(t); return rc; }
-    { const char *g = getenv("AZ_TRAIN_GRAPH"); if (g && atoi(g) == 0) t->graphs_ok = false; }
-    { const char *g = getenv("AZ_TRAIN_GRAPH_STEPS"); if (g && atoi(g) >= 1 && atoi(g) <= 64) t->graph_steps = atoi(g); }
-    // names as in the reference's state dict (othello.py:341-368, connect4.py:370-389)
+    if (rc != AZ_OK) return rc;
     auto reg = [&](const std::string &name, float *p, long long n, int kind = 0, int a = 0) { t->tensors[name] = TensorRef{p, n, kind, a}; };
     for (int l = 0; l < 4; ++l) {
         const std::string c = "conv" + std::to_string(l + 1), b = "bn" + std::to_string(l + 1);
@@ -2162,6 +2114,44 @@ extern "C" int az_trainer_create(int game, int H, int W, int max_batch, az_train
     reg("fc_bn2.weight", t->q.p.g2, d.F2); reg("fc_bn2.bias", t->q.p.be2, d.F2); reg("fc_bn2.running_mean", t->q.rm2, d.F2); reg("fc_bn2.running_var", t->q.rv2, d.F2);
     reg("fc_probs.weight", t->q.p.wh, (long long)d.A * d.F2); reg("fc_probs.bias", t->q.p.bh, d.A);
     reg("fc_value.weight", t->q.p.wh + (size_t)d.A * d.F2, d.F2); reg("fc_value.bias", t->q.p.bh + d.A, 1);
+    return AZ_OK;
+}
+
+extern "C" int az_trainer_create(int game, int H, int W, int max_batch, az_trainer **out) {
+    AZ_REQUIRE(out, AZ_EINVAL, "null argument");
+    AZ_REQUIRE(game == AZ_OTHELLO || game == AZ_CONNECT4 || game == AZ_TICTACTOE, AZ_EINVAL, "unknown game %d", game);
+    TDims d;
+    memset(&d, 0, sizeof d);
+    if (game == AZ_TICTACTOE) {
+        AZ_REQUIRE(H == 3 && W == 3, AZ_EINVAL, "TicTacToe board is 3x3");
+        AZ_REQUIRE(max_batch >= 2 && max_batch <= TTT_MAXB, AZ_EINVAL, "TicTacToeNet training step: batch size in [2, %d], got %d", TTT_MAXB, max_batch);
+    } else {
+        AZ_REQUIRE(max_batch >= 16 && max_batch <= MAXB && max_batch % 16 == 0, AZ_EINVAL, "batch size must be a multiple of 16 in [16, %d], got %d", MAXB, max_batch);
+        if (game == AZ_OTHELLO) {
+            AZ_REQUIRE(H == W && H >= 6 && H <= 8 && H % 2 == 0, AZ_EINVAL, "OthelloNet training step: board 6x6 or 8x8, got %dx%d", H, W);
+            d.CH = H; d.CW = W; d.F1 = 1024; d.F2 = 512; d.A = H * W + 1;
+        } else {
+            AZ_REQUIRE(H >= 5 && H <= 8 && W >= 5 && W <= 8, AZ_EINVAL, "Connect4Net training step: board between 5x5 and 8x8, got %dx%d", W, H);
+            d.CH = W; d.CW = H; d.F1 = 64; d.F2 = 32; d.A = W;  // input.view(-1, 1, width, height) (connect4.py:399)
+        }
+        d.P1 = d.CH * d.CW; d.H3 = d.CH - 2; d.W3 = d.CW - 2; d.P3 = d.H3 * d.W3; d.H4 = d.CH - 4; d.W4 = d.CW - 4; d.P4 = d.H4 * d.W4;
+        d.FIN = 32 * d.P4; d.NH = d.A + 1; d.NHP = (d.NH + 15) / 16 * 16;
+        AZ_REQUIRE(d.NHP == 16 || d.NHP == 48 || d.NHP == 80, AZ_EINVAL, "no heads kernel for %d outputs", d.NH);
+    }
+    az_trainer *t = new az_trainer();
+    t->game = game; t->H = H; t->W = W; t->max_batch = max_batch;
+    t->d = d;  // B, S, NB, RB, NRB, F1B: from the plan of every az_trainer_steps call
+    t->shape = TrainShape{game, d.F1, d.F2, d.FIN, d.NHP};
+    t->graphs_ok = train_tuning().graph;
+    memset(&t->q, 0, sizeof t->q); memset(&t->tq, 0, sizeof t->tq);
+    int rc = game == AZ_TICTACTOE ? ttt_buffers(t) : net_buffers(t);
+    if (rc == AZ_OK && (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
+                        hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming) != hipSuccess ||
+                        hipEventCreateWithFlags(&t->ev_out, hipEventDisableTiming) != hipSuccess)) {
+        az_set_error("could not create the trainer's stream");
+        rc = AZ_EHIP;
+    }
+    if (rc != AZ_OK) { az_trainer_destroy(t); return rc; }
     *out = t;
     return AZ_OK;
 }
@@ -2254,112 +2244,74 @@ extern "C" int az_trainer_set_lr(az_trainer *t, float lr, void *stream) {
     return t_leave(t, user);
 }
 
-static bool wgrad_beside_conv1() {  // AZ_TRAIN_WG_LATE=0: fc1's weight gradient stays in k_mix2 on the row-split path too
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("AZ_TRAIN_WG_LATE"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return v == 1;
-}
-
-static bool fc2_rows64() {  // AZ_TRAIN_FC2_RB64=0: fc2's forward keeps the step's row-block size
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("AZ_TRAIN_FC2_RB64"); v = (e && atoi(e) == 0) ? 0 : 1; }
-    return v == 1;
-}
-
-template <int RTM, int NW, int PF, int NT, bool SPLIT>
-static int enqueue_step_t(az_trainer *t) {
-    const TDims &d = t->d;
-    const TPtr &q = t->q;
-    hipStream_t st = t->stream;
-    const int Bw = SPLIT ? RTM * 16 : d.B;  // rows a dense workgroup holds
-    const int fcl = fc_lds_bytes(NW, Bw), hbl = Bw * 16 * 4 + 768 * 8;
-    const unsigned NRB = SPLIT ? (unsigned)d.NRB : 1u;
-#define SETATTR(k, bytes) AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)))
-    if (!t->attrs_set) {
-        SETATTR(k_conv_fwd, CONV_FWD_LDS_BYTES); SETATTR(k_conv_bwd, CONV_BWD_LDS_BYTES); SETATTR(k_mix2, CONV_BWD_LDS_BYTES);
-        t->attrs_set = true;
+// Carries out launch record l with kernel k -- or, with `attr`, raises k's dynamic-LDS limit to max_lds: the most this instantiation
+// is ever launched with (0: it never asks for more than the default limit)
+template <typename... P, typename... A>
+static int issue(void (*k)(P...), int max_lds, bool attr, const TrainLaunch &l, hipStream_t st, A... args) {
+    if (attr) {
+        if (max_lds) AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        return AZ_OK;
     }
-    {   // per instantiation: the largest batch this configuration serves (set every time: cheap, and correct across batch sizes)
-        const int fmax = fc_lds_bytes(NW, RTM * 16);
-        SETATTR((k_fc_fwd<RTM, NW, PF, SPLIT>), fmax); SETATTR((k_fc_dgrad<RTM, NW, PF, SPLIT>), fmax); SETATTR((k_mix1<RTM, NW, PF, SPLIT>), fmax);
-        SETATTR((k_heads_bwd<RTM, NT, SPLIT>), RTM * 16 * 16 * 4 + 768 * 8);
-    }
-#undef SETATTR
-#define SETATTR2(k, bytes) AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)))
-    const dim3 tb(TPB), tw(NW * 64);
-    hipLaunchKernelGGL(k_conv1_fwd, dim3(d.NB), tb, 0, st, d, q);
-    for (int l = 1; l <= 3; ++l) hipLaunchKernelGGL(k_conv_fwd, dim3(d.NB), tb, CONV_FWD_LDS_BYTES, st, d, q, l);
-    hipLaunchKernelGGL((k_fc_fwd<RTM, NW, PF, SPLIT>), dim3(d.F1 / 16, NRB), tw, fcl, st, d, q, 1);
-    if (SPLIT) hipLaunchKernelGGL(k_fc_fin, dim3(d.F1 / 16, NRB), tb, 0, st, d, q, 1);
-    if (SPLIT && RTM == 8 && fc2_rows64()) {
-        // fc2 has half of fc1's columns: at 128 rows per block its forward would run 32 x NRB = 128 workgroups on 256 CUs.  It takes the
-        // 64-row configuration (sixteen waves split K = 1024) instead; its statistics partials and its finalize kernel follow that block size
-        TDims d2 = d;
-        d2.RB = 64; d2.NRB = (d.B + 63) / 64;
-        SETATTR2((k_fc_fwd<4, 16, 1, true>), fc_lds_bytes(16, 64));
-        hipLaunchKernelGGL((k_fc_fwd<4, 16, 1, true>), dim3(d.F2 / 16, (unsigned)d2.NRB), dim3(16 * 64), fc_lds_bytes(16, 64), st, d2, q, 2);
-        hipLaunchKernelGGL(k_fc_fin, dim3(d.F2 / 16, (unsigned)d2.NRB), tb, 0, st, d2, q, 2);
-    } else {
-        hipLaunchKernelGGL((k_fc_fwd<RTM, NW, PF, SPLIT>), dim3(d.F2 / 16, NRB), tw, fcl, st, d, q, 2);
-        if (SPLIT) hipLaunchKernelGGL(k_fc_fin, dim3(d.F2 / 16, NRB), tb, 0, st, d, q, 2);
-    }
-    hipLaunchKernelGGL((k_heads_fwd<NT, 8>), dim3(d.B / 16), dim3(8 * 64), 0, st, d, q);
-    hipLaunchKernelGGL((k_heads_bwd<RTM, NT, SPLIT>), dim3(d.F2 / 16, NRB), tb, hbl, st, d, q);
-    if (SPLIT) hipLaunchKernelGGL(k_bn1d_bwd_fin, dim3(d.F2 / 16, NRB), tb, 0, st, d, q, 2);
-    hipLaunchKernelGGL((k_fc_dgrad<RTM, NW, PF, SPLIT>), dim3(d.F1 / 16, NRB), tw, fcl, st, d, q);
-    if (SPLIT) hipLaunchKernelGGL(k_bn1d_bwd_fin, dim3(d.F1 / 16, NRB), tb, 0, st, d, q, 1);
-    const int nw2 = fc_wgrad_blocks(d.F2, d.F1, SPLIT ? NW / 4 : NW), nw1 = fc_wgrad_blocks(d.F1, d.FIN, 4);
-    hipLaunchKernelGGL((k_mix1<RTM, NW, PF, SPLIT>), dim3(nw2 + (d.FIN / 16) * NRB), tw, fcl, st, d, q, nw2);
-    const bool wg_late = SPLIT && wgrad_beside_conv1();  // fc1's weight gradient beside conv1's backward instead of conv4's
-    if (wg_late) hipLaunchKernelGGL(k_conv_bwd, dim3(d.NB), tb, CONV_BWD_LDS_BYTES, st, d, q, 3);
-    else hipLaunchKernelGGL(k_mix2, dim3(nw1 + d.NB), tb, CONV_BWD_LDS_BYTES, st, d, q, nw1);
-    hipLaunchKernelGGL(k_conv_bwd, dim3(d.NB), tb, CONV_BWD_LDS_BYTES, st, d, q, 2);
-    hipLaunchKernelGGL(k_conv_bwd, dim3(d.NB), tb, CONV_BWD_LDS_BYTES, st, d, q, 1);
-    if (wg_late) hipLaunchKernelGGL(k_conv1_bwd, dim3(d.NB + (d.F1 / 32) * (d.FIN / 32)), tb, CONV1_WG_LDS_BYTES, st, d, q);
-    else if (!d.F1B) hipLaunchKernelGGL(k_conv1_bwd, dim3(d.NB), tb, 0, st, d, q);
-    hipLaunchKernelGGL(k_update, dim3((UPD_ALL + 63) / 64 + 4 + (d.F1B ? 6 : 0)), tb, 0, st, d, q);
-    AZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k, dim3(l.gx, l.gy), dim3(l.threads), l.lds, st, args...);
     return AZ_OK;
 }
 
-template <int RTM, int NW, int PF, bool SPLIT = false>
-static int enqueue_step_r(az_trainer *t) {
-    switch (t->d.NHP) {
-        case 16: return enqueue_step_t<RTM, NW, PF, 1, SPLIT>(t);
-        case 48: return enqueue_step_t<RTM, NW, PF, 3, SPLIT>(t);
-        default: return enqueue_step_t<RTM, NW, PF, 5, SPLIT>(t);
+// the dense templates of one configuration; a workgroup of it holds at most RTM * 16 rows
+template <int RTM, int NW, int PF, bool SPLIT>
+static int launch_dense(az_trainer *t, const TrainLaunch &l, const TDims &d, bool attr) {
+    const int fmax = fc_lds_bytes(NW, RTM * 16), hmax = heads_bwd_lds_bytes(RTM * 16);
+    switch (l.k) {
+        case TK_FC_FWD: return issue(k_fc_fwd<RTM, NW, PF, SPLIT>, fmax, attr, l, t->stream, d, t->q, l.arg);
+        case TK_FC_DGRAD: return issue(k_fc_dgrad<RTM, NW, PF, SPLIT>, fmax, attr, l, t->stream, d, t->q);
+        case TK_MIX1: return issue(k_mix1<RTM, NW, PF, SPLIT>, fmax, attr, l, t->stream, d, t->q, l.arg);
+        default: break;  // TK_HEADS_BWD
+    }
+    if (t->plan.NT == 1) return issue(k_heads_bwd<RTM, 1, SPLIT>, hmax, attr, l, t->stream, d, t->q);
+    if (t->plan.NT == 3) return issue(k_heads_bwd<RTM, 3, SPLIT>, hmax, attr, l, t->stream, d, t->q);
+    return issue(k_heads_bwd<RTM, 5, SPLIT>, hmax, attr, l, t->stream, d, t->q);
+}
+
+// The one place that names the step's kernels: launch record l of t->plan -> its kernel, launched (or, with `attr`, prepared: issue).
+// d: t->d with the launch's own RB / NRB.
+static int launch_one(az_trainer *t, const TrainLaunch &l, const TDims &d, bool attr) {
+    hipStream_t st = t->stream;
+    const TPtr &q = t->q;
+    switch (l.k) {
+        case TK_TTT_STEP: return issue(k_ttt_step, ttt_lds_bytes(TTT_MAXB), attr, l, st, t->tq, d.B);
+        case TK_CONV1_FWD: return issue(k_conv1_fwd, 0, attr, l, st, d, q);
+        case TK_CONV_FWD: return issue(k_conv_fwd, CONV_FWD_LDS_BYTES, attr, l, st, d, q, l.arg);
+        case TK_FC_FIN: return issue(k_fc_fin, 0, attr, l, st, d, q, l.arg);
+        case TK_HEADS_FWD:
+            if (t->plan.NT == 1) return issue(k_heads_fwd<1, 8>, 0, attr, l, st, d, q);
+            if (t->plan.NT == 3) return issue(k_heads_fwd<3, 8>, 0, attr, l, st, d, q);
+            return issue(k_heads_fwd<5, 8>, 0, attr, l, st, d, q);
+        case TK_BN1D_BWD_FIN: return issue(k_bn1d_bwd_fin, 0, attr, l, st, d, q, l.arg);
+        case TK_MIX2: return issue(k_mix2, CONV_BWD_LDS_BYTES, attr, l, st, d, q, l.arg);
+        case TK_CONV_BWD: return issue(k_conv_bwd, CONV_BWD_LDS_BYTES, attr, l, st, d, q, l.arg);
+        case TK_CONV1_BWD: return issue(k_conv1_bwd, 0, attr, l, st, d, q);
+        case TK_UPDATE: return issue(k_update, 0, attr, l, st, d, q);
+        default: break;  // the dense templates: by the rows the launch's workgroups hold
+    }
+    const DenseConfig c = dense_config(l.RB, t->plan.SPLIT != 0);
+    if (c.SPLIT) return c.RTM == 4 ? launch_dense<4, 16, 1, true>(t, l, d, attr) : launch_dense<8, 8, 1, true>(t, l, d, attr);
+    switch (c.RTM) {
+        case 4: return launch_dense<4, 16, 1, false>(t, l, d, attr);
+        case 8: return launch_dense<8, 8, 1, false>(t, l, d, attr);
+        case 16: return launch_dense<16, 4, 1, false>(t, l, d, attr);
+        default: return launch_dense<32, 4, 0, false>(t, l, d, attr);
     }
 }
 
-// rows per row block of the dense kernels for batch size B: 0 = no split (a workgroup sees all rows of its 16 columns: <= 128 rows,
-// where sixteen or eight waves splitting K keep a 16-column workgroup short); above, blocks of 64 rows (the batch-64 configuration:
-// sixteen waves split K) up to 368 rows and of 128 rows (eight waves) from 384 on, so that fc1 / fc2 run 4 x 64 / 4 x 32 workgroups at
-// batch 512 instead of 64 / 32 (measured, ms per step at 256 / 512: unsplit 0.412 / 0.658, blocks of 64 0.315 / 0.442, of 128
-// 0.337 / 0.408).  AZ_TRAIN_RB = 0 / 64 / 128 overrides.
-static int dense_row_block(int B) {
-    static int force = -2;
-    if (force == -2) { const char *e = getenv("AZ_TRAIN_RB"); force = e ? atoi(e) : -1; }
-    if (force == 0 || ((force == 64 || force == 128) && B > force)) return force;
-    return B > 128 ? (B >= 384 ? 128 : 64) : 0;
-}
-
-static int enqueue_step(az_trainer *t) {  // (row tiles, waves that split K, prefetch depth) by batch size: see "dense layers: shared pieces"
-    if (t->game == AZ_TICTACTOE) {
-        const int lds = ttt_lds_bytes(t->d.B);
-        if (!t->attrs_set) {
-            AZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ttt_step), hipFuncAttributeMaxDynamicSharedMemorySize, ttt_lds_bytes(256)));
-            t->attrs_set = true;
-        }
-        hipLaunchKernelGGL(k_ttt_step, dim3(1), dim3(TPB), lds, t->stream, t->tq, t->d.B);
-        AZ_HIP(hipGetLastError());
-        return AZ_OK;
+// one step of t->plan onto the trainer's stream (attr: no launch, the attributes of the step's kernels instead)
+static int enqueue_step(az_trainer *t, bool attr = false) {
+    TDims d = t->d;
+    for (int i = 0; i < t->plan.n_launches; ++i) {
+        const TrainLaunch &l = t->plan.launches[i];
+        d.RB = l.RB; d.NRB = l.NRB;
+        AZ_TRY(launch_one(t, l, d, attr));
     }
-    const int RT = t->d.B / 16;
-    if (t->d.NRB > 1) return t->d.RB == 64 ? enqueue_step_r<4, 16, 1, true>(t) : enqueue_step_r<8, 8, 1, true>(t);
-    if (RT <= 4) return enqueue_step_r<4, 16, 1>(t);  // (both register buffers two steps deep: 0.219 vs 0.195 ms at batch 64)
-    if (RT <= 8) return enqueue_step_r<8, 8, 1>(t);
-    if (RT <= 16) return enqueue_step_r<16, 4, 1>(t);
-    return enqueue_step_r<32, 4, 0>(t);
+    AZ_HIP(hipGetLastError());
+    return AZ_OK;
 }
 
 // n_steps optimisation steps on device-resident samples: step s trains on rows d_perm[s * B .. s * B + B) of (d_state int8 [S][cells],
@@ -2387,19 +2339,11 @@ extern "C" int az_trainer_steps(az_trainer *t, const int8_t *d_state, const floa
     const bool same = t->g_state == d_state && t->g_pi == d_pi && t->g_z == d_z && t->g_perm == d_perm && t->g_lp == d_loss_pi && t->g_lv == d_loss_v && t->g_B == B;
     if (!same && t->graph) { (void)hipGraphExecDestroy(t->graph); t->graph = nullptr; }
     if (!same && t->graph_k) { (void)hipGraphExecDestroy(t->graph_k); t->graph_k = nullptr; }
-    {   // workgroups per board in the conv kernels (AZ_TRAIN_SPLIT = 1 / 2 / 4 overrides; must divide 256)
-        static int force = -1;
-        if (force < 0) { const char *e = getenv("AZ_TRAIN_SPLIT"); force = e ? atoi(e) : 0; }
-        int S = force == 1 || force == 2 || force == 4 ? force : 1;
-        while (S > 1 && B * S > 256) S >>= 1;
-        t->d.B = B; t->d.S = S; t->d.NB = B * S < 256 ? B * S : 256;
-        const int rb = dense_row_block(B);
-        t->d.RB = rb ? rb : B; t->d.NRB = rb ? (B + rb - 1) / rb : 1;
-        // conv1's backward folded into conv2's (one launch less) where a workgroup holds whole boards and fc1's weight gradient does not
-        // need k_conv1_bwd's launch (AZ_TRAIN_FOLD1=0: the separate kernel everywhere)
-        static int fold = -1;
-        if (fold < 0) { const char *e = getenv("AZ_TRAIN_FOLD1"); fold = e ? atoi(e) : 1; }
-        t->d.F1B = (fold && S == 1 && rb == 0) ? 1 : 0;
+    const TrainPlan &p = t->plan = plan_train_step(t->shape, train_tuning(), B);  // every step of this call
+    t->d.B = p.B; t->d.S = p.S; t->d.NB = p.NB; t->d.RB = p.RB; t->d.NRB = p.NRB; t->d.F1B = p.F1B;
+    if (!same_plan(p, t->attr_plan)) {  // before any launch or capture: the dynamic-LDS limits of the kernels this plan launches
+        AZ_TRY(enqueue_step(t, true));
+        t->attr_plan = p;
     }
     t->q.state = d_state; t->q.pi = d_pi; t->q.z = d_z; t->q.perm = (const long long *)d_perm; t->q.loss_pi = d_loss_pi; t->q.loss_v = d_loss_v;
     t->tq.state = d_state; t->tq.pi = d_pi; t->tq.z = d_z; t->tq.perm = (const long long *)d_perm; t->tq.loss_pi = d_loss_pi; t->tq.loss_v = d_loss_v;
@@ -2410,7 +2354,7 @@ extern "C" int az_trainer_steps(az_trainer *t, const int8_t *d_state, const floa
     static_assert(sizeof tail == sizeof(Hyper) - offsetof(Hyper, perm_off), "Hyper tail layout");
     AZ_HIP(hipMemcpy(&t->q.hp->perm_off, &tail, sizeof tail, hipMemcpyHostToDevice));
     int done = 0;
-    if (t->steps_done == 0) {  // the very first step of a trainer runs as plain launches: kernel attributes get set outside a capture
+    if (t->steps_done == 0) {  // the very first step of a trainer runs as plain launches (which steps replay is behaviour the tests pin; it needs no capture to be valid)
         AZ_TRY(enqueue_step(t));
         done = 1; t->steps_done = 1;
     }
@@ -2429,9 +2373,10 @@ extern "C" int az_trainer_steps(az_trainer *t, const int8_t *d_state, const floa
         if (g) (void)hipGraphDestroy(g);
     };
     if (t->graphs_ok && !t->graph && n_steps - done >= 1) capture(1, &t->graph);
-    if (t->graphs_ok && !t->graph_k && t->graph_steps > 1 && n_steps - done >= t->graph_steps) capture(t->graph_steps, &t->graph_k);
+    const int gk = train_tuning().graph_steps;
+    if (t->graphs_ok && !t->graph_k && gk > 1 && n_steps - done >= gk) capture(gk, &t->graph_k);
     while (done < n_steps) {
-        if (t->graph_k && n_steps - done >= t->graph_steps) { AZ_HIP(hipGraphLaunch(t->graph_k, t->stream)); done += t->graph_steps; t->steps_done += t->graph_steps; }
+        if (t->graph_k && n_steps - done >= gk) { AZ_HIP(hipGraphLaunch(t->graph_k, t->stream)); done += gk; t->steps_done += gk; }
         else if (t->graph) { AZ_HIP(hipGraphLaunch(t->graph, t->stream)); done++; t->steps_done++; }
         else { AZ_TRY(enqueue_step(t)); done++; t->steps_done++; }
     }
