@@ -21,6 +21,8 @@
 //   k_trunk_quad<CH,CW,FORM>: k_trunk with conv3 / conv4 over row tiles that the workgroup's four boards share (8x8, 7x6 planes);
 //                    FORM 1 / 2 run conv2 in four passes and fit four / three waves on a SIMD, beside another chain's kernels.
 //   k_gemm<...>    : LDS-tiled f32 MFMA GEMM with bias(+ReLU) epilogue for fc1 / fc2.
+//   k_gemm_ring<...>: k_gemm's 64 x 64 tile with a ring of K tiles in LDS: the MFMA chain runs across tile boundaries (one wave per SIMD
+//                    beside another chain's kernels).
 //   k_heads        : policy+value GEMM (N padded to 16) fused with softmax / tanh.
 //   k_mlp          : the 316-parameter TicTacToe MLP, one thread per board.
 #include <math.h>
@@ -1603,7 +1605,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm(const float *__restrict__ A, co
         unsigned long long p_end = 0;
         STAMP(p_end)
         unsigned long long *o = az_probe_buf + (size_t)bid * 8;
-        o[0] = ph_issue; o[1] = ph_comp; o[2] = ph_store; o[3] = ph_bar; o[4] = p_end - p_begin; o[5] = p_begin; o[6] = p_end;
+        o[0] = ph_issue; o[1] = ph_comp; o[2] = ph_store; o[3] = ph_bar; o[4] = (unsigned long long)T; o[5] = p_begin; o[6] = p_end;  // tools/probe_gemm.py
         o[7] = __builtin_amdgcn_s_memrealtime() - rt_begin;  // 100 MHz ticks
     }
 #endif
@@ -1620,6 +1622,145 @@ __global__ __launch_bounds__(256, 2) void k_gemm(const float *__restrict__ A, co
                 if (RELU) v = v > 0.0f ? v : 0.0f;
                 if (row < M) C[(size_t)row * N + col] = v;
             }
+}
+
+// k_gemm's ring form (StagePlan::gemm_form 1): the 64 x 64 tile for a launch with ONE wave per SIMD and nothing of
+// its own to cover a K-tile boundary (fc2 of a 2048-row slot group beside the other group's chain).  A wave of that tile has a single
+// accumulator, so 32 k are 16 dependent MFMAs = 1024 cycles, and the form above stops the chain behind each of them: wait for the
+// staged loads, write LDS, barrier, first fragment reads.  Here the chain runs through:
+//   * K tiles of BK = 16 in a ring of three LDS buffers: 25 KB, less than the double buffer's 33 KB (beside another chain every KB of the
+//     request is room taken from the neighbour's blocks: the double buffer padded to 50 KB cost the pair of forwards 5 %).
+//   * Tile t + 2 is written inside the k-steps of tile t, one staging register per k-step, and the register is refilled with its part
+//     of tile t + 6 right behind its store: four register sets, a load rests four tiles (2048 cycles) before its wait.
+//   * The barrier at the end of tile t publishes tile t + 2; tile t + 1 was published one barrier earlier, so the fragment ring (FRD)
+//     runs across the boundary: the first FRD - 1 k-steps of tile t + 1 are read under the last MFMAs of tile t, and the barrier has
+//     no LDS read and no store between itself and the next MFMA, only the skew of the four waves.
+//   * Ring safety with one barrier per tile: tile t's stores go to the buffer tile t - 1 was read from; every wave's last read of it
+//     was issued (and, by the barrier's lgkmcnt(0), had landed) before the barrier at the end of tile t - 1.
+// The tile loop is fully unrolled (KT = K / 32 >= 2), for the reason given above.  Same chain: bias, then k ascending.
+template <bool RELU, int KT>
+__global__ __launch_bounds__(256, 2) void k_gemm_ring(const float *__restrict__ A, const float *__restrict__ Bw, const float *__restrict__ bias,
+                                                    float *__restrict__ C, int M, int N, const int *__restrict__ dyn_count) {
+    static_assert(KT >= 2, "NSET tiles are staged before the first MFMA");
+    if (dyn_count) { int c = *dyn_count; M = c < M ? c : M; }
+    constexpr int BM = 64, BN = 64, BK = 16, K = KT * 32, T = K / BK, NBUF = 3, NSET = 4, FRD = 4, KS = BK / 2, ASTR = BK + 1, BSTR = BN;
+    const int nbx = N / BN, nb = nbx * (int)gridDim.y;
+    int bid = (int)blockIdx.y * nbx + (int)blockIdx.x;
+    if (nb % 8 == 0) bid = (bid % 8) * (nb / 8) + bid / 8;  // XCD-aware tile order, as k_gemm
+    const int tile_y = bid / nbx, tile_x = bid % nbx;
+    if (tile_y * BM >= M) return;  // whole block beyond the rows filled this step (uniform exit)
+    extern __shared__ __attribute__((aligned(16))) float gsm[];
+    float *As = gsm;                       // [NBUF][BM][ASTR]
+    float *Bs = gsm + NBUF * BM * ASTR;    // [NBUF][BK][BSTR]   (NBUF*BM*ASTR is a multiple of 4 floats: 16-byte aligned)
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;
+    const int bm0 = tile_y * BM, bn0 = tile_x * BN;
+    f32x16 acc;
+    {
+        const float bv = bias[bn0 + wn0 + (lane & 31)];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = bv;
+    }
+    // staging: per K tile a thread carries one 4-float piece of the A tile (row arow, k quad aq) and one of the B tile (k row bkr,
+    // column quad bc): slots 0 and 1 of a register set; tile u lives in set u % NSET
+    const int arow = tid >> 2, aq = tid & 3, bkr = tid >> 4, bc = tid & 15;
+    int gr = bm0 + arow;
+    gr = gr < M ? gr : M - 1;
+    const float *ap = A + (size_t)gr * K + 4 * aq;
+    const unsigned bstep = 4u * BK * N;  // the launch holds 4 K N below 2^32
+    unsigned bo = 4u * (bkr * N + bn0 + 4 * bc);
+    float *sa = As + arow * ASTR + 4 * aq, *sb = Bs + bkr * BSTR + 4 * bc;
+    float4 rs[NSET][2];
+    // B walks K tile by tile on one byte offset (tiles are loaded in ascending order): formed from t, all T addresses would be live at once
+#define RING_LD(s, j, t)                                                                                              \
+    {                                                                                                                 \
+        if ((j) == 0) rs[s][0] = *reinterpret_cast<const float4 *>(ap + (t) * BK);                                    \
+        else {                                                                                                        \
+            rs[s][1] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(Bw) + bo);                    \
+            bo += bstep;                                                                                              \
+            asm("" : "+v"(bo));                                                                                       \
+        }                                                                                                             \
+    }
+#define RING_ST(s, j, buf)                                                                                            \
+    {                                                                                                                 \
+        if ((j) == 0) {                                                                                               \
+            float *d = sa + (buf) * BM * ASTR;                                                                        \
+            d[0] = rs[s][0].x; d[1] = rs[s][0].y; d[2] = rs[s][0].z; d[3] = rs[s][0].w;                               \
+        } else *reinterpret_cast<float4 *>(sb + (buf) * BK * BSTR) = rs[s][1];                                        \
+    }
+    // prologue: tiles 0 and 1 into the ring, the NSET tiles behind them into the registers
+#pragma unroll
+    for (int u = 0; u < NSET; ++u)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) RING_LD(u, j, u)
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            RING_ST(u, j, u)
+            if (u + NSET < T) RING_LD(u, j, u + NSET)
+        }
+    __syncthreads();
+    const float *as = As + (wm0 + (lane & 31)) * ASTR + (lane >> 5);
+    const float *bs = Bs + (lane >> 5) * BSTR + wn0 + (lane & 31);
+    float afr[FRD], bfr[FRD];
+#pragma unroll
+    for (int p = 0; p < FRD - 1; ++p) {  // k-steps 0 .. FRD - 2 of tile 0
+        afr[p] = as[p * 2];
+        bfr[p] = bs[p * 2 * BSTR];
+    }
+    unsigned long long p0 = 0, p1 = 0, p2 = 0, ph_comp = 0, ph_bar = 0, p_begin = 0;
+    (void)p0; (void)p1; (void)p2; (void)ph_comp; (void)ph_bar; (void)p_begin;
+    STAMP(p_begin)
+#ifdef AZ_PROBE
+    const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();
+#endif
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        STAMP(p0)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int g = t * KS + ks, gn = g + FRD - 1;  // k-steps counted through the tiles: the fragment ring ignores the boundary
+            if (gn < T * KS) {
+                afr[gn % FRD] = as[(gn / KS % NBUF) * BM * ASTR + (gn % KS) * 2];
+                bfr[gn % FRD] = bs[(gn / KS % NBUF) * BK * BSTR + (gn % KS) * 2 * BSTR];
+            }
+            if (ks == 2 || ks == 4) {  // one slot of tile t + 2 to LDS, its register refilled with tile t + 2 + NSET
+                if (t + 2 < T) RING_ST((t + 2) % NSET, ks / 2 - 1, (t + 2) % NBUF)
+                if (t + 2 + NSET < T) RING_LD((t + 2) % NSET, ks / 2 - 1, t + 2 + NSET)
+            }
+            // the MFMA takes its fragments through an ordered no-op: instruction selection keeps it behind this k-step's memory
+            // instructions (a plain sched_barrier left the MFMAs of the staging k-steps free to gather ahead of their reads)
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("" : "+v"(afr[g % FRD]), "+v"(bfr[g % FRD]));
+            acc = MFMA32(afr[g % FRD], bfr[g % FRD], acc);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        STAMP(p1)
+        if (t + 2 < T) __syncthreads();  // publishes tile t + 2; behind it tile t's buffer may be refilled
+        STAMP(p2)
+        ph_comp += p1 - p0; ph_bar += p2 - p1;
+    }
+#undef RING_LD
+#undef RING_ST
+#ifdef AZ_PROBE
+    if (tid == 0 && bid < 8192) {  // k_gemm's words (per 32 k, as there); the staging has no phase of its own here
+        unsigned long long p_end = 0;
+        STAMP(p_end)
+        unsigned long long *o = az_probe_buf + (size_t)bid * 8;
+        o[0] = 0; o[1] = ph_comp; o[2] = 0; o[3] = ph_bar; o[4] = KT; o[5] = p_begin; o[6] = p_end;
+        o[7] = __builtin_amdgcn_s_memrealtime() - rt_begin;  // 100 MHz ticks
+    }
+#endif
+    // C/D layout of 32x32x2: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = bm0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int col = bn0 + wn0 + (lane & 31);
+        float v = acc[r];
+        if (RELU) v = v > 0.0f ? v : 0.0f;
+        if (row < M) C[(size_t)row * N + col] = v;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2075,6 +2216,7 @@ __global__ void k_retile_q(const float *__restrict__ W, float *__restrict__ dst,
 
 template <int BM, int BN>
 constexpr int gemm_lds_bytes() { return 4 * (2 * BM * (32 + 1) + 2 * 32 * BN); }
+constexpr int gemm_ring_lds_bytes() { return 4 * 3 * (64 * (16 + 1) + 16 * 64); }  // k_gemm_ring: three K tiles (BK = 16) of the 64 x 64 tile
 
 // policy + value heads (othello.py:379-382, base.py:355): logits = h2 * Wh + bh with
 // Wh = [fc_probs | fc_value | 0-pad] of width NH = 16*NT; then softmax over the first A columns
@@ -3626,6 +3768,29 @@ static int gemm_go(LaunchCtx &c, const Dense &a) {
     }
 }
 
+template <int KT>
+static int gemm_ring_launch(LaunchCtx &c, const Dense &a) {
+    constexpr int lds = gemm_ring_lds_bytes();
+    AZ_TRY((lds_attr<&k_gemm_ring<true, KT>, &k_gemm_ring<false, KT>>(lds)));
+    dim3 grid(a.N / 64, (a.M + 63) / 64);
+    if (a.relu) AZ_LAUNCH(c, (k_gemm_ring<true, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.dyn);
+    else AZ_LAUNCH(c, (k_gemm_ring<false, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.dyn);
+    return AZ_OK;
+}
+
+// the ring form of the 64 x 64 tile: the K values of gemm_unrolled_kt
+static int gemm_ring_go(LaunchCtx &c, const Dense &a) {
+    AZ_REQUIRE((long long)a.K * a.N < (1LL << 30), AZ_EINVAL, "k_gemm's ring form addresses the weights by 32-bit byte offsets: K=%d N=%d", a.K, a.N);
+    switch (a.K) {
+        case 1024: return gemm_ring_launch<32>(c, a);
+        case 512: return gemm_ring_launch<16>(c, a);
+        case 192: return gemm_ring_launch<6>(c, a);
+        case 128: return gemm_ring_launch<4>(c, a);
+        case 64: return gemm_ring_launch<2>(c, a);
+        default: az_set_error("k_gemm's ring form has no instantiation for K=%d", a.K); return AZ_EINVAL;
+    }
+}
+
 template <int TM, int TN>
 static int solo_t_launch(LaunchCtx &c, const Dense &a) {
     constexpr int BM = 64 * TM, BN = 64 * TN, lds = 4 * (2 * BM * 33 + 2 * 32 * BN);
@@ -3668,6 +3833,7 @@ static int launch_dense(LaunchCtx &c, const StagePlan &p, const Dense &a) {
         case K_GEMM_SOLO_T: return solo_t_launch<2, 2>(c, a);
         default: break;  // K_GEMM
     }
+    if (p.gemm_form == 1) return gemm_ring_go(c, a);
 #define TILE(tm, tn, wm, wn) if (p.bm == tm && p.bn == tn) return gemm_go<tm, tn, wm, wn>(c, a);
     TILE(128, 128, 64, 64) TILE(128, 64, 32, 64) TILE(64, 64, 32, 32) TILE(64, 128, 32, 64) TILE(128, 32, 32, 32)
 #undef TILE

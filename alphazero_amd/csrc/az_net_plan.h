@@ -28,6 +28,7 @@ struct NetTuning {
     int gemm_solo;            // AZ_GEMM_SOLO (-1: by size): 0 = never a one-wave-per-SIMD GEMM, 1 / 2 forces k_gemm_solo / k_gemm_solo_t
     int dense_frag_max;       // AZ_DENSE_FRAG_MAX (-1: 1024 rows, 2048 for K >= 1024): rows up to which k_dense_frag runs; 0 = never
     int gemm_tile;            // AZ_GEMM_TILE (0: by size): k_gemm's tile 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 64x128 (A/B)
+    int gemm_form;            // AZ_GEMM_FORM (-1: by regime, see plan_dense): 0 = k_gemm's double-buffer form everywhere, 1 = the ring form wherever it exists (A/B)
     int qd_small_max;         // AZ_QD_SMALL_MAX (512): rows up to which k_qdense_small serves a fixed-point layer; 0 = never
     int qg_cfg;               // AZ_QG_CFG (0: by size): k_qgemm's tile plan 1 .. 5, see plan_dense (A/B; every plan gives the same bits)
     int heads_small_max;      // AZ_HEADS_SMALL_MAX (-1: 128, 0 for OthelloNet): rows up to which k_heads_small runs (A/B)
@@ -50,6 +51,7 @@ inline const NetTuning &net_tuning() {
         if (v.trunk_blocks_per_cu < 0 && getenv("AZ_TRUNK_BLOCKS_PER_CU")) v.trunk_blocks_per_cu = 0;  // set to a negative number: as any value outside 1..8
         v.beside_trunk2_min = net_env("AZ_BESIDE_TRUNK2_MIN", 4096); v.beside_frag_max = net_env("AZ_BESIDE_FRAG_MAX", 1024); v.beside_tile = net_env("AZ_BESIDE_TILE", 0);
         v.gemm_solo = net_env("AZ_GEMM_SOLO", -1); v.dense_frag_max = net_env("AZ_DENSE_FRAG_MAX", -1); v.gemm_tile = net_env("AZ_GEMM_TILE", 0);
+        v.gemm_form = net_env("AZ_GEMM_FORM", -1);
         v.qd_small_max = net_env("AZ_QD_SMALL_MAX", 512); v.qg_cfg = net_env("AZ_QG_CFG", 0);
         v.heads_small_max = net_env("AZ_HEADS_SMALL_MAX", -1); v.heads_v1 = net_env("AZ_HEADS_V1", 0) != 0; v.heads_rh = net_env("AZ_HEADS_RH", 0);
         v.tail_v1 = net_env("AZ_TAIL_V1", 0) != 0; v.no_fused_tail = net_env("AZ_NO_FUSED_TAIL", 0) != 0; v.tail_r8_from = net_env("AZ_TAIL_R8_FROM", INT_MAX);
@@ -78,6 +80,7 @@ struct StagePlan {
     int quad_form;     // k_trunk_quad: 0 / 1 / 2
     int lds_blocks;    // k_trunk, k_trunk_quad: blocks per CU the LDS request is padded to (outside 1..8: the kernel's natural size)
     int bm, bn;        // k_gemm: the workgroup tile (0: N fits none)
+    int gemm_form;     // k_gemm: 0 = LDS double buffer, the chain stops at every K tile; 1 = LDS ring, the chain runs through (k_gemm_ring)
     int qg[4];         // k_qgemm: the tile plan <NWM, NWN, WM, WN>
     int nt, rh;        // k_heads, k_heads2: 16-column tiles; k_heads2: 16-row tiles per block
     int tail_r;        // k_tail_small: R (4 R rows per workgroup)
@@ -85,6 +88,10 @@ struct StagePlan {
 
 // layers k_dense_frag can run: K in whole 128-k groups of fragments (PF = 8 loads of 16 k), the 16 rows of K + 4 floats within the LDS
 constexpr bool frag_shape(int N, int K) { return N % 64 == 0 && K % 128 == 0 && K <= 2048; }
+// K / 32 of the layers k_gemm's tile loop is unrolled for: 512 / 1024 (Othello 8x8), 128 (Othello 6x6), 192 / 64 (Connect4); 0 = the runtime loop
+constexpr int gemm_unrolled_kt(int K) { return (K == 1024 || K == 512 || K == 192 || K == 128 || K == 64) ? K / 32 : 0; }
+// k_gemm's ring form exists for the 64 x 64 tile with an unrolled tile loop
+constexpr bool gemm_ring_shape(int bm, int bn, int K) { return bm == 64 && bn == 64 && gemm_unrolled_kt(K) >= 2; }
 // 8x8, 6x6 and 7x6 planes run the tuned kernels; every other plane between 5x5 and 8x8 -- Connect4Net on the board sizes the engine
 // plays -- runs k_trunk (one board per wave, direct form) at any batch size
 constexpr bool plane_tuned(int CH, int CW) { return (CH == 8 && CW == 8) || (CH == 6 && CW == 6) || (CH == 7 && CW == 6); }
@@ -176,7 +183,25 @@ inline StagePlan plan_dense(const NetDims &d, const NetTuning &t, int stage, int
     // phases then overlap the other block's MFMAs.  Beside another chain the 64 x 64 tile runs from one block per CU up (above).
     const long long mb128 = (B + 127) / 128, mb64 = (B + 63) / 64;
     const int tile = t.gemm_tile ? t.gemm_tile : (beside ? t.beside_tile : 0);
-    auto tiled = [&](int bm, int bn) { p.bm = bm; p.bn = bn; return is(K_GEMM); };
+    // The form.  A wave of the 64 x 64 tile holds one accumulator: 32 k are 16 dependent MFMAs, 1024 cycles, and the double-buffer form
+    // stops the chain behind each of them for the staged loads, the LDS stores, the barrier and the first fragment reads.  Its own
+    // stamps: fc2, one wave per SIMD, takes 1850 cycles per 32 k, 45 % of its tile loop outside the MFMA chain; fc1, two waves on most
+    // SIMDs, takes 2590 for the 2048 of the two chains, 21 % (tools/probe_gemm.py prints the share against ONE chain, 59 % for fc1: the
+    // partner's MFMAs counted as a stop).  With two blocks per CU a second wave of the launch fills the stop.  Beside another chain the
+    // tile runs from ONE block per CU up, where nothing does -- the other chain's kernels do not -- and there the
+    // ring form, whose chain runs through the boundary, is the pick: fc2 of the headline's 2048-row groups, 135.1 against 137.4 us per
+    // pair of forwards.  The rule is the measured shape and no more: OthelloNet on the 8x8 plane (the neighbour is k_trunk_quad<8,8,2>,
+    // whose 35 KB blocks the LDS figures were taken against), beside, at most one block per CU -- fc2 at 1985 .. 2048 rows.  Other nets
+    // and planes reach the ring through AZ_GEMM_FORM=1 only.  Measured and left on the double buffer: beside launches above one block
+    // per CU (fc1 at 480 blocks: 141 against 137.4 us per pair, with 25 KB of LDS as with 50), and lone launches (the ring is
+    // 0.5 .. 2.5 us faster on every lone 64 x 64 launch measured; not the headline's regime, not made the rule on two runs).
+    // Legs: profiles/r23_gemm_form.txt.
+    auto tiled = [&](int bm, int bn) {
+        p.bm = bm; p.bn = bn;
+        const bool measured = d.game == AZ_OTHELLO && d.CH == 8 && d.CW == 8 && beside && bm == 64 && bn == 64 && mb64 * (N / 64) <= 256;
+        p.gemm_form = gemm_ring_shape(bm, bn, K) && (t.gemm_form >= 0 ? t.gemm_form == 1 : measured) ? 1 : 0;
+        return is(K_GEMM);
+    };
     if (tile == 1 && N % 128 == 0) return tiled(128, 128);
     if (tile == 2 && N % 64 == 0) return tiled(128, 64);
     if (tile == 3 && N % 64 == 0) return tiled(64, 64);

@@ -44,7 +44,7 @@ def classify(name, game, grid=None):
     if "k_tail_small" in name or "k_tail_mfma" in name:
         return "k_tail"
     if "k_gemm" in name or "k_dense" in name:
-        kt = re.search(r"k_gemm<[^>]*,\s*(\d+)>", name)
+        kt = re.search(r"k_gemm(?:_ring)?<[^>]*,\s*(\d+)>", name)
         return "k_gemm_fc1" if kt and kt.group(1) == FC1_KT[game] else "k_gemm_fc2"
     if re.search(r"k_step<\s*true,\s*true\s*>", name) or "k_stepILb1ELb1" in name:
         return "k_step"
