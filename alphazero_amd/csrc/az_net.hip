@@ -50,10 +50,17 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define PLANE_STRIDE(x) (((x) + 1) | 1)
 
 #ifdef AZ_PROBE  // diagnostic build only (make PROBE=1): per-phase shader-clock stamps of wave 0 of every block
-__device__ unsigned long long az_probe_buf[8192 * 8];  // k_gemm: 8 words per block; k_trunk2: 8 words per (block, wave)
+__device__ unsigned long long az_probe_buf[8192 * 8];  // k_gemm: 8 words per block; k_trunk2: 8 words per (block, wave); k_trunk_quad: 24 words per (block, wave)
 #define STAMP(var) { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
+// k_trunk_quad's stamps, 24 words per (block, wave): the layer functions take the wave's stamp array behind their own arguments
+#define TS_PARAM , unsigned long long *ts = nullptr
+#define TS_ARG , ts
+#define TSTAMP(k) { if (ts) STAMP(ts[k]) }
 #else
 #define STAMP(var)
+#define TS_PARAM
+#define TS_ARG
+#define TSTAMP(k) {}
 #endif
 
 struct TrunkParams {
@@ -65,6 +72,8 @@ struct TrunkParams {
     const float *wu;             // conv2 in the Winograd F(2x2,3x3) form: U = G g' G^T as 16x16x4 B fragments
                                  // [2 passes][8 k-steps][4][64 lanes][4]: fragment e = 2 f8 + nt of frequency f = 8 p + f8
     const float *wu32;           // the same U as 32x32x2 B fragments [4][16 frequencies][64 lanes][4 k-steps] (conv2_wino32)
+    const float *wh[2];          // conv3, conv4 once more, one channel half after the other: [half nt][9 taps][2][64 lanes][4], the fragments
+                                 // 2 j + nt of wq at [nt][tap][j / 4][lane][j % 4] (k_trunk_quad's prefetching form: a wave reads its half alone)
 };
 
 #define LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
@@ -182,8 +191,13 @@ AZ_D void store_relu_lds(float *out, int lane, const f32x4 (&acc)[MT][2]) {
 // Y[1][c] = (R[1][c]-R[2][c])-R[3][c], out = relu(Y + bias): one IEEE operation per step, in this order.
 // The output overwrites the input planes (all reads are done before the first write).
 // ---------------------------------------------------------------------------------------------
-template <int CH, int CW, int PS, int RING, int NP = 2>
-AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bias, int lane) {
+// PF (NP = 4 only; k_trunk_quad's prefetching form): nothing of the wave's own waits at a pass boundary.  The U ring
+// runs through the 32 k-steps of the four passes -- its first RING - 1 k-steps arrive in `ubx`, requested by the caller --, pass i + 1's
+// first patch read goes out under pass i's last MFMAs, and the two output biases are requested ahead of the last pass.  Same operations
+// on the same operands: same bits.
+template <int CH, int CW, int PS, int RING, int NP = 2, bool PF = false>
+AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bias, int lane, float4 (*ubx)[2] = nullptr TS_PARAM) {
+    static_assert(!PF || NP == 4, "the prefetching form exists for the four-pass form");
     constexpr int TW = (CW + 1) / 2, NTL = ((CH + 1) / 2) * TW, P1 = CH * CW;
     static_assert(NTL <= 16 && PS > P1, "one 16-row tile of 2x2 output tiles per board; a zero slot behind every plane");
     static_assert(NP == 2 || NP == 4, "two passes of two frequency rows or four passes of one");
@@ -194,49 +208,81 @@ AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bi
     const float4 *ul = wu4 + lane;
     float cu[2][4][2], cw_[2][4][2];  // pass 0 -> pass 1: R[0][c] + R[1][c] and R[1][c] per (nt, r)
     float yo[2][4][2][2];             // Y[i][c] per (nt, r)
+    [[maybe_unused]] float bvo[2];    // PF: the output biases
     // NP = 4: one frequency ROW per pass -- 32 accumulator registers, two patch rows and two U float4 per k-step live instead of 64,
     // three and four -- for the kernels that are to share a SIMD with another chain's waves (k_trunk_quad forms 1 and 2).  Pass i reads
     // patch rows (0,2), (1,2), (2,1), (1,3) and forms T[i] = d_a -+ d_b, the row of B^T d the two-pass form takes in its half; V, the
     // chains and R[i][c] are the same operations, and the column sums are carried as Y[0] = (R0 + R1) + R2 in yo[..][0] and
     // R1, R1 - R2, Y[1] = (R1 - R2) - R3 in yo[..][1]: the two-pass form's additions in its order, so the same bits.
     if constexpr (NP == 4) {
+        constexpr int RA[4] = {0, 1, 2, 1}, RB[4] = {2, 2, 1, 3};
+        // the patch offsets of pass i_: formed from the lane number alone behind a pin, in the pass (PF: under the last MFMAs of the pass
+        // before), not ahead of conv1 for all four passes
+#define WINO_OFFSETS(i_, off_)                                                                                           \
+        {                                                                                                                \
+            int li = lane;                                                                                               \
+            asm volatile("" : "+v"(li));                                                                                 \
+            const int mi = li & 15, kqi = li >> 4, ti = mi < NTL ? mi : NTL - 1, tyi = ti / TW, txi = ti % TW;           \
+            _Pragma("unroll") for (int a = 0; a < 2; ++a)                                                                \
+                _Pragma("unroll") for (int b = 0; b < 4; ++b) {                                                          \
+                    const int iy = 2 * tyi - 1 + (a ? RB[i_] : RA[i_]), ix = 2 * txi - 1 + b;                            \
+                    off_[a * 4 + b] = kqi * PS + ((iy >= 0 && iy < CH && ix >= 0 && ix < CW) ? iy * CW + ix : P1);       \
+                }                                                                                                        \
+        }
+        // the U fragments of k-step g_ of the 32 (pass g_ / 8): frequency 4 i + c is fragment pair q = 2 (i & 1) + (c >> 1) of pass i >> 1
+        // in the two-pass U layout
+#define WINO_U(g_, q_) ul[(size_t)((((g_) / 8) >> 1) * 32 + 2 * (((g_) / 8) & 1) + ((g_) % 8) * 4 + (q_)) * 64]
+        [[maybe_unused]] int offn[8];
+        [[maybe_unused]] float dx[8];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            constexpr int RA[4] = {0, 1, 2, 1}, RB[4] = {2, 2, 1, 3};
-            // the pass's patch offsets are formed in the pass, from the lane number alone: not ahead of conv1 for all four passes
-            int off[8], li = lane;
-            asm volatile("" : "+v"(li));
-            const int mi = li & 15, kqi = li >> 4, ti = mi < NTL ? mi : NTL - 1, tyi = ti / TW, txi = ti % TW;
+            int off[8];
+            float d[8];
+            if constexpr (PF) {
+                if (i > 0) {
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int iy = 2 * tyi - 1 + (a ? RB[i] : RA[i]), ix = 2 * txi - 1 + b;
-                    off[a * 4 + b] = kqi * PS + ((iy >= 0 && iy < CH && ix >= 0 && ix < CW) ? iy * CW + ix : P1);
+                    for (int e = 0; e < 8; ++e) { off[e] = offn[e]; d[e] = dx[e]; }
                 }
+                if (i == 3) {  // the output biases: on their way through the last pass
+                    int lb = lane;
+                    asm volatile("" : "+v"(lb));
+                    bvo[0] = bias[lb & 15]; bvo[1] = bias[16 + (lb & 15)];
+                }
+            }
+            if (!PF || i == 0) WINO_OFFSETS(i, off)
             f32x4 acc[4][2];
 #pragma unroll
             for (int f = 0; f < 4; ++f) { acc[f][0] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f}; acc[f][1] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f}; }
-            // frequency 4 i + c is fragment pair q = 2 (i & 1) + (c >> 1) of pass i >> 1 in the two-pass U layout
-            const float4 *up = ul + (size_t)((i >> 1) * 32 + 2 * (i & 1)) * 64;
-            float4 ub[RING][2];
+            float4 ubl[RING][2];
+            float4 (*ub)[2] = PF ? ubx : ubl;  // PF: one ring through all 32 k-steps, slot g % RING
+            if constexpr (!PF) {
 #pragma unroll
-            for (int jj = 0; jj < RING - 1; ++jj)
+                for (int jj = 0; jj < RING - 1; ++jj)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) ub[jj][q] = up[(size_t)(jj * 4 + q) * 64];
-            float d[8];
+                    for (int q = 0; q < 2; ++q) ub[jj][q] = WINO_U(8 * i + jj, q);
+            }
+            if (!PF || i == 0) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) d[e] = act[off[e]];
+                for (int e = 0; e < 8; ++e) d[e] = act[off[e]];
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
+                const int g = 8 * i + j, slot = PF ? g % RING : j % RING;
                 float dn[8];
-                if (j + RING - 1 < 8) {
+                if (PF ? g + RING - 1 < 32 : j + RING - 1 < 8) {
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) ub[(j + RING - 1) % RING][q] = up[(size_t)((j + RING - 1) * 4 + q) * 64];
+                    for (int q = 0; q < 2; ++q) ub[PF ? (g + RING - 1) % RING : (j + RING - 1) % RING][q] = WINO_U(g + RING - 1, q);
                 }
                 if (j + 1 < 8) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) dn[e] = act[off[e] + 4 * (j + 1) * PS];
+                }
+                if constexpr (PF) {
+                    if (j == 7 && i < 3) {  // the next pass's first patch: read under this pass's last MFMAs
+                        WINO_OFFSETS(i + 1, offn)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) dx[e] = act[offn[e]];
+                    }
                 }
                 float T[4], V[4];
 #pragma unroll
@@ -245,11 +291,13 @@ AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bi
                 __builtin_amdgcn_sched_barrier(0);  // the loads above stay issued ahead of this k-step's MFMAs
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {
-                    const float4 u = ub[j % RING][f >> 1];
+                    const float4 u = ub[slot][f >> 1];
                     acc[f][0] = MFMA(V[f], (f & 1) ? u.z : u.x, acc[f][0]);
                     acc[f][1] = MFMA(V[f], (f & 1) ? u.w : u.y, acc[f][1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
+                if (j == 0) TSTAMP(4 + 2 * i)  // behind the issue of the pass's first k-step: its operands have arrived
+                if (j == 7) TSTAMP(5 + 2 * i)
                 if (j + 1 < 8) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) d[e] = dn[e];
@@ -283,6 +331,8 @@ AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bi
                     }
             __builtin_amdgcn_sched_barrier(0);
         }
+#undef WINO_OFFSETS
+#undef WINO_U
     }
 #pragma unroll
     for (int p = 0; p < (NP == 4 ? 0 : 2); ++p) {
@@ -366,7 +416,9 @@ AZ_D void conv2_wino(float *act, const float4 *wu4, const float *__restrict__ bi
     const int kqe = le >> 4, me = le & 15;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        const float bv = bias[nt * 16 + me];
+        float bv;
+        if constexpr (PF) bv = bvo[nt];
+        else bv = bias[nt * 16 + me];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int tt = 4 * kqe + r, y0 = 2 * (tt / TW), x0 = 2 * (tt % TW);  // C layout of 16x16x4: row 4 (lane >> 4) + r, column lane & 15
@@ -543,10 +595,12 @@ struct TrunkGeom {
 // this deal without the rotation; the rotation was chosen because it also halves a wave's weight-fragment registers: one channel half.)
 //   rows = nb * P_OUT (>= 1).  Rows past the last valid one repeat it (finite operands from a valid board) and are never stored.
 //   NA: size of the caller's accumulator array, NU <= NA tiles are computed.
+//   HALF (k_trunk_quad's prefetching form): wf is the per-half order TrunkParams::wh -- two 16-byte loads per tap
+//   instead of four, all of them used.
 // ---------------------------------------------------------------------------------------------
-template <int P_OUT, int W_OUT, int IN_W, int IN_PS, int BS, int NU, int NA>
+template <int P_OUT, int W_OUT, int IN_W, int IN_PS, int BS, int NU, int NA, bool HALF = false>
 AZ_D void conv_quad(const float *planes, const float *__restrict__ wf, const float *__restrict__ bias, int lane, int nt, int mt0, int rows,
-                    f32x4 (&acc)[NA]) {
+                    f32x4 (&acc)[NA] TS_PARAM, int ts0 = 0) {
     static_assert(NU >= 1 && NU <= NA, "accumulators for every tile of the wave");
     const int m_lane = lane & 15, kq = lane >> 4;
     int abase[NU];
@@ -566,7 +620,11 @@ AZ_D void conv_quad(const float *planes, const float *__restrict__ wf, const flo
         bfr[buf_][2 * q] = nt ? v[1] : v[0];                                               \
         bfr[buf_][2 * q + 1] = nt ? v[3] : v[2];                                           \
     }
-    QUAD_BLOAD(0, 0)
+    // HALF: the wave's half alone; k-step j of a tap is component j % 4 of its float4 j / 4
+    [[maybe_unused]] const float4 *wl4 = reinterpret_cast<const float4 *>(wf) + nt * (9 * 2 * 64) + lane;
+    [[maybe_unused]] float4 bfq[2][2];
+    if constexpr (HALF) { bfq[0][0] = wl4[0]; bfq[0][1] = wl4[64]; }
+    else { QUAD_BLOAD(0, 0) }
     const float bv = bias[16 * nt + m_lane];
 #pragma unroll
     for (int i = 0; i < NU; ++i) acc[i] = (f32x4){bv, bv, bv, bv};
@@ -579,7 +637,14 @@ AZ_D void conv_quad(const float *planes, const float *__restrict__ wf, const flo
 #pragma unroll
     for (int c = 0; c < 72; ++c) {
         const int tap = c / 8, j = c % 8;
-        if (j == 0 && tap < 8) { QUAD_BLOAD(tap + 1, (tap + 1) & 1) }
+        if constexpr (HALF) {
+            if (j == 0 && tap < 8) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) bfq[(tap + 1) & 1][q] = wl4[((tap + 1) * 2 + q) * 64];
+            }
+        } else {
+            if (j == 0 && tap < 8) { QUAD_BLOAD(tap + 1, (tap + 1) & 1) }
+        }
         float ac[NU];
 #pragma unroll
         for (int i = 0; i < NU; ++i) ac[i] = ar[c % A_RING][i];
@@ -588,26 +653,33 @@ AZ_D void conv_quad(const float *planes, const float *__restrict__ wf, const flo
             for (int i = 0; i < NU; ++i) ar[c % A_RING][i] = QUAD_LOAD(c + A_RING, i);
         }
         __builtin_amdgcn_sched_barrier(0);  // loads stay issued ahead of this step's MFMAs (see conv_mfma)
+        float bw;
+        if constexpr (HALF) {
+            const float4 w = bfq[tap & 1][j / 4];
+            bw = j % 4 == 0 ? w.x : j % 4 == 1 ? w.y : j % 4 == 2 ? w.z : w.w;
+        } else bw = bfr[tap & 1][j];
 #pragma unroll
-        for (int i = 0; i < NU; ++i) acc[i] = MFMA(ac[i], bfr[tap & 1][j], acc[i]);
+        for (int i = 0; i < NU; ++i) acc[i] = MFMA(ac[i], bw, acc[i]);
         __builtin_amdgcn_sched_barrier(0);
+        if (c == 0) TSTAMP(ts0)  // behind the issue of the layer's first k-step: its operands have arrived
+        if (c == 71) TSTAMP(ts0 + 1)
     }
 #undef QUAD_LOAD
 #undef QUAD_BLOAD
 }
 
 // one layer of the QUAD form on the wave's share of the NT = ceil(4 P_OUT / 16) row tiles: nu = the number of tiles computed
-template <int P_OUT, int W_OUT, int IN_W, int IN_PS, int BS, int NA>
+template <int P_OUT, int W_OUT, int IN_W, int IN_PS, int BS, int NA, bool HALF = false>
 AZ_D int conv_quad_deal(const float *planes, const float *__restrict__ wf, const float *__restrict__ bias, int lane, int nt, int par, int rows,
-                        f32x4 (&acc)[NA]) {
+                        f32x4 (&acc)[NA] TS_PARAM, int ts0 = 0) {
     constexpr int NT = (4 * P_OUT + 15) / 16, NH = (NT + 1) / 2, NL = NT / 2;
     static_assert(NA == NH, "the accumulators of the heavier share");
     if constexpr (NH == NL) {
-        conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NH, NA>(planes, wf, bias, lane, nt, par, rows, acc);
+        conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NH, NA, HALF>(planes, wf, bias, lane, nt, par, rows, acc TS_ARG, ts0);
         return NH;
     } else {
-        if (par == 0) { conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NH, NA>(planes, wf, bias, lane, nt, 0, rows, acc); return NH; }
-        if constexpr (NL > 0) conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NL, NA>(planes, wf, bias, lane, nt, 1, rows, acc);
+        if (par == 0) { conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NH, NA, HALF>(planes, wf, bias, lane, nt, 0, rows, acc TS_ARG, ts0); return NH; }
+        if constexpr (NL > 0) conv_quad<P_OUT, W_OUT, IN_W, IN_PS, BS, NL, NA, HALF>(planes, wf, bias, lane, nt, 1, rows, acc TS_ARG, ts0);
         return NL;
     }
 }
@@ -714,14 +786,47 @@ __global__ __launch_bounds__(256, 2) void k_trunk(const float *__restrict__ in, 
 // and still computes its share of the tiles, which read valid boards' planes alone.  A workgroup wholly beyond the row count leaves
 // before the first barrier.  Sharing the tiles of conv1 / the direct conv2 as well (6x6: 9 for 12) needs three more barriers and
 // measured slower.
-template <int CH, int CW, int FORM>
+// PF, the prefetching form (the four-pass forms): no wave waits for a weight or for its input behind a phase boundary
+// where the whole launch stands at the same place.  Requested before the wave knows the row count: the board's input (guarded by the
+// LAUNCH's B: rows between the count and B are allocated and may hold anything; a wave that turns out to have no board drops them),
+// conv1's weights and bias, and the first k-steps of conv2's U ring; in conv2 the ring runs through the pass boundaries (conv2_wino);
+// conv3 / conv4 read their weights from the per-half order tp.wh, half the bytes (conv_quad).  Every output element keeps its chain:
+// the same bits.  Requesting conv3 / conv4's first taps in front of the barrier the layer starts behind, and conv4's taps two ahead,
+// were measured and did not pay (profiles/r24_trunk_prefetch.txt).
+template <int CH, int CW, int FORM, bool PF = false>
 __global__ __launch_bounds__(256, FORM == 1 ? 4 : FORM == 2 ? 3 : 2) void k_trunk_quad(const float *__restrict__ in, int B, const int *__restrict__ dyn_count, TrunkParams tp, float *__restrict__ feat) {
     using G = TrunkGeom<CH, CW>;
+    static_assert(!PF || FORM != 0, "the prefetching form exists for the four-pass forms");
+    constexpr int RING = FORM == 1 ? 2 : 3, NX = (G::P1 + 63) / 64;
+#ifdef AZ_PROBE
+    unsigned long long tsv[24] = {}, *ts = tsv;
+#endif
+    TSTAMP(0)
+    [[maybe_unused]] float xin[NX], w1r[3][2], b1r[2];
+    [[maybe_unused]] float4 ubx[RING][2];
+    if constexpr (PF) {
+        const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+        const int br = b < B ? b : B - 1;  // a wave beyond the launch reads the launch's last row (B >= 1), and drops it
+#pragma unroll
+        for (int k = 0; k < NX; ++k) {
+            const int p = lane + 64 * k;
+            xin[k] = in[(size_t)br * G::P1 + (p < G::P1 ? p : G::P1 - 1)];
+        }
+#pragma unroll
+        for (int s = 0; s < 3; ++s) { w1r[s][0] = tp.w1f[(s * 2 + 0) * 64 + lane]; w1r[s][1] = tp.w1f[(s * 2 + 1) * 64 + lane]; }
+        b1r[0] = tp.b1[lane & 15]; b1r[1] = tp.b1[16 + (lane & 15)];
+#pragma unroll
+        for (int jj = 0; jj < RING - 1; ++jj)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) ubx[jj][q] = reinterpret_cast<const float4 *>(tp.wu)[(size_t)(jj * 4 + q) * 64 + lane];
+        __builtin_amdgcn_sched_barrier(0);
+    }
     if (dyn_count) { int c = *dyn_count; B = c < B ? c : B; }  // rows actually filled this step
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
     if ((int)blockIdx.x * 4 >= B) return;  // the whole workgroup (B and blockIdx.x are uniform): no barrier is left behind
+    TSTAMP(1)
     const bool has = b < B;  // a wave without a board takes part in the shared layers and in every barrier
     const int nb = B - (int)blockIdx.x * 4 < 4 ? B - (int)blockIdx.x * 4 : 4;  // boards of this workgroup
     const int nt = wave >> 1, par = (wave & 1) ^ (__builtin_popcount(blockIdx.x) & 1);  // the wave's share of a shared layer (conv_quad)
@@ -732,19 +837,32 @@ __global__ __launch_bounds__(256, FORM == 1 ? 4 : FORM == 2 ? 3 : 2) void k_trun
         for (int i = lane; i < G::INP; i += 64) inp[i] = 0.0f;
         if (lane < NCH) act[lane * G::PS + G::P1] = 0.0f;  // every plane's zero slot: where the Winograd patches read outside the plane
         LDS_FENCE();
-        for (int p = lane; p < G::P1; p += 64) inp[(p / CW + 1) * G::PW + (p % CW) + 1] = in[(size_t)b * G::P1 + p];
+        if constexpr (PF) {
+#pragma unroll
+            for (int k = 0; k < NX; ++k) {
+                const int p = lane + 64 * k;
+                if (p < G::P1) inp[(p / CW + 1) * G::PW + (p % CW) + 1] = xin[k];
+            }
+        } else {
+            for (int p = lane; p < G::P1; p += 64) inp[(p / CW + 1) * G::PW + (p % CW) + 1] = in[(size_t)b * G::P1 + p];
+        }
         LDS_FENCE();
     }
+    TSTAMP(2)
     if (has) {  // conv1 1->32, pad 1 (othello.py:370) as a K = 12 MFMA product: taps 0..8, taps 9..11 carry zero weights
         f32x4 acc[G::MT2][2];
         const int m_lane = lane & 15, kq = lane >> 4;
-        const float bv0 = tp.b1[m_lane], bv1 = tp.b1[16 + m_lane];
+        float bv0, bv1;
+        if constexpr (PF) { bv0 = b1r[0]; bv1 = b1r[1]; }
+        else { bv0 = tp.b1[m_lane]; bv1 = tp.b1[16 + m_lane]; }
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
             int tap = 4 * s + kq;
             tap = tap < 9 ? tap : 8;  // finite operand for the zero-weight columns
             const int toff = (tap / 3) * G::PW + tap % 3;
-            const float b0 = tp.w1f[(s * 2 + 0) * 64 + lane], b1 = tp.w1f[(s * 2 + 1) * 64 + lane];
+            float b0, b1;
+            if constexpr (PF) { b0 = w1r[s][0]; b1 = w1r[s][1]; }
+            else { b0 = tp.w1f[(s * 2 + 0) * 64 + lane]; b1 = tp.w1f[(s * 2 + 1) * 64 + lane]; }
 #pragma unroll
             for (int mt = 0; mt < G::MT2; ++mt) {
                 int p = 16 * mt + m_lane;
@@ -758,23 +876,41 @@ __global__ __launch_bounds__(256, FORM == 1 ? 4 : FORM == 2 ? 3 : 2) void k_trun
         store_relu_lds<G::P1, G::PS, G::MT2>(act, lane, acc);
         LDS_FENCE();
     }
+    TSTAMP(3)
     if (has) {  // conv2 32->32, pad 1 (othello.py:371), Winograd form
-        conv2_wino<CH, CW, G::PS, FORM == 1 ? 2 : 3, FORM ? 4 : 2>(act, reinterpret_cast<const float4 *>(tp.wu), tp.cb[0], lane);
+        conv2_wino<CH, CW, G::PS, RING, FORM ? 4 : 2, PF>(act, reinterpret_cast<const float4 *>(tp.wu), tp.cb[0], lane, PF ? ubx : nullptr TS_ARG);
         LDS_FENCE();
     }
+    TSTAMP(12)
     __syncthreads();  // conv2 of every board is in LDS
+    TSTAMP(13)
     {  // conv3 32->32, valid (othello.py:372)
         f32x4 acc[((4 * G::P3 + 15) / 16 + 1) / 2];
-        const int nu = conv_quad_deal<G::P3, G::W3, CW, G::PS, G::WAVE_FLOATS>(act0, tp.wq[1], tp.cb[1], lane, nt, par, nb * G::P3, acc);
+        const int nu = conv_quad_deal<G::P3, G::W3, CW, G::PS, G::WAVE_FLOATS, ((4 * G::P3 + 15) / 16 + 1) / 2, PF>(
+            act0, PF ? tp.wh[0] : tp.wq[1], tp.cb[1], lane, nt, par, nb * G::P3, acc TS_ARG, 14);
+        TSTAMP(16)
         __syncthreads();  // every wave has finished reading the conv2 planes
+        TSTAMP(17)
         store_quad_relu<G::P3, G::PS, G::WAVE_FLOATS>(act0, lane, nt, par, nu, nb * G::P3, acc);
     }
+    TSTAMP(18)
     __syncthreads();  // conv3 of every board is in LDS
+    TSTAMP(19)
     {  // conv4 32->32, valid (othello.py:373) -> flattened NCHW features (othello.py:374) of boards 4 blockIdx.x .. + nb - 1
         f32x4 acc[((4 * G::P4 + 15) / 16 + 1) / 2];
-        const int nu = conv_quad_deal<G::P4, G::W4, G::W3, G::PS, G::WAVE_FLOATS>(act0, tp.wq[2], tp.cb[2], lane, nt, par, nb * G::P4, acc);
+        const int nu = conv_quad_deal<G::P4, G::W4, G::W3, G::PS, G::WAVE_FLOATS, ((4 * G::P4 + 15) / 16 + 1) / 2, PF>(
+            act0, PF ? tp.wh[1] : tp.wq[2], tp.cb[2], lane, nt, par, nb * G::P4, acc TS_ARG, 20);
         store_quad_relu<G::P4, G::P4, NCH * G::P4>(feat + (size_t)blockIdx.x * 4 * (NCH * G::P4), lane, nt, par, nu, nb * G::P4, acc);
     }
+    TSTAMP(22)
+#ifdef AZ_PROBE
+    if (lane == 0 && blockIdx.x < 512) {  // az_probe_buf: 24 words per (block, wave); word 23 = 1 + the wave holds a board
+        unsigned long long *o = az_probe_buf + ((size_t)blockIdx.x * 4 + wave) * 24;
+        tsv[23] = has ? 2 : 1;
+#pragma unroll
+        for (int k = 0; k < 24; ++k) o[k] = tsv[k];
+    }
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3174,6 +3310,7 @@ extern "C" int az_net_create(int game, int H, int W, int max_batch, az_net **out
         for (int l = 0; l < 3; ++l) { NA(n->tp.cb[l], NCH) }
         NA(n->tp.w1p, 5 * 64)
         for (int l = 0; l < 3; ++l) { NA(n->tp.wp[l], 9 * 16 * 64) NA(n->tp.wq[l], 9 * 16 * 64) }
+        for (int l = 0; l < 2; ++l) { NA(n->tp.wh[l], 2 * 9 * 2 * 64 * 4) }
         NA(n->tp.wu, 2 * 8 * 4 * 64 * 4) NA(n->tp.wu32, 4 * 16 * 64 * 4)
         NA(n->fc1w, (size_t)n->FIN * n->F1) NA(n->fc1b, n->F1) NA(n->fc2w, (size_t)n->F1 * n->F2) NA(n->fc2b, n->F2)
         NA(n->hw, (size_t)n->F2 * n->NH) NA(n->hb, n->NH) NA(n->hwq, (size_t)n->F2 * n->NH)
@@ -3373,6 +3510,18 @@ extern "C" int az_net_commit(az_net *n, void *stream) {
                             fp[((t * 4 + i / 4) * 64 + lane) * 4 + i % 4] = (float)((double)(*w)[(oc * NCH + ic) * 9 + t] * s[oc]);
                         }
             AZ_TRY(upload((float *)n->tp.wq[l - 1], fp, st));
+            if (l >= 2) {
+                // conv3 / conv4 once more, one channel half after the other (k_trunk_quad's prefetching form):
+                // [nt][tap][j / 4][lane][j % 4] = W'[oc = nt*16 + (lane&15)][ic = 4 j + (lane>>4)][tap]
+                for (int nt = 0; nt < 2; ++nt)
+                    for (int t = 0; t < 9; ++t)
+                        for (int j = 0; j < 8; ++j)
+                            for (int lane = 0; lane < 64; ++lane) {
+                                int oc = nt * 16 + (lane & 15), ic = 4 * j + (lane >> 4);
+                                fp[(((nt * 9 + t) * 2 + j / 4) * 64 + lane) * 4 + j % 4] = (float)((double)(*w)[(oc * NCH + ic) * 9 + t] * s[oc]);
+                            }
+                AZ_TRY(upload((float *)n->tp.wh[l - 2], fp, st));
+            }
             if (l == 1) {
                 // conv2 in the Winograd F(2x2,3x3) form: U[f = 4 i + jj][ic][oc] = (G g' G^T)[i][jj], g' = w * s, all in float64, rounded
                 // once; stored as 16x16x4 B fragments [pass p][k-step j][e / 4][lane][e % 4], e = 2 f8 + nt, f = 8 p + f8:
@@ -3466,7 +3615,7 @@ extern "C" int az_net_commit(az_net *n, void *stream) {
 // trainer.py:383-387): one thread per destination element, float64 arithmetic in the host code's operation order
 // (no contraction), so both paths produce identical bits.
 // ---------------------------------------------------------------------------------------------
-enum { FOLD_BIAS = 0, FOLD_W1F, FOLD_W1P, FOLD_WP, FOLD_WQ, FOLD_WINO, FOLD_WINO32, FOLD_DENSE_T, FOLD_HEADS_W, FOLD_HEADS_WQ, FOLD_HEADS_B };
+enum { FOLD_BIAS = 0, FOLD_W1F, FOLD_W1P, FOLD_WP, FOLD_WQ, FOLD_WH, FOLD_WINO, FOLD_WINO32, FOLD_DENSE_T, FOLD_HEADS_W, FOLD_HEADS_WQ, FOLD_HEADS_B };
 struct FoldJob {
     int mode, n_dst, K, N, A;
     const float *w, *b, *g, *beta, *mean, *var;  // w: the layer's weight (heads: fc_probs.weight), b: bias (heads: fc_value.*)
@@ -3501,6 +3650,12 @@ __global__ void k_fold(FoldJob j) {
         case FOLD_WQ: {  // fragment f = 2 j8 + nt at [tap][f / 4][lane][f % 4] = W'[oc = nt*16 + (lane&15)][ic = 4 j8 + (lane>>4)][tap]
             const int r = i % 4, lane = (i / 4) % 64, q = (i / 256) % 4, t = i / 1024;
             const int f = 4 * q + r, j8 = f / 2, nt = f % 2, oc = nt * 16 + (lane & 15), ic = 4 * j8 + (lane >> 4);
+            out = (float)((double)j.w[(oc * NCH + ic) * 9 + t] * fold_scale(j, oc));
+            break;
+        }
+        case FOLD_WH: {  // the same fragments, one channel half after the other: [nt][tap][j8 / 4][lane][j8 % 4]
+            const int r = i % 4, lane = (i / 4) % 64, q = (i / 256) % 2, t = (i / 512) % 9, nt = i / 4608;
+            const int j8 = 4 * q + r, oc = nt * 16 + (lane & 15), ic = 4 * j8 + (lane >> 4);
             out = (float)((double)j.w[(oc * NCH + ic) * 9 + t] * fold_scale(j, oc));
             break;
         }
@@ -3621,6 +3776,7 @@ extern "C" int az_net_commit_device(az_net *n, void *stream) {
             AZ_TRY(fold_launch(n, FOLD_BIAS, (float *)n->tp.cb[l - 1], NCH, "", 0, cn + ".bias", NCH, bnn, NCH, 0, 0, 0, st));
             AZ_TRY(fold_launch(n, FOLD_WP, (float *)n->tp.wp[l - 1], 9 * 16 * 64, cn + ".weight", wn, "", 0, bnn, NCH, 0, 0, 0, st));
             AZ_TRY(fold_launch(n, FOLD_WQ, (float *)n->tp.wq[l - 1], 9 * 16 * 64, cn + ".weight", wn, "", 0, bnn, NCH, 0, 0, 0, st));
+            if (l >= 2) AZ_TRY(fold_launch(n, FOLD_WH, (float *)n->tp.wh[l - 2], 2 * 9 * 2 * 64 * 4, cn + ".weight", wn, "", 0, bnn, NCH, 0, 0, 0, st));
             if (l == 1) AZ_TRY(fold_launch(n, FOLD_WINO, (float *)n->tp.wu, 2 * 8 * 4 * 64 * 4, cn + ".weight", wn, "", 0, bnn, NCH, 0, 0, 0, st));
             if (l == 1) AZ_TRY(fold_launch(n, FOLD_WINO32, (float *)n->tp.wu32, 4 * 16 * 64 * 4, cn + ".weight", wn, "", 0, bnn, NCH, 0, 0, 0, st));
         }
@@ -3714,6 +3870,13 @@ static int trunk_go(az_net *n, LaunchCtx &c, const StagePlan &p, const float *in
     const int b = p.lds_blocks, lds = (b >= 1 && b <= 8 && 160 * 1024 / b > G::LDS_BYTES) ? (160 * 1024 / b) & ~15 : G::LDS_BYTES;
     if constexpr (WINO && plane_wino(CH, CW)) {
 #define QUAD(form) if (p.kernel == K_TRUNK_QUAD && p.quad_form == form) {                                                            \
+        if constexpr (quad_prefetch_shape(CH, CW, form)) {  /* the plan asks for the prefetching form only where it is built */      \
+            if (p.quad_prefetch) {                                                                                                   \
+                AZ_TRY((lds_attr<&k_trunk_quad<CH, CW, form, true>>(lds)));                                                          \
+                AZ_LAUNCH(c, (k_trunk_quad<CH, CW, form, true>), dim3((B + 3) / 4), dim3(256), lds, in, B, dyn, n->tp, c.feat);      \
+                return AZ_OK;                                                                                                        \
+            }                                                                                                                        \
+        }                                                                                                                            \
         AZ_TRY((lds_attr<&k_trunk_quad<CH, CW, form>>(lds)));                                                                        \
         AZ_LAUNCH(c, (k_trunk_quad<CH, CW, form>), dim3((B + 3) / 4), dim3(256), lds, in, B, dyn, n->tp, c.feat);                    \
         return AZ_OK; }
@@ -4104,6 +4267,14 @@ extern "C" int az_net_stage_kernel(const az_net *n, int stage, int B, char *buf,
     AZ_REQUIRE(n && buf && cap > 0 && stage >= 0 && stage <= 3 && B > 0, AZ_EINVAL, "bad arguments");
     snprintf(buf, (size_t)cap, "%s", plan_family_name(plan_stage(net_dims(n), net_tuning(), stage, B, 0)));
     return AZ_OK;
+}
+
+// 1 where the trunk of a launch of B boards (beside: az_net_forward_lane's flag) runs k_trunk_quad's prefetching form, else 0: the plan's
+// quad_prefetch, for the tools that print which form they timed
+extern "C" int az_net_trunk_prefetch(const az_net *n, int B, int beside) {
+    if (!n || B <= 0 || n->game == AZ_TICTACTOE) return 0;
+    const StagePlan p = plan_stage(net_dims(n), net_tuning(), 0, B, beside);
+    return p.kernel == K_TRUNK_QUAD && p.quad_prefetch ? 1 : 0;
 }
 
 #ifdef AZ_PROBE

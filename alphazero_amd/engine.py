@@ -200,6 +200,10 @@ class HipNet:
         check(lib().az_net_stage_kernel(self.h, stage, B, buf, 64))
         return buf.value.decode()
 
+    def trunk_prefetch(self, B, beside):
+        """True where the trunk of a launch of B boards (beside: az_net_forward_lane's flag) runs k_trunk_quad's prefetching form"""
+        return bool(lib().az_net_trunk_prefetch(self.h, B, int(beside)))
+
     def profile(self, enable=True):
         """bracket every stage launch of the following forwards with HIP events (az_net_profile)"""
         check(lib().az_net_profile(self.h, 1 if enable else 0))

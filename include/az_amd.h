@@ -135,6 +135,9 @@ int64_t az_net_flops_per_board(const az_net *net);
 int az_net_time_stage(az_net *net, int stage, int B, int iters, void *stream, float *ms_per_launch);
 /* name of the kernel family of the plan for stage (0..3) of a lone launch of B boards, as rocprofv3 lists it (template arguments abbreviated) */
 int az_net_stage_kernel(const az_net *net, int stage, int B, char *buf, int cap);
+/* 1 where the trunk of a launch of B boards (beside as in az_net_forward_lane) runs the prefetching form of k_trunk_quad, else 0
+ * (AZ_TRUNK_QUAD_PREFETCH: unset = by regime, 0 = never, 1 = wherever the form is built); the forms give the same bits */
+int az_net_trunk_prefetch(const az_net *net, int B, int beside);
 /* Live measurement (the idiom of timers.py:53-76 applied per kernel): while enabled, every forward brackets its stage
  * launches with a start and a stop event each (hipExtLaunchKernelGGL).  ms_total[8] / launches[8], one slot per kernel family so that a slot's mean is the
  * figure rocprofv3 lists for that kernel: k_trunk2, fc1 and fc2 on the tiled GEMMs (k_gemm / k_gemm_solo; Connect4Net's fused tail
