@@ -699,6 +699,28 @@ AZ_D void store_quad_relu(float *out, int lane, int nt, int par, int nu, int row
         }
 }
 
+// store_quad_relu for a layer whose P_OUT is a multiple of 4 (k_trunk_quad's VST form): an accumulator's four values
+// are rows r .. r + 3 with r % 4 == 0, four consecutive positions of ONE board's plane, and rows = nb * P_OUT is a multiple of 4 too, so
+// the bound holds for all four or for none.  One predicate and one 16-byte store where the strides keep r's alignment (conv4's
+// features); otherwise four stores under the one predicate, which the compiler pairs (conv3's planes: PS is odd, 4-byte alignment).
+template <int P_OUT, int OUT_CS, int OUT_BS, int NA>
+AZ_D void store_quad_relu4(float *out, int lane, int nt, int par, int nu, int rows, const f32x4 (&acc)[NA]) {
+    static_assert(P_OUT % 4 == 0, "an accumulator's four rows lie in one plane");
+#pragma unroll
+    for (int i = 0; i < NA; ++i)
+        if (i < nu) {
+            const int r = 16 * (par + 2 * i) + (lane >> 4) * 4;
+            if (r < rows) {
+                float *o = out + (r / P_OUT) * OUT_BS + (nt * 16 + (lane & 15)) * OUT_CS + r % P_OUT;
+                float4 v;
+                v.x = acc[i][0] > 0.0f ? acc[i][0] : 0.0f; v.y = acc[i][1] > 0.0f ? acc[i][1] : 0.0f;
+                v.z = acc[i][2] > 0.0f ? acc[i][2] : 0.0f; v.w = acc[i][3] > 0.0f ? acc[i][3] : 0.0f;
+                if constexpr (OUT_CS % 4 == 0 && OUT_BS % 4 == 0) *reinterpret_cast<float4 *>(o) = v;  // the caller's base is 16-byte aligned
+                else { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+            }
+        }
+}
+
 // One wavefront per board; activations never leave the wave's private LDS region and every layer writes
 // its output IN PLACE over its input (the outputs wait in the MFMA accumulators until the layer's last
 // LDS read has been consumed):
@@ -793,10 +815,15 @@ __global__ __launch_bounds__(256, 2) void k_trunk(const float *__restrict__ in, 
 // conv3 / conv4 read their weights from the per-half order tp.wh, half the bytes (conv_quad).  Every output element keeps its chain:
 // the same bits.  Requesting conv3 / conv4's first taps in front of the barrier the layer starts behind, and conv4's taps two ahead,
 // were measured and did not pay (profiles/r24_trunk_prefetch.txt).
-template <int CH, int CW, int FORM, bool PF = false>
+// VST, the prefetching form with vector stores (StagePlan::quad_stores), same bits: P3 and P4 are multiples of 4, so
+// an accumulator's four values are four consecutive positions of one board's plane and the row bound holds for all of them or for none.
+// conv3's planes are written under one predicate per accumulator, as paired LDS writes (the planes' odd stride leaves 4-byte
+// alignment); conv4's features leave as one 16-byte store per accumulator, two per wave where there were eight (store_quad_relu4).
+template <int CH, int CW, int FORM, bool PF = false, bool VST = false>
 __global__ __launch_bounds__(256, FORM == 1 ? 4 : FORM == 2 ? 3 : 2) void k_trunk_quad(const float *__restrict__ in, int B, const int *__restrict__ dyn_count, TrunkParams tp, float *__restrict__ feat) {
     using G = TrunkGeom<CH, CW>;
     static_assert(!PF || FORM != 0, "the prefetching form exists for the four-pass forms");
+    static_assert(PF || !VST, "the vector stores are a form of the prefetching form");
     constexpr int RING = FORM == 1 ? 2 : 3, NX = (G::P1 + 63) / 64;
 #ifdef AZ_PROBE
     unsigned long long tsv[24] = {}, *ts = tsv;
@@ -891,7 +918,8 @@ __global__ __launch_bounds__(256, FORM == 1 ? 4 : FORM == 2 ? 3 : 2) void k_trun
         TSTAMP(16)
         __syncthreads();  // every wave has finished reading the conv2 planes
         TSTAMP(17)
-        store_quad_relu<G::P3, G::PS, G::WAVE_FLOATS>(act0, lane, nt, par, nu, nb * G::P3, acc);
+        if constexpr (VST) store_quad_relu4<G::P3, G::PS, G::WAVE_FLOATS>(act0, lane, nt, par, nu, nb * G::P3, acc);
+        else store_quad_relu<G::P3, G::PS, G::WAVE_FLOATS>(act0, lane, nt, par, nu, nb * G::P3, acc);
     }
     TSTAMP(18)
     __syncthreads();  // conv3 of every board is in LDS
@@ -900,7 +928,8 @@ __global__ __launch_bounds__(256, FORM == 1 ? 4 : FORM == 2 ? 3 : 2) void k_trun
         f32x4 acc[((4 * G::P4 + 15) / 16 + 1) / 2];
         const int nu = conv_quad_deal<G::P4, G::W4, G::W3, G::PS, G::WAVE_FLOATS, ((4 * G::P4 + 15) / 16 + 1) / 2, PF>(
             act0, PF ? tp.wh[1] : tp.wq[2], tp.cb[2], lane, nt, par, nb * G::P4, acc TS_ARG, 20);
-        store_quad_relu<G::P4, G::P4, NCH * G::P4>(feat + (size_t)blockIdx.x * 4 * (NCH * G::P4), lane, nt, par, nu, nb * G::P4, acc);
+        if constexpr (VST) store_quad_relu4<G::P4, G::P4, NCH * G::P4>(feat + (size_t)blockIdx.x * 4 * (NCH * G::P4), lane, nt, par, nu, nb * G::P4, acc);
+        else store_quad_relu<G::P4, G::P4, NCH * G::P4>(feat + (size_t)blockIdx.x * 4 * (NCH * G::P4), lane, nt, par, nu, nb * G::P4, acc);
     }
     TSTAMP(22)
 #ifdef AZ_PROBE
@@ -3871,6 +3900,11 @@ static int trunk_go(az_net *n, LaunchCtx &c, const StagePlan &p, const float *in
     if constexpr (WINO && plane_wino(CH, CW)) {
 #define QUAD(form) if (p.kernel == K_TRUNK_QUAD && p.quad_form == form) {                                                            \
         if constexpr (quad_prefetch_shape(CH, CW, form)) {  /* the plan asks for the prefetching form only where it is built */      \
+            if (p.quad_prefetch && p.quad_stores) {                                                                                  \
+                AZ_TRY((lds_attr<&k_trunk_quad<CH, CW, form, true, true>>(lds)));                                                    \
+                AZ_LAUNCH(c, (k_trunk_quad<CH, CW, form, true, true>), dim3((B + 3) / 4), dim3(256), lds, in, B, dyn, n->tp, c.feat); \
+                return AZ_OK;                                                                                                        \
+            }                                                                                                                        \
             if (p.quad_prefetch) {                                                                                                   \
                 AZ_TRY((lds_attr<&k_trunk_quad<CH, CW, form, true>>(lds)));                                                          \
                 AZ_LAUNCH(c, (k_trunk_quad<CH, CW, form, true>), dim3((B + 3) / 4), dim3(256), lds, in, B, dyn, n->tp, c.feat);      \
@@ -4275,6 +4309,45 @@ extern "C" int az_net_trunk_prefetch(const az_net *n, int B, int beside) {
     if (!n || B <= 0 || n->game == AZ_TICTACTOE) return 0;
     const StagePlan p = plan_stage(net_dims(n), net_tuning(), 0, B, beside);
     return p.kernel == K_TRUNK_QUAD && p.quad_prefetch ? 1 : 0;
+}
+
+// 1 where the trunk of a launch of B boards runs k_trunk_quad's prefetching form with vector stores, else 0: the plan's quad_stores
+extern "C" int az_net_trunk_stores(const az_net *n, int B, int beside) {
+    if (!n || B <= 0 || n->game == AZ_TICTACTOE) return 0;
+    const StagePlan p = plan_stage(net_dims(n), net_tuning(), 0, B, beside);
+    return p.kernel == K_TRUNK_QUAD && p.quad_stores ? 1 : 0;
+}
+
+// The plan of stage 0..3 of a launch of B boards as text: the kernel the launch runs (k_trunk_quad by its own name, not its family's)
+// and the plan's fields for it -- what the tools print beside a time, so that a line says which form it timed
+extern "C" int az_net_stage_plan(const az_net *n, int stage, int B, int beside, char *buf, int cap) {
+    AZ_REQUIRE(n && buf && cap > 0 && stage >= 0 && stage <= 3 && B > 0, AZ_EINVAL, "bad arguments");
+    const StagePlan p = plan_stage(net_dims(n), net_tuning(), stage, B, beside);
+    const char *k = net_kernel_name(p.kernel);
+    switch (p.kernel) {
+        case K_TRUNK: snprintf(buf, (size_t)cap, "%s %s lds_blocks=%d", k, p.wino ? "wino" : "direct", p.lds_blocks); break;
+        case K_TRUNK_QUAD:
+            snprintf(buf, (size_t)cap, "%s form=%d lds_blocks=%d prefetch=%d stores=%d", k, p.quad_form, p.lds_blocks, p.quad_prefetch, p.quad_stores);
+            break;
+        case K_TRUNK_Q: case K_TRUNK2: snprintf(buf, (size_t)cap, "%s %s waves=%d", k, p.wino ? "wino" : "direct", p.waves); break;
+        case K_GEMM: snprintf(buf, (size_t)cap, "%s %dx%d form=%d", k, p.bm, p.bn, p.gemm_form); break;
+        default: snprintf(buf, (size_t)cap, "%s", k);
+    }
+    return AZ_OK;
+}
+
+// ONE stage of az_net_forward_lane: the launch the forward would make for that stage, on the lane's activation rows as they stand
+// (stage 1 reads the lane's conv features, 2 its fc1 rows, 3 its fc2 rows).  For tools that time a stage beside another one.
+extern "C" int az_net_stage_lane(az_net *n, int lane, int beside, int stage, const float *d_input, const int32_t *d_count, int max_B,
+                                 float *d_probs, float *d_value, void *stream) {
+    AZ_REQUIRE(n && d_input && d_count && d_probs && d_value, AZ_EINVAL, "null argument");
+    AZ_REQUIRE(stage >= 0 && stage <= 3 && n->game != AZ_TICTACTOE, AZ_EINVAL, "stage %d outside 0..3 of a conv net", stage);
+    AZ_REQUIRE(lane >= 0 && lane <= (int)n->lanes.size(), AZ_EINVAL, "lane %d of %d (az_net_set_lanes)", lane, (int)n->lanes.size() + 1);
+    AZ_REQUIRE(n->committed, AZ_ESTATE, "az_net_commit has not been called since the last az_net_set_tensor");
+    AZ_REQUIRE(max_B > 0 && max_B <= n->max_batch && (lane == 0 || max_B <= n->lane_rows), AZ_EINVAL, "batch %d beyond the rows of lane %d", max_B, lane);
+    const az_net::Acts rows = lane > 0 ? n->lanes[lane - 1] : az_net::Acts{n->feat, n->h1, n->h2};
+    LaunchCtx c = {(hipStream_t)stream, beside, rows.feat, rows.h1, rows.h2};
+    return run_stage(n, c, stage, d_input, max_B, d_count, d_probs, d_value);
 }
 
 #ifdef AZ_PROBE

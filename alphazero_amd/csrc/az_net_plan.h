@@ -20,6 +20,7 @@ struct NetTuning {
     int trunk_quad;           // AZ_TRUNK_QUAD (-1: by plane and regime): 1 / 0 forces k_trunk_quad / k_trunk on the Winograd 8x8 and 7x6 planes (A/B)
     int trunk_quad_form;      // AZ_TRUNK_QUAD_FORM (-1: 7x6 form 1, 8x8 form 2): 0 / 1 / 2 forces one k_trunk_quad form (A/B)
     int trunk_quad_prefetch;  // AZ_TRUNK_QUAD_PREFETCH (-1: by regime, see plan_trunk): 0 = k_trunk_quad as it was everywhere, 1 = its prefetching form wherever it is built (A/B)
+    int trunk_quad_stores;    // AZ_TRUNK_QUAD_STORES (-1: with the prefetching form by the same regime, see plan_trunk): 0 = the prefetching form's scalar stores everywhere, 1 = its vector stores wherever the prefetching form runs (A/B)
     int trunk_q_max;          // AZ_TRUNK_Q_MAX (512): boards up to which the trunk runs several waves per board (k_trunk_q); 0 = never
     int trunk_q_waves;        // AZ_TRUNK_Q_WAVES (0: by size): 8 forces eight waves per board, any other value four
     int trunk_blocks_per_cu;  // AZ_TRUNK_BLOCKS_PER_CU (-1: 3, and the natural size for the four-pass 8x8 forms): blocks per CU the LDS request of k_trunk / k_trunk_quad is padded to on the tuned planes; outside 1..8 = the natural size
@@ -53,6 +54,7 @@ inline const NetTuning &net_tuning() {
         v.beside_trunk2_min = net_env("AZ_BESIDE_TRUNK2_MIN", 4096); v.beside_frag_max = net_env("AZ_BESIDE_FRAG_MAX", 1024); v.beside_tile = net_env("AZ_BESIDE_TILE", 0);
         v.gemm_solo = net_env("AZ_GEMM_SOLO", -1); v.dense_frag_max = net_env("AZ_DENSE_FRAG_MAX", -1); v.gemm_tile = net_env("AZ_GEMM_TILE", 0);
         v.gemm_form = net_env("AZ_GEMM_FORM", -1); v.trunk_quad_prefetch = net_env("AZ_TRUNK_QUAD_PREFETCH", -1);
+        v.trunk_quad_stores = net_env("AZ_TRUNK_QUAD_STORES", -1);
         v.qd_small_max = net_env("AZ_QD_SMALL_MAX", 512); v.qg_cfg = net_env("AZ_QG_CFG", 0);
         v.heads_small_max = net_env("AZ_HEADS_SMALL_MAX", -1); v.heads_v1 = net_env("AZ_HEADS_V1", 0) != 0; v.heads_rh = net_env("AZ_HEADS_RH", 0);
         v.tail_v1 = net_env("AZ_TAIL_V1", 0) != 0; v.no_fused_tail = net_env("AZ_NO_FUSED_TAIL", 0) != 0; v.tail_r8_from = net_env("AZ_TAIL_R8_FROM", INT_MAX);
@@ -80,6 +82,7 @@ struct StagePlan {
     int waves;         // k_trunk_q: waves per board (4 / 8); k_trunk2: waves per workgroup (4 / 8)
     int quad_form;     // k_trunk_quad: 0 / 1 / 2
     int quad_prefetch; // k_trunk_quad: 1 = the prefetching form (weights and input requested across the phase boundaries; same bits)
+    int quad_stores;   // k_trunk_quad's prefetching form: 1 = conv3's planes and conv4's features stored as vectors (same bits)
     int lds_blocks;    // k_trunk, k_trunk_quad: blocks per CU the LDS request is padded to (outside 1..8: the kernel's natural size)
     int bm, bn;        // k_gemm: the workgroup tile (0: N fits none)
     int gemm_form;     // k_gemm: 0 = LDS double buffer, the chain stops at every K tile; 1 = LDS ring, the chain runs through (k_gemm_ring)
@@ -154,6 +157,10 @@ inline StagePlan plan_trunk(const NetDims &d, const NetTuning &t, int B, int bes
     // (AZ_TRUNK_QUAD=1) reaches it through AZ_TRUNK_QUAD_PREFETCH=1 only.  Legs: profiles/r24_trunk_prefetch.txt.
     const bool measured = d.game == AZ_OTHELLO && beside;
     p.quad_prefetch = quad_prefetch_shape(d.CH, d.CW, p.quad_form) && (t.trunk_quad_prefetch >= 0 ? t.trunk_quad_prefetch == 1 : measured) ? 1 : 0;
+    // Its vector stores: conv3's planes as paired LDS writes, conv4's features as 16-byte stores.  A form OF the
+    // prefetching form, under the same rule, on the same measurement (OthelloNet 8x8 beside another chain).  Legs:
+    // profiles/r25_beside_fc1_trunk.txt.
+    p.quad_stores = p.quad_prefetch && (t.trunk_quad_stores >= 0 ? t.trunk_quad_stores == 1 : measured) ? 1 : 0;
     return p;
 }
 

@@ -204,6 +204,16 @@ class HipNet:
         """True where the trunk of a launch of B boards (beside: az_net_forward_lane's flag) runs k_trunk_quad's prefetching form"""
         return bool(lib().az_net_trunk_prefetch(self.h, B, int(beside)))
 
+    def stage_plan(self, stage, B, beside):
+        """the plan of stage 0..3 of a launch of B boards as text: kernel and the plan's fields for it (az_net_stage_plan)"""
+        buf = C.create_string_buffer(128)
+        check(lib().az_net_stage_plan(self.h, stage, B, int(beside), buf, 128))
+        return buf.value.decode()
+
+    def trunk_stores(self, B, beside):
+        """True where that trunk runs the prefetching form with vector stores of conv3's planes and conv4's features"""
+        return bool(lib().az_net_trunk_stores(self.h, B, int(beside)))
+
     def profile(self, enable=True):
         """bracket every stage launch of the following forwards with HIP events (az_net_profile)"""
         check(lib().az_net_profile(self.h, 1 if enable else 0))

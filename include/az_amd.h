@@ -138,6 +138,19 @@ int az_net_stage_kernel(const az_net *net, int stage, int B, char *buf, int cap)
 /* 1 where the trunk of a launch of B boards (beside as in az_net_forward_lane) runs the prefetching form of k_trunk_quad, else 0
  * (AZ_TRUNK_QUAD_PREFETCH: unset = by regime, 0 = never, 1 = wherever the form is built); the forms give the same bits */
 int az_net_trunk_prefetch(const az_net *net, int B, int beside);
+/* 1 where the trunk of that launch runs the prefetching form with vector stores (conv3's planes as paired LDS writes, conv4's features
+ * as 16-byte stores), else 0 (AZ_TRUNK_QUAD_STORES: unset = by regime, 0 = never, 1 = wherever the prefetching form runs); the same bits */
+int az_net_trunk_stores(const az_net *net, int B, int beside);
+/* The plan of stage 0..3 of a launch of B boards (beside as in az_net_forward_lane) as text: the kernel by its own name and the
+ * plan's fields for it, e.g. "k_trunk_quad form=2 lds_blocks=0 prefetch=1 stores=1", "k_gemm 64x64 form=1".  For tools' output. */
+int az_net_stage_plan(const az_net *net, int stage, int B, int beside, char *buf, int cap);
+/* One stage (0 trunk, 1 fc1, 2 fc2, 3 heads) of az_net_forward_lane with the same arguments: exactly the launch the forward makes for
+ * that stage, reading the lane's activation rows as they stand.  For tools that time one stage beside another on two streams.
+ * Only stage 3 writes d_probs / d_value (the fused tails: stage 1); they are required for every stage so that the call is the
+ * forward's.  The launch carries no events: under az_net_profile(net, 1) it is NOT booked in any slot.
+ * AZ_EINVAL: a null argument, a stage outside 0..3, the TicTacToe MLP (one stage), a lane or row count az_net_forward_lane refuses. */
+int az_net_stage_lane(az_net *net, int lane, int beside, int stage, const float *d_input, const int32_t *d_count, int max_B,
+                      float *d_probs, float *d_value, void *stream);
 /* Live measurement (the idiom of timers.py:53-76 applied per kernel): while enabled, every forward brackets its stage
  * launches with a start and a stop event each (hipExtLaunchKernelGGL).  ms_total[8] / launches[8], one slot per kernel family so that a slot's mean is the
  * figure rocprofv3 lists for that kernel: k_trunk2, fc1 and fc2 on the tiled GEMMs (k_gemm / k_gemm_solo; Connect4Net's fused tail

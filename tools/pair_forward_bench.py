@@ -40,4 +40,5 @@ for rep in range(3):
     t0 = time.perf_counter(); pair(400); torch.cuda.synchronize()
     pairs.append(round(1e6 * (time.perf_counter() - t0) / 400, 2))
 print(tag, "AZ_TRUNK_QUAD=" + os.environ.get("AZ_TRUNK_QUAD", "-"), "lone trunk us at 600/1024/2048/4095 x3:", lone, "pair of 2048-row forwards (count 1885) us x3:", pairs, "kernel", hnet.stage_kernel(0, 2048),
-      "k_trunk_quad prefetching form (AZ_TRUNK_QUAD_PREFETCH=" + os.environ.get("AZ_TRUNK_QUAD_PREFETCH", "-") + "): lone", hnet.trunk_prefetch(2048, 0), "pair", hnet.trunk_prefetch(2048, 1))
+      "k_trunk_quad prefetching form (AZ_TRUNK_QUAD_PREFETCH=" + os.environ.get("AZ_TRUNK_QUAD_PREFETCH", "-") + "): lone", hnet.trunk_prefetch(2048, 0), "pair", hnet.trunk_prefetch(2048, 1),
+      "its vector stores (AZ_TRUNK_QUAD_STORES=" + os.environ.get("AZ_TRUNK_QUAD_STORES", "-") + "): lone", hnet.trunk_stores(2048, 0), "pair", hnet.trunk_stores(2048, 1))

@@ -7,8 +7,9 @@ cycles inside the MFMA chain (from behind the issue of the phase's first k-step 
 the phase before up to that first k-step: the waits for weights, input and patches, the transforms' start, stores); per barrier the
 wait of the wave that arrives first and of the one that arrives last in its workgroup.  The stamps drain the LDS counter, so a probed
 kernel is a little slower than an unprobed one: compare the forms, not the absolute figures.  fc1 / fc2 stamp the first 3840 words of
-the same buffer behind the trunk, so workgroups 0 .. 39 are left out.
-  python tools/probe_trunk_quad.py"""
+the same buffer behind the trunk, so workgroups 0 .. 39 are left out.  AZ_TRUNK_QUAD_STORES in the environment reaches both children
+(0 / 1: the prefetching form's scalar / vector stores); one leg alone: AZ_TRUNK_QUAD_PREFETCH=1 ... child.
+  python tools/probe_trunk_quad.py [child]"""
 import ctypes as C
 import os
 import subprocess
@@ -47,7 +48,7 @@ def child():
                 E.check(L.az_net_forward_lane(hnet.h, l, 1, x[l].data_ptr(), cnt.data_ptr(), ROWS, pr[l].data_ptr(), va[l].data_ptr(), C.c_void_p(ss[l].cuda_stream)))
         torch.cuda.synchronize()
 
-    form = "prefetching" if hnet.trunk_prefetch(ROWS, 1) else "as it was"
+    form = ("prefetching, vector stores" if hnet.trunk_stores(ROWS, 1) else "prefetching") if hnet.trunk_prefetch(ROWS, 1) else "as it was"
     for lanes, what in (((0,), "alone"), ((0, 1), "two chains")):
         run(lanes, 20)
         n_wg = (COUNT + 3) // 4

@@ -20,7 +20,7 @@ def main():
     for B in sizes:
         t = [1e3 * hnet.time_stage(s, B, 200) for s in (0, 1, -1)]
         print(f"{B:>6} " + " ".join(f"{x:8.1f}" for x in t) + "   " + ", ".join(hnet.stage_kernel(s, B) for s in (0, 1))
-              + (" (k_trunk_quad, prefetching form)" if hnet.trunk_prefetch(B, 0) else ""), flush=True)
+              + (" (k_trunk_quad, prefetching form" + (", vector stores)" if hnet.trunk_stores(B, 0) else ")") if hnet.trunk_prefetch(B, 0) else ""), flush=True)
 
 
 if __name__ == "__main__":
