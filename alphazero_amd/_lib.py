@@ -36,7 +36,8 @@ class EngineCfg(C.Structure):
 class EngineStats(C.Structure):
     _fields_ = [("games_done", C.c_int64), ("samples", C.c_int64), ("net_evals", C.c_int64),
                 ("lockstep_iters", C.c_int64), ("plies", C.c_int64), ("max_nodes_used", C.c_int32),
-                ("error_flags", C.c_int32), ("graph_replays", C.c_int64), ("max_path_len", C.c_int32), ("reserved", C.c_int32)]
+                ("error_flags", C.c_int32), ("graph_replays", C.c_int64), ("max_path_len", C.c_int32), ("reserved", C.c_int32),
+                ("cache_hits", C.c_int64)]
 
 
 class EvalBatch(C.Structure):
@@ -69,6 +70,7 @@ SYMBOLS = [
     "az_engine_set_gumbel_full", "az_engine_root_value",
     "az_engine_set_playout_cap", "az_engine_playout_cap_stats", "az_playout_cap_full",
     "az_engine_set_forced_playouts", "az_engine_forced_playouts_stats", "az_forced_playout", "az_forced_prune",
+    "az_engine_set_eval_cache", "az_engine_eval_cache_stats",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
     "az_trainer_steps", "az_trainer_check", "az_trainer_debug", "az_trainer_buffer",
 ]
@@ -149,6 +151,8 @@ def lib():
     L.az_playout_cap_full.argtypes = [C.c_uint32, C.c_uint32, i32, C.c_double]
     L.az_engine_set_forced_playouts.argtypes = [vp, C.c_double]
     L.az_engine_forced_playouts_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.az_engine_set_eval_cache.argtypes = [vp, i32, i32, i32]
+    L.az_engine_eval_cache_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.az_forced_playout.argtypes = [i32, C.c_double, i32, C.c_double]
     L.az_forced_prune.argtypes = [i32, vp, vp, vp, i32, C.c_double, vp]
     L.az_augment_count.argtypes = [C.c_int, vp, i64, C.POINTER(i64), vp]

@@ -12,6 +12,9 @@
 // (Opt-in, default off: az_engine_set_gumbel replaces the root's PUCT pick by Sequential Halving over actions sampled with Gumbel
 // noise and reads the root out by the completed Q-values -- k_step_gumbel below, another search again; az_engine_set_gumbel_batch
 // walks up to K simulations of a Sequential Halving phase per game and lock-step -- k_step_gumbel_multi.)
+// (By a measured rule: az_engine_set_eval_cache.  The games of an az_engine_run wave start from one position under one set of weights,
+// so a slot group keeps the network's outputs by exact position -- ec_lookup_grp, leaf_output -- and a leaf found there takes no batch
+// row; the bits a slot backs up are the ones the forward would have written.)
 //
 // HBM layout
 //   boards   : 2 x u64 bitboards + int8 side-to-move per slot (root and current leaf), SoA over slots
@@ -39,6 +42,7 @@
 
 #include "az_device.h"
 #include "az_host.h"
+#include "az_search_plan.h"  // up here for the evaluation cache's key arithmetic, which the step kernels share with the host (ec_*)
 
 #define F_EXPANDED 1
 #define F_TERMINAL 2
@@ -64,6 +68,7 @@
 enum { CTR_SAMPLES = 0, CTR_GAMES_DONE, CTR_NET_EVALS, CTR_NEXT_GAME, CTR_TOTAL_GAMES, CTR_FIRST_ID, CTR_PLIES,
        CTR_FULL_PLIES, CTR_FAST_PLIES,  // az_engine_set_playout_cap: the plies k_move played after a full / a fast search (counted while the mode is on)
        CTR_FORCED_PICKS, CTR_PRUNED,    // az_engine_set_forced_playouts: root selections with a forced child / playouts pruned from the recorded targets
+       CTR_CACHE_HITS,                  // az_engine_set_eval_cache: leaves answered from the group's table (they count in CTR_NET_EVALS too)
        CTR_COUNT };
 // entries beyond CTR_COUNT live as long as the engine (k_reset_all clears [0, CTR_COUNT) only)
 enum { CTR_COLLISIONS = CTR_COUNT, CTR_ALLOC };
@@ -130,7 +135,22 @@ struct EngDev {
     // with a forced child since its last move (k_move folds them into ctr[], as evals).  Null unless the mode is on: then no kernel touches it.
     double kforced;
     int *fpicks;
+    // az_engine_set_eval_cache (step_grp): the slot group's table of network outputs by exact position -- ec_hdr
+    // [ec_mask + 1] tag and key, ec_pay [ec_mask + 1][ec_stride] the A priors and the value -- and the group's serial word, from which
+    // a step kernel forms its stamp; ec_claim [G] = the entry the slot's pending leaf claimed (-1: none), ec_hits [G] = the slot's
+    // leaves answered from the table in this ply (the ply's last backup folds them into ctr[]).  Positions of at most ec_limit
+    // stones only.  Null unless the cache is in force (az_engine_run alone sets them): then no kernel touches it.
+    struct EcHdr *ec_hdr;
+    float *ec_pay;
+    u32 *ec_serial;
+    int *ec_claim, *ec_hits;
+    u32 ec_mask;
+    int ec_limit, ec_stride;
 };
+// tag = ec_tag(hash, the claimer's stamp), 0 = empty: claimed by one device-scope compare-and-swap, never rewritten within a run; the
+// key is written by the claimer in the same kernel, the payload in the group's next one
+struct __attribute__((aligned(16))) EcHdr { u64 tag, p1, m1; long long player; };
+static_assert(sizeof(EcHdr) == 32, "an entry's tag and key are two 16-byte accesses");
 #define CAP_FULL 0x7fffffff  // the budget of a full ply: every simulation of any search call, and the mark root noise asks for
 
 // ---------------------------------------------------------------------------------------------
@@ -487,6 +507,53 @@ AZ_D int alloc_rows_block(int *counter, bool want) {
     return s_base + rank;
 }
 
+// az_engine_set_eval_cache: the pending leaf `b` of a slot against its group's table, by the group's lanes sub < AZ_EC_PROBE with one
+// entry each (tag and key come in one round trip).  `stamp` is this kernel's.  Returns the entry on a hit; else -1, with *claim = the
+// entry this slot claimed for the position -- it writes the key here and the payload in the next kernel's backup -- or -1.
+//   hit   : the full key is equal and the entry's stamp is older than this kernel's.  Such an entry was claimed in an earlier kernel of
+//           this stream, so its key is complete (kernel boundary); its payload is written by the kernel after the claim -- at the latest
+//           the one running -- and is read by the NEXT kernel's backup, behind another boundary.
+//   claim : the first probed entry seen empty, by one device-scope atomicCAS (executed at the memory side, so exact whatever an XCD's
+//           L2 holds).  A tag is written once per run, so a stale view of it is the empty one and ends in a lost CAS: a miss, no insert.
+//   An entry of this very kernel (equal stamp) under the position's hash ends the lookup without a claim: most likely another slot's
+//   claim of the same position.  Nothing loops, nothing waits for another workgroup.
+AZ_D int ec_lookup_grp(const EngDev &E, const BB &b, u32 stamp, int sub, int *claim) {
+    const u32 h = ec_hash(b.p1, b.m1, b.player);
+    const int idx = (int)ec_bucket(h, sub & (AZ_EC_PROBE - 1), E.ec_mask + 1u);
+    EcHdr *p = E.ec_hdr + idx;
+    const uint4 *q = reinterpret_cast<const uint4 *>(p);
+    const uint4 x = q[0], y = q[1];
+    const u64 tag = ((u64)x.y << 32) | x.x, p1 = ((u64)x.w << 32) | x.z, m1 = ((u64)y.y << 32) | y.x;
+    const bool lane = sub < AZ_EC_PROBE;
+    const bool same = tag != 0 && ec_tag_hash(tag) == h, older = ec_tag_stamp(tag) < stamp;
+    const u32 m_hit = grp_ballot(lane && same && older && p1 == b.p1 && m1 == b.m1 && (int)y.z == b.player);
+    const u32 m_now = grp_ballot(lane && same && !older);
+    const u32 m_free = grp_ballot(lane && tag == 0);
+    *claim = -1;
+    if (m_hit) return __shfl(idx, __ffs((int)m_hit) - 1, LPG);
+    if (m_now || !m_free) return -1;
+    const int first = __ffs((int)m_free) - 1;
+    int won = 0;
+    if (sub == first) {
+        won = atomicCAS(&p->tag, 0ULL, ec_tag(h, stamp)) == 0ULL ? 1 : 0;
+        if (won) { p->p1 = b.p1; p->m1 = b.m1; p->player = (long long)b.player; }
+    }
+    if (__shfl(won, first, LPG)) *claim = __shfl(idx, first, LPG);
+    return -1;
+}
+
+// The network's output for the leaf a slot selected in the previous lock-step: row `row` of the batch, or the payload of the table
+// entry the row stands for (ec_row_of_entry; only with az_engine_set_eval_cache in force).  *v = the value.
+AZ_D const float *leaf_output(const EngDev &E, int row, float *v) {
+    if (ec_row_is_entry(row)) {
+        const float *pay = E.ec_pay + (size_t)ec_entry_of_row(row) * E.ec_stride;
+        *v = pay[E.A];
+        return pay;
+    }
+    *v = E.value[row];
+    return E.probs + (size_t)row * E.A;
+}
+
 AZ_D double log_gamma_draw(const EngDev &E, u32 gid, int ply, int sim, double alpha, u32 j) {
     double d = (alpha + 1.0) - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d), g = d;
     bool accepted = false;
@@ -680,7 +747,9 @@ __device__ unsigned long long az_step_probe[4096 * 8];
 // FORCED (az_engine_set_forced_playouts, k_step_forced / k_step_cap_forced): on a full ply (budget == CAP_FULL) the root's selection
 // is walk_grp's forced one with k = kforced, and the group's first lane counts the selections that had a forced child in fpicks[g],
 // with the pending-leaf stores.  FORCED false is the kernel as it was.
-template <bool BACKUP, bool SELECT, bool CAP, bool FORCED>
+// EC (az_engine_set_eval_cache, k_step_cached): the leaf is looked up in the slot group's table before it asks for a batch row, and a
+// slot that claimed an entry fills it in its next backup.  EC false is the kernel as it was: none of that code is compiled in.
+template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false>
 AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
@@ -715,6 +784,11 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
     int node = E.root[gs];
     const int budget = CAP ? E.budget[gs] : CAP_FULL;  // with the loads above: no round trip of its own
     const int fpicks = (FORCED && SELECT) ? E.fpicks[gs] : 0;
+    // az_engine_set_eval_cache: the entry the pending leaf claimed, and the group's serial word (uniform; this kernel's stamp with sim)
+    // and, in the ply's last backup, the slot's hits of this ply, which that kernel folds into ctr[]
+    const int ec_prev = (EC && BACKUP) ? E.ec_claim[gs] : -1;
+    const u32 ec_serial = EC ? *E.ec_serial : 0u;
+    const int ec_nhits = (EC && !SELECT) ? E.ec_hits[gs] : 0;
     Node fwd;
     bool have_root = false;
     PSTAMP(1)
@@ -726,8 +800,15 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
         double outcome;
         bool ok = true;
         if (st == LS_EVAL) {
-            const float v = E.value[row_prev];
-            int k = create_children_grp(E, g, pool, n_nodes, leaf, lb, E.probs + (size_t)row_prev * E.A, sub);
+            float v = 0.0f;
+            const float *pr = E.probs + (size_t)row_prev * E.A;
+            if (EC) pr = leaf_output(E, row_prev, &v);
+            else v = E.value[row_prev];
+            int k = create_children_grp(E, g, pool, n_nodes, leaf, lb, pr, sub);
+            if (EC && ec_prev >= 0) {  // the slot won its claim in the previous kernel: its batch row becomes the entry's payload
+                float *pay = E.ec_pay + (size_t)ec_prev * E.ec_stride;
+                for (int i = sub; i <= E.A; i += LPG) pay[i] = i < E.A ? pr[i] : v;
+            }
             ok = k > 0;
             n_nodes += ok ? k : 0;
             outcome = (double)lb.player * (double)v;  // base.py:366
@@ -754,7 +835,12 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
     }
     PSTAMP(3)
     if (BACKUP && sub == 0 && in_range) E.evals[g] = evals;
-    if (!SELECT) return;
+    if (!SELECT) {
+        // the ply's last backup: no lookup in this kernel, so no block needs the serial word any more -- the next ply's stamps follow on
+        if (EC && blockIdx.x == 0 && threadIdx.x == 0) *E.ec_serial = ec_stamp(ec_serial, sim);
+        if (EC && sub == 0 && in_range && ec_nhits) { atomicAdd(&E.ctr[CTR_CACHE_HITS], (unsigned long long)ec_nhits); E.ec_hits[g] = 0; }
+        return;
+    }
     // From here on no group may leave early: the leaf rows are handed out per block (alloc_rows_block) behind workgroup barriers.
     int status = LS_NONE, w = 0;
     Walk wk = {b, Node(), node, 1, sub == 0 ? node : -1, false};
@@ -777,10 +863,14 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
         if (sub == 0) { E.path_len[g] = wk.plen; if (wk.plen > LPG) atomicMax(E.max_path, wk.plen); }
         status = classify_leaf_grp(E, pool, wk, w, sub);
     }
-    const int row = __shfl(alloc_rows_block(E.batch_cnt + (sim & 1), status == LS_EVAL && sub == 0), 0, LPG);
+    // az_engine_set_eval_cache: a leaf within the stone limit is looked up first; a hit takes no batch row and writes no input, the next
+    // backup reads the entry's payload through the negative row.  Beyond the limit the kernel pays this one compare.
+    int ec_hit = -1, ec_claim = -1;
+    if (EC && status == LS_EVAL && ec_in_limit(wk.b.p1, wk.b.m1, E.ec_limit)) ec_hit = ec_lookup_grp(E, wk.b, ec_stamp(ec_serial, sim), sub, &ec_claim);
+    const int row = __shfl(alloc_rows_block(E.batch_cnt + (sim & 1), status == LS_EVAL && ec_hit < 0 && sub == 0), 0, LPG);
     if (status == LS_EVAL) {
-        write_nn_input_grp(E, row, wk.b, sub);
-        if (sub == 0) E.row_of_slot[g] = row;
+        if (ec_hit < 0) write_nn_input_grp(E, row, wk.b, sub);
+        if (sub == 0) E.row_of_slot[g] = ec_hit < 0 ? row : ec_row_of_entry(ec_hit);
     }
     if (sub == 0 && in_range) {
         if (walks) {
@@ -789,6 +879,10 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
             if (FORCED && forced_pick) E.fpicks[g] = fpicks + 1;
         }
         E.leaf_status[g] = (int8_t)status;
+        if (EC) {
+            if (!BACKUP || ec_claim != ec_prev) E.ec_claim[g] = ec_claim;  // beyond the opening both are -1: no store
+            if (ec_hit >= 0) atomicAdd(&E.ec_hits[g], 1);  // the slot's own word: no return value, no round trip
+        }
     }
     PSTAMP(6)
 #ifdef AZ_PROBE
@@ -810,6 +904,10 @@ template <bool BACKUP, bool SELECT>
 __global__ __launch_bounds__(256) void k_step_forced(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, false, true>(E, sim, g0, g1); }
 template <bool BACKUP, bool SELECT>
 __global__ __launch_bounds__(256) void k_step_cap_forced(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, true, true>(E, sim, g0, g1); }
+// and any of the four with the leaf evaluation cache in force (az_engine_set_eval_cache): launched only where E.ec_hdr is set, so the
+// kernels above stay the code they were for every search that does not cache
+template <bool BACKUP, bool SELECT, bool CAP, bool FORCED>
+__global__ __launch_bounds__(256) void k_step_cached(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, CAP, FORCED, true>(E, sim, g0, g1); }
 
 // One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
 // SELECT of kt walkers.  Lane j of the game's group owns walker j's pending words (loaded / stored coalesced, handed round by
@@ -2214,6 +2312,18 @@ struct az_engine {
     // az_engine_set_forced_playouts: the per-slot counts of forced root selections, [G], allocated when the mode first goes on; in
     // force (d.fpicks == forced_picks, d.kforced > 0) only while it is on, else d.fpicks is null
     int *forced_picks = nullptr;
+    // az_engine_set_eval_cache: the request (AZ_EVAL_CACHE_*) and whether AZ_ENGINE_EVAL_CACHE made it; entries per group and the stone
+    // limit; the groups' tables, their serial words and the per-slot words, allocated by the first run that caches.  d.ec_* point at
+    // them only inside az_engine_run (ec_attach): every other entry point launches with null pointers.  graphs_ec: the captured
+    // searches carry the tables' pointers (a search with the other setting drops them first).
+    int ec_req = AZ_EVAL_CACHE_AUTO;
+    bool ec_env = false;
+    int ec_capacity = AZ_EC_DEFAULT_CAPACITY, ec_limit = AZ_EC_DEFAULT_LIMIT;
+    EcHdr *ec_hdr[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
+    float *ec_pay[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
+    u32 *ec_serial = nullptr;
+    int *ec_claim = nullptr, *ec_hits = nullptr;
+    bool graphs_ec = false;
     int groups_req = 0;
     bool groups_env = false;
     hipStream_t gstream[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2313,6 +2423,8 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.nval = nullptr;
     d.cap_nfast = 0; d.cap_pfull = 1.0; d.budget = nullptr;
     d.kforced = 0.0; d.fpicks = nullptr;
+    d.ec_hdr = nullptr; d.ec_pay = nullptr; d.ec_serial = nullptr; d.ec_claim = nullptr; d.ec_hits = nullptr;
+    d.ec_mask = 0; d.ec_limit = 0; d.ec_stride = 0;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2341,6 +2453,10 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
         const char *g = getenv("AZ_ENGINE_GROUPS");
         const int n = g ? atoi(g) : 0;
         if (n == 1 || n == 2 || n == 4) { e->groups_req = n; e->groups_env = true; }
+    }
+    if (rc == AZ_OK) {  // AZ_ENGINE_EVAL_CACHE, likewise: 0 = never, 1 = wherever the cache is served (eval_cache_in_force)
+        const char *c = getenv("AZ_ENGINE_EVAL_CACHE");
+        if (c && (c[0] == '0' || c[0] == '1') && c[1] == 0) { e->ec_req = c[0] == '1' ? AZ_EVAL_CACHE_ON : AZ_EVAL_CACHE_OFF; e->ec_env = true; }
     }
     if (rc != AZ_OK) { az_engine_destroy(e); return rc; }
     if (hipStreamSynchronize(e->stream) != hipSuccess) { az_engine_destroy(e); az_set_error("stream sync failed"); return AZ_EHIP; }
@@ -2374,6 +2490,7 @@ extern "C" void az_engine_destroy(az_engine *e) {
     }
     for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
     for (void *p : e->allocs) (void)hipFree(p);
+    for (int i = 0; i < AZ_MAX_GROUPS; ++i) { if (e->ec_hdr[i]) (void)hipFree(e->ec_hdr[i]); if (e->ec_pay[i]) (void)hipFree(e->ec_pay[i]); }
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->h_ctr) (void)hipHostFree(e->h_ctr);
@@ -2441,10 +2558,23 @@ static void launch_step_as(const SearchPlan &p, const Chain &c, int n_sim, const
     const dim3 gg((unsigned)((c.g1 - c.g0 + GPB - 1) / GPB)), gb(256);
     switch (p.family) {
         case SF_ROLLOUT: hipLaunchKernelGGL(k_rollout_step, gg, gb, 0, c.st, d, a.t); break;
-        case SF_STEP: hipLaunchKernelGGL((k_step<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
-        case SF_STEP_CAP: hipLaunchKernelGGL((k_step_cap<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
-        case SF_STEP_FORCED: hipLaunchKernelGGL((k_step_forced<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
-        case SF_STEP_CAP_FORCED: hipLaunchKernelGGL((k_step_cap_forced<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1); break;
+        // the four one-leaf families: with the evaluation cache's pointers set (az_engine_run alone sets them) their cached instantiation
+        case SF_STEP:
+            if (d.ec_hdr) hipLaunchKernelGGL((k_step_cached<B, S, false, false>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            break;
+        case SF_STEP_CAP:
+            if (d.ec_hdr) hipLaunchKernelGGL((k_step_cached<B, S, true, false>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step_cap<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            break;
+        case SF_STEP_FORCED:
+            if (d.ec_hdr) hipLaunchKernelGGL((k_step_cached<B, S, false, true>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step_forced<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            break;
+        case SF_STEP_CAP_FORCED:
+            if (d.ec_hdr) hipLaunchKernelGGL((k_step_cached<B, S, true, true>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step_cap_forced<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            break;
         case SF_STEP_MULTI: hipLaunchKernelGGL((k_step_multi<B, S>), gg, gb, 0, c.st, d, a.t, a.kb, a.kt); break;
         case SF_STEP_GUMBEL:
             if (p.full) hipLaunchKernelGGL((k_step_gumbel<B, S, true>), gg, gb, 0, c.st, d, a.t, n_sim, c.g0, c.g1);
@@ -2507,6 +2637,8 @@ static int do_search(az_engine *e, int n_sim, const Chain *grp = nullptr) {
     if (graphable || (profiled && d.sim_base == 0)) cap = quantised_cap(W * d.K, cap);
     if (!graphable) return enqueue_search(e, c, plan, n_sim, cap);
     // another family, or the full instantiation of a Gumbel one, launches other kernels: the key keeps their graphs apart
+    // (and a captured search holds the evaluation cache's pointers, or null ones, by value: one with the other setting replays none of them)
+    if ((d.ec_hdr != nullptr) != e->graphs_ec) { drop_graphs(e); e->graphs_ec = d.ec_hdr != nullptr; }
     const SearchKey key = search_key(plan, n_sim, cap, c.g0, c.g1);
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) {
@@ -2653,6 +2785,8 @@ static int make_chain(az_engine *e, int i, int n, Chain *c) {
     c->d.sim_base = 0;
     c->d.nn_in = d.nn_in + (size_t)g0 * d.gd.cells; c->d.probs = d.probs + (size_t)g0 * d.A; c->d.value = d.value + g0;
     c->d.batch_cnt = d.batch_cnt + 4 * i; c->d.live = d.live + i;
+    // the group's own evaluation cache: the two groups' kernels are not ordered against each other, a table's producers and consumers are
+    if (d.ec_hdr) { c->d.ec_hdr = e->ec_hdr[i]; c->d.ec_pay = e->ec_pay[i]; c->d.ec_serial = e->ec_serial + i; }
     return AZ_OK;
 }
 
@@ -2714,10 +2848,50 @@ static int run_grouped(az_engine *e, int n, int32_t n_games, long long max_iters
     return AZ_ESTATE;
 }
 
+// ---- leaf evaluation cache (az_engine_set_eval_cache) -----------------------------------------------------------
+// whether the next az_engine_run caches: the request (auto: the rule) where the cache is served
+static bool eval_cache_on(const az_engine *e) {
+    return eval_cache_in_force(e->ec_req, e->cfg.evaluator, e->cfg.game, e->cfg.H, e->cfg.W, e->d.G, beyond_plain_search(e) != nullptr,
+                               e->net && az_net_profiling(e->net));
+}
+
+// A run that caches: the tables of its n slot groups (allocated at their first use), cleared on the engine's stream -- every group's
+// stream is ordered behind it (ev_grp) -- and the engine's device view pointing at group 0's until the run returns (ec_detach).
+static int ec_attach(az_engine *e, int n) {
+    EngDev &d = e->d;
+    const size_t cap = (size_t)e->ec_capacity, stride = (size_t)ec_stride(d.A);
+    if (!e->ec_serial) AZ_TRY(dev_alloc(e, &e->ec_serial, (size_t)AZ_MAX_GROUPS));
+    if (!e->ec_claim) AZ_TRY(dev_alloc(e, &e->ec_claim, (size_t)d.G));
+    if (!e->ec_hits) AZ_TRY(dev_alloc(e, &e->ec_hits, (size_t)d.G));
+    for (int i = 0; i < n; ++i) {
+        if (!e->ec_hdr[i]) AZ_HIP(hipMalloc((void **)&e->ec_hdr[i], cap * sizeof(EcHdr)));
+        if (!e->ec_pay[i]) AZ_HIP(hipMalloc((void **)&e->ec_pay[i], cap * stride * sizeof(float)));
+        AZ_HIP(hipMemsetAsync(e->ec_hdr[i], 0, cap * sizeof(EcHdr), e->stream));  // the tags (0 = empty) with their keys
+    }
+    AZ_HIP(hipMemsetAsync(e->ec_serial, 0, sizeof(u32) * AZ_MAX_GROUPS, e->stream));
+    AZ_HIP(hipMemsetAsync(e->ec_hits, 0, sizeof(int) * (size_t)d.G, e->stream));
+    d.ec_hdr = e->ec_hdr[0]; d.ec_pay = e->ec_pay[0]; d.ec_serial = e->ec_serial; d.ec_claim = e->ec_claim; d.ec_hits = e->ec_hits;
+    d.ec_mask = (u32)cap - 1u; d.ec_limit = e->ec_limit; d.ec_stride = (int)stride;
+    return AZ_OK;
+}
+static void ec_detach(az_engine *e) {
+    EngDev &d = e->d;
+    d.ec_hdr = nullptr; d.ec_pay = nullptr; d.ec_serial = nullptr; d.ec_claim = nullptr; d.ec_hits = nullptr;
+    d.ec_mask = 0; d.ec_limit = 0; d.ec_stride = 0;
+}
+
+static int run_games(az_engine *e, uint32_t first_game_id, int32_t n_games);
+
 extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_games) {
     AZ_REQUIRE(e && n_games > 0, AZ_EINVAL, "bad arguments");
     AZ_NO_OPEN_SEARCH(e, "az_engine_run");
     AZ_NOT_IN_CALLBACK(e, "az_engine_run");
+    const int rc = run_games(e, first_game_id, n_games);
+    ec_detach(e);
+    return rc;
+}
+
+static int run_games(az_engine *e, uint32_t first_game_id, int32_t n_games) {
     AZ_TRY(enter(e));
     EngDev &d = e->d;
     AZ_TRY(reset_external(e));
@@ -2727,6 +2901,11 @@ extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_gam
         az_set_error("az_engine_run: %d slot groups were asked for (az_engine_set_groups) and are not served for %s", e->groups_req, beyond_plain_search(e));
         return AZ_EINVAL;
     }
+    if (e->ec_req == AZ_EVAL_CACHE_ON && !e->ec_env && beyond_plain_search(e)) {
+        az_set_error("az_engine_run: the evaluation cache was asked for (az_engine_set_eval_cache) and is not served for %s", beyond_plain_search(e));
+        return AZ_EINVAL;
+    }
+    if (eval_cache_on(e)) AZ_TRY(ec_attach(e, n_groups));
     hipLaunchKernelGGL(k_reset_all, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, (u32)first_game_id, (int)n_games);
     long long max_iters = ((long long)n_games / d.G + 2) * (long long)d.max_plies + 8;
     e->active_bound = n_games < d.G ? n_games : d.G;
@@ -2766,6 +2945,7 @@ extern "C" int az_engine_get_stats(az_engine *e, az_engine_stats *out) {
     out->graph_replays = e->graph_replays;
     out->max_path_len = e->h_err[2];
     out->reserved = 0;
+    out->cache_hits = (int64_t)e->h_ctr[CTR_CACHE_HITS];
     return AZ_OK;
 }
 
@@ -3433,6 +3613,44 @@ extern "C" int az_engine_forced_playouts_stats(az_engine *e, int64_t *forced_pic
     AZ_TRY(fetch_counters(e));
     *forced_picks = (int64_t)e->h_ctr[CTR_FORCED_PICKS];
     *pruned_playouts = (int64_t)e->h_ctr[CTR_PRUNED];
+    return AZ_OK;
+}
+
+// ---- leaf evaluation cache (k_step_cached) ------------------------------------------------------------------------
+extern "C" int az_engine_set_eval_cache(az_engine *e, int32_t mode, int32_t capacity, int32_t stone_limit) {
+    AZ_SETTER(e, "az_engine_set_eval_cache");
+    AZ_REQUIRE(mode == AZ_EVAL_CACHE_AUTO || mode == AZ_EVAL_CACHE_OFF || mode == AZ_EVAL_CACHE_ON, AZ_EINVAL,
+               "az_engine_set_eval_cache: mode %d (AZ_EVAL_CACHE_AUTO = -1, _OFF = 0, _ON = 1)", mode);
+    AZ_REQUIRE(ec_capacity_ok(capacity), AZ_EINVAL, "az_engine_set_eval_cache: capacity must be a power of two in [1, %d] (0 = the default, %d), got %d", AZ_EC_MAX_CAPACITY, AZ_EC_DEFAULT_CAPACITY, capacity);
+    AZ_REQUIRE(ec_limit_ok(stone_limit), AZ_EINVAL, "az_engine_set_eval_cache: stone_limit must be in [1, 64] (0 = the default, %d), got %d", AZ_EC_DEFAULT_LIMIT, stone_limit);
+    if (mode == AZ_EVAL_CACHE_ON) {
+        AZ_REQUIRE(e->cfg.evaluator == AZ_EVAL_NET, AZ_EINVAL, "az_engine_set_eval_cache: the evaluation cache is not served for %s", e->cfg.evaluator == AZ_EVAL_FAKE ? "the fake evaluator (AZ_EVAL_FAKE)" : beyond_plain_search(e));
+        const char *why = beyond_plain_search(e);
+        AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_eval_cache: the evaluation cache is not served for %s", why);
+    }
+    const int cap = capacity > 0 ? capacity : AZ_EC_DEFAULT_CAPACITY, lim = stone_limit > 0 ? stone_limit : AZ_EC_DEFAULT_LIMIT;
+    if (mode == e->ec_req && !e->ec_env && cap == e->ec_capacity && lim == e->ec_limit) return AZ_OK;
+    AZ_TRY(enter(e));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    if (cap != e->ec_capacity)  // tables of another size: the next caching run allocates them
+        for (int i = 0; i < AZ_MAX_GROUPS; ++i) {
+            if (e->ec_hdr[i]) (void)hipFree(e->ec_hdr[i]);
+            if (e->ec_pay[i]) (void)hipFree(e->ec_pay[i]);
+            e->ec_hdr[i] = nullptr; e->ec_pay[i] = nullptr;
+        }
+    e->ec_req = mode; e->ec_env = false; e->ec_capacity = cap; e->ec_limit = lim;
+    // the tables' pointers, the mask and the limit are launch arguments: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_eval_cache_stats(az_engine *e, int32_t *in_force, int64_t *hits) {
+    AZ_REQUIRE(e && in_force && hits, AZ_EINVAL, "null argument");
+    AZ_USABLE(e, "az_engine_eval_cache_stats");  // as az_engine_get_stats, whose net_evals the hits are a part of
+    AZ_TRY(enter(e));
+    AZ_TRY(fetch_counters(e));
+    *in_force = eval_cache_on(e) ? 1 : 0;
+    *hits = (int64_t)e->h_ctr[CTR_CACHE_HITS];
     return AZ_OK;
 }
 

@@ -121,6 +121,67 @@ inline int groups_auto(int evaluator, int game, int H, int W, int G) {
     return 1;
 }
 
+// ---- the leaf evaluation cache (az_engine_set_eval_cache) ----------------------------------------------------------
+// A slot group's table of network outputs by exact position.  The arithmetic of its keys lives here so that the step kernels and the
+// host test (tests/eval_cache_table.cpp) share it.
+#if defined(__HIPCC__)
+#define AZ_PLAN_HD __host__ __device__ inline
+#else
+#define AZ_PLAN_HD inline
+#endif
+#define AZ_EC_PROBE 4                    // entries a lookup looks at: the bucket and the three behind it (one lane each)
+#define AZ_EC_DEFAULT_CAPACITY (1 << 18) // entries per slot group: 108 568 distinct positions of <= 12 stones in 1024 games (tools/eval_cache_count.py)
+#define AZ_EC_DEFAULT_LIMIT 12           // stones: keeps 4.54 of the 4.74 plies' worth of repeats per game
+#define AZ_EC_MAX_CAPACITY (1 << 22)
+
+// the bucket hash of a position: a 64-bit mix of the three key words, folded to 32 bits
+AZ_PLAN_HD uint32_t ec_hash(uint64_t p1, uint64_t m1, int player) {
+    uint64_t x = p1 * 0x9E3779B97F4A7C15ull ^ (m1 + (player > 0 ? 0x632BE59BD9B4E019ull : 0xD6E8FEB86659FD93ull));
+    x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 29; x *= 0x9E3779B97F4A7C15ull; x ^= x >> 32;
+    return (uint32_t)x;
+}
+// probe j of a lookup in a table of `capacity` entries (a power of two)
+AZ_PLAN_HD uint32_t ec_bucket(uint32_t hash, int j, uint32_t capacity) { return (hash + (uint32_t)j) & (capacity - 1u); }
+// only positions with at most `limit` stones are looked up or inserted
+AZ_PLAN_HD bool ec_in_limit(uint64_t p1, uint64_t m1, int limit) { return __builtin_popcountll(p1 | m1) <= limit; }
+// The stamp of a step kernel: the group's serial word (advanced by the ply's last backup) and the kernel's simulation index; never 0,
+// and greater in every later kernel of the group's stream.  An entry's tag word is its claimer's stamp over the hash: 0 = empty.
+AZ_PLAN_HD uint32_t ec_stamp(uint32_t serial, int sim) { return serial + (uint32_t)sim + 1u; }
+AZ_PLAN_HD uint64_t ec_tag(uint32_t hash, uint32_t stamp) { return ((uint64_t)stamp << 32) | hash; }
+AZ_PLAN_HD uint32_t ec_tag_stamp(uint64_t tag) { return (uint32_t)(tag >> 32); }
+AZ_PLAN_HD uint32_t ec_tag_hash(uint64_t tag) { return (uint32_t)tag; }
+// row_of_slot of a slot whose leaf was found in the table: the entry, as a negative row (batch rows are >= 0)
+AZ_PLAN_HD int ec_row_of_entry(int entry) { return -(1 + entry); }
+AZ_PLAN_HD bool ec_row_is_entry(int row) { return row < 0; }
+AZ_PLAN_HD int ec_entry_of_row(int row) { return -(row + 1); }
+// floats of an entry's payload: A priors and the value, in whole 16-byte words
+AZ_PLAN_HD int ec_stride(int A) { return (A + 1 + 3) & ~3; }
+
+// capacity and stone limit as az_engine_set_eval_cache takes them: 0 = the default; the capacity a power of two
+inline bool ec_capacity_ok(int capacity) { return capacity == 0 || (capacity >= 1 && capacity <= AZ_EC_MAX_CAPACITY && (capacity & (capacity - 1)) == 0); }
+inline bool ec_limit_ok(int limit) { return limit >= 0 && limit <= 64; }
+
+// Where the cache is served at all: az_engine_run's plain PUCT search of a network engine, the net not under az_net_profile (the
+// profiled step divides FLOPs x net_evals by kernel time and must keep describing full launches).  `beyond_plain`: az_engine.hip's
+// beyond_plain_search is not null (external / rollout evaluator, a symmetry mode, leaf_batch > 1, the Gumbel search).
+inline bool eval_cache_served(int evaluator, bool beyond_plain, bool profiled) { return evaluator == AZ_EVAL_NET && !beyond_plain && !profiled; }
+
+// The measured rule (profiles/r26_eval_cache.txt): the shapes az_engine_run caches at where nothing was asked
+// for.  As groups_auto: on only where the slowest of three cached runs beat the fastest of three uncached ones by more than their
+// spread; every shape that was not measured, or did not pass, plays without.
+inline bool eval_cache_auto(int evaluator, int game, int H, int W, int G) {
+    if (evaluator != AZ_EVAL_NET) return false;
+    if (game == AZ_GAME_OTHELLO && H == 8 && W == 8) return G >= 512;   // 512 slots +1.4 %, 4096 (2 x 2048) +2.5 %, 32768 (2 x 16384) +7.7 %
+    if (game == AZ_GAME_CONNECT4 && H == 6 && W == 7) return G >= 8192;  // 8192 slots (4 x 2048), 200 sims: +11.6 %
+    return false;                                                        // everything else: not measured
+}
+
+// request: AZ_EVAL_CACHE_AUTO (the rule), _OFF, _ON (wherever served)
+inline bool eval_cache_in_force(int request, int evaluator, int game, int H, int W, int G, bool beyond_plain, bool profiled) {
+    if (!eval_cache_served(evaluator, beyond_plain, profiled) || request == AZ_EVAL_CACHE_OFF) return false;
+    return request == AZ_EVAL_CACHE_ON || eval_cache_auto(evaluator, game, H, W, G);
+}
+
 // What a captured search is keyed by.  (What else travels in the launch arguments -- K, m, the playout cap's n_fast and p_full, forced
 // playouts' k, the pools -- drops every graph when it changes: az_engine.hip, drop_graphs.)
 typedef std::tuple<int, bool, int, int, int, int> SearchKey;

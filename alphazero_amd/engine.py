@@ -430,6 +430,22 @@ class SelfPlayEngine:
         check(lib().az_engine_forced_playouts_stats(self.h, C.byref(picks), C.byref(pruned)))
         return {"forced_picks": picks.value, "pruned_playouts": pruned.value}
 
+    def set_eval_cache(self, mode=None, capacity=0, stone_limit=0):
+        """the leaf evaluation cache of run() (az_engine_set_eval_cache): each slot group keeps the network's
+        outputs by exact position, so a leaf another game of the wave already sent through the network takes no batch row; the
+        samples do not change by a bit.  mode None = the measured rule, False = off, True = on wherever it is served (run() of an
+        EVAL_NET engine in the plain search; any other mode is a ValueError that names it).  capacity: entries per group, a power
+        of two (0: 2^18); stone_limit: only positions with at most that many stones are cached (0: 12)."""
+        m = -1 if mode is None else (1 if mode else 0)
+        check(lib().az_engine_set_eval_cache(self.h, m, int(capacity), int(stone_limit)))
+
+    def eval_cache_stats(self):
+        """{"in_force", "cache_hits"}: whether the next run() would cache, and the leaves answered from the cache since the last
+        run() began (they count in stats()["net_evals"] too: net_evals - cache_hits rows went through the network)"""
+        on, hits = C.c_int32(), C.c_int64()
+        check(lib().az_engine_eval_cache_stats(self.h, C.byref(on), C.byref(hits)))
+        return {"in_force": bool(on.value), "cache_hits": hits.value}
+
     @staticmethod
     def forced_playout(n, p, root_n, k):
         """the forced test of a root child with n visits and prior p under a root of root_n visits: True = forced (az_forced_playout:

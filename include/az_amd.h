@@ -189,6 +189,8 @@ typedef struct {
     int32_t max_path_len;   /* longest root..leaf path (nodes) of a simulation since the last run/set_roots; only paths
                                longer than 16 nodes are recorded (they take the parent-chasing back-propagation), else 0 */
     int32_t reserved;
+    int64_t cache_hits;     /* az_engine_set_eval_cache: the leaves answered from a slot group's table since the last az_engine_run began;
+                               they count in net_evals too (ABI 113) */
 } az_engine_stats;
 
 /* `stream` (hipStream_t, may be the default stream): the stream the caller's own work is queued on.  The engine runs on a
@@ -519,6 +521,33 @@ int az_engine_set_forced_playouts(az_engine *e, double k);
 int az_engine_forced_playouts_stats(az_engine *e, int64_t *forced_picks, int64_t *pruned_playouts);
 int az_forced_playout(int32_t n, double p, int32_t root_n, double k);
 int az_forced_prune(int32_t n_children, const int32_t *N, const double *Q, const double *P, int32_t root_n, double k, int32_t *out_N);
+
+/* ---- leaf evaluation cache -------------------------------------------------------------------------------
+ * Every game of an az_engine_run wave starts from the same position under one set of weights, and the network is a pure function
+ * of (board, side to move): each slot group keeps a table of the network's outputs by exact position, filled and read on the device
+ * by the plain search's step kernels.  A leaf found there takes no row of the lock-step's network batch and is backed up from the
+ * stored 65 + 1 floats -- the bits the forward would have written, so the samples of a run do not change by a bit.  The table is
+ * cleared at the start of every az_engine_run; nothing in it outlives a run or a set of weights.
+ *   mode        AZ_EVAL_CACHE_AUTO: the measured rule (on for the shapes where it was measured to pay, az_search_plan.h:
+ *               eval_cache_auto); AZ_EVAL_CACHE_OFF; AZ_EVAL_CACHE_ON: wherever it is served.  AZ_ENGINE_EVAL_CACHE in the
+ *               environment, read when the engine is created, makes the request where this setter has not been called: unset = auto,
+ *               0 = off, 1 = on (engines that do not serve the cache ignore it).
+ *   capacity    entries per slot group, a power of two up to 2^22; 0 = the default, 2^18.  A full table, or four occupied entries
+ *               behind a position's bucket, is a miss without an insert, never an error.
+ *   stone_limit only positions with at most this many stones are looked up or inserted, 1 .. 64; 0 = the default, 12.
+ *   counters    az_engine_eval_cache_stats: in_force = whether the next az_engine_run would cache; hits = the leaves answered from
+ *               the table since the last az_engine_run began, folded in by every ply's last backup (also az_engine_stats.cache_hits).  az_engine_stats'
+ *               net_evals keeps counting every evaluation the search consumed: net_evals - hits rows went through the network.
+ * Served: az_engine_run (1, 2 or 4 slot groups) of an AZ_EVAL_NET engine in the plain PUCT search, with the playout cap and forced
+ * playouts on or off.  Not served -- AZ_EVAL_CACHE_ON then answers AZ_EINVAL naming the mode, here or from az_engine_run if the mode
+ * came later; the rule and the environment switch answer off: AZ_EVAL_FAKE / _ROLLOUT / _EXTERNAL, either symmetry mode, leaf_batch
+ * > 1, the Gumbel search.  Never used, whatever the request: az_engine_search / _search_begin / az_engine_advance (the arena), and
+ * a run whose net is under az_net_profile.  AZ_ESTATE while a search is open.  A change drops the cached search graphs. */
+#define AZ_EVAL_CACHE_AUTO (-1)
+#define AZ_EVAL_CACHE_OFF 0
+#define AZ_EVAL_CACHE_ON 1
+int az_engine_set_eval_cache(az_engine *e, int32_t mode, int32_t capacity, int32_t stone_limit);
+int az_engine_eval_cache_stats(az_engine *e, int32_t *in_force, int64_t *hits);
 
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
