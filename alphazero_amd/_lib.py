@@ -13,6 +13,7 @@ NOISE_OFF, NOISE_PHILOX, NOISE_HASH = 0, 1, 2
 EVAL_NET, EVAL_FAKE, EVAL_ROLLOUT, EVAL_EXTERNAL = 0, 1, 2, 3
 SYM_ALL = -1  # AZ_SYM_ALL: every transform code the board has
 MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH
+SOLVE_MAX_EMPTIES, UNSOLVED, EXACT_MAX_EMPTIES = 12, 2, 10  # AZ_SOLVE_MAX_EMPTIES, AZ_UNSOLVED, AZ_EXACT_MAX_EMPTIES
 # AZ_TBUF_*: the class of a trainer's device buffer (az_trainer_buffer), by its number
 TRAINER_BUFFER_CLASSES = ("parameter", "momentum", "running_stat", "hyper", "workspace")
 
@@ -59,7 +60,7 @@ EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(EvalBatch), C.c_void_p)
 
 # every symbol include/az_amd.h declares (tests check that the library exports all of them)
 SYMBOLS = [
-    "az_last_error", "az_version", "az_board_legal_batch", "az_board_play_batch", "az_board_status_batch",
+    "az_last_error", "az_version", "az_board_legal_batch", "az_board_play_batch", "az_board_status_batch", "az_solve_batch",
     "az_net_create", "az_net_destroy", "az_net_set_tensor", "az_net_commit", "az_net_set_tensor_device", "az_net_commit_device", "az_net_forward", "az_net_forward_dyn", "az_net_set_lanes", "az_net_forward_lane", "az_net_forward_sym", "az_net_forward_sym_codes",
     "az_net_action_size",
     "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_trunk_prefetch", "az_net_trunk_stores", "az_net_stage_lane", "az_net_stage_plan", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
@@ -71,6 +72,7 @@ SYMBOLS = [
     "az_engine_set_playout_cap", "az_engine_playout_cap_stats", "az_playout_cap_full",
     "az_engine_set_forced_playouts", "az_engine_forced_playouts_stats", "az_forced_playout", "az_forced_prune",
     "az_engine_set_eval_cache", "az_engine_eval_cache_stats",
+    "az_engine_set_exact_endgame", "az_engine_exact_endgame_stats",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
     "az_trainer_steps", "az_trainer_check", "az_trainer_debug", "az_trainer_buffer",
 ]
@@ -89,6 +91,7 @@ def lib():
     L.az_board_legal_batch.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, i64, vp, vp]
     L.az_board_play_batch.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, i64, vp, vp, vp, vp]
     L.az_board_status_batch.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, i64, vp, vp, vp, vp]
+    L.az_solve_batch.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, i64, i32, i64, vp, vp, vp, vp]
     L.az_net_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.az_net_destroy.argtypes = [vp]
     L.az_net_destroy.restype = None
@@ -153,6 +156,8 @@ def lib():
     L.az_engine_forced_playouts_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.az_engine_set_eval_cache.argtypes = [vp, i32, i32, i32]
     L.az_engine_eval_cache_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+    L.az_engine_set_exact_endgame.argtypes = [vp, i32]
+    L.az_engine_exact_endgame_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.az_forced_playout.argtypes = [i32, C.c_double, i32, C.c_double]
     L.az_forced_prune.argtypes = [i32, vp, vp, vp, i32, C.c_double, vp]
     L.az_augment_count.argtypes = [C.c_int, vp, i64, C.POINTER(i64), vp]
@@ -178,7 +183,7 @@ def lib():
 
 # the sources a measurement depends on: counter files of the network kernels stay valid while only the engine or the training step
 # changes, and the other way round
-CSRC_COMPONENTS = {"net": ("az_net.hip",), "engine": ("az_engine.hip",), "train": ("az_train.hip",)}
+CSRC_COMPONENTS = {"net": ("az_net.hip",), "engine": ("az_engine.hip", "az_solve.h"), "train": ("az_train.hip",)}
 _CSRC_SHARED = ("az_device.h", "az_host.h", "Makefile")  # az_common.hip (version number, error string) holds no kernel code
 
 

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "az_device.h"
+#include "az_solve.h"
 #include "az_host.h"
 #include "az_search_plan.h"  // up here for the evaluation cache's key arithmetic, which the step kernels share with the host (ec_*)
 
@@ -49,6 +50,7 @@
 #define F_PF32 4
 #define F_NOISED 8
 #define F_EVALUATED 16
+#define F_SOLVED 32  // az_engine_set_exact_endgame: with F_TERMINAL, the winner was computed by the solver, not read off a finished board
 
 #define LS_NONE 0
 #define LS_EVAL 1
@@ -146,6 +148,12 @@ struct EngDev {
     int *ec_claim, *ec_hits;
     u32 ec_mask;
     int ec_limit, ec_stride;
+    // az_engine_set_exact_endgame (k_step_exact): exact_max = the empties limit of a solved leaf (0: off); x_solved / x_nodes [G] = the
+    // slot's leaves solved and the positions the solver entered for them since the last k_reset_all (the slot's own words, summed when
+    // the stats are read).  Null unless the mode is on: then no kernel touches them.
+    int exact_max;
+    int *x_solved;
+    unsigned long long *x_nodes;
 };
 // tag = ec_tag(hash, the claimer's stamp), 0 = empty: claimed by one device-scope compare-and-swap, never rewritten within a run; the
 // key is written by the claimer in the same kernel, the payload in the group's next one
@@ -682,6 +690,7 @@ __global__ void k_reset_all(EngDev E, u32 first_id, int n_games) {
     }
     if (g >= E.G) return;
     E.pool_sel[g] = 0;
+    if (E.x_solved) { E.x_solved[g] = 0; E.x_nodes[g] = 0; }
     if (g < n_games) reset_slot(E, g, first_id + (u32)g);
     else { E.active[g] = 0; E.leaf_status[g] = LS_NONE; }
 }
@@ -749,8 +758,12 @@ __device__ unsigned long long az_step_probe[4096 * 8];
 // with the pending-leaf stores.  FORCED false is the kernel as it was.
 // EC (az_engine_set_eval_cache, k_step_cached): the leaf is looked up in the slot group's table before it asks for a batch row, and a
 // slot that claimed an entry fills it in its next backup.  EC false is the kernel as it was: none of that code is compiled in.
-template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false>
-AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
+// EXACT (az_engine_set_exact_endgame, k_step_exact): a leaf that wants a network row and has at most exact_max empty cells is solved
+// on the spot (az_solve.h; xstk = the block's frame store in LDS) and becomes a terminal node whose winner is the outcome.  Before the
+// cache is consulted, and before the rows are handed out: the solver holds no barrier and the group leaves it as a whole.  EXACT false
+// is the kernel as it was.
+template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false, bool EXACT = false>
+AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
     // previous step's network kernels, which have completed) is cleared for the next step
@@ -862,6 +875,20 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1) {
         E.path[(size_t)g * LPG + sub] = wk.my_path;
         if (sub == 0) { E.path_len[g] = wk.plen; if (wk.plen > LPG) atomicMax(E.max_path, wk.plen); }
         status = classify_leaf_grp(E, pool, wk, w, sub);
+        if (EXACT && status == LS_EVAL && wk.plen > 1 && __popcll(E.gd.valid & ~(wk.b.p1 | wk.b.m1)) <= E.exact_max) {
+            int sw = 0, sa = -1;
+            unsigned long long cnt = 0;
+            if (az_solve_grp<AZ_EXACT_MAX_EMPTIES, 256>(E.gd, wk.b, sub, xstk + threadIdx.x, false, 0, &sw, &sa, &cnt) == AZ_SOLVE_OK) {
+                w = sw;
+                status = LS_TERM;
+                if (sub == 0) {
+                    pool[wk.node].flags = wk.cur.flags | F_TERMINAL | F_SOLVED; pool[wk.node].win = (int8_t)w;
+                    E.x_solved[g] += 1; E.x_nodes[g] += cnt;
+                }
+            } else if (sub == 0) {
+                atomicOr(E.err, ERR_INTERNAL);  // the solver's ceiling: reported, and the leaf goes to the network
+            }
+        }
     }
     // az_engine_set_eval_cache: a leaf within the stone limit is looked up first; a hit takes no batch row and writes no input, the next
     // backup reads the entry's payload through the negative row.  Beyond the limit the kernel pays this one compare.
@@ -908,6 +935,19 @@ __global__ __launch_bounds__(256) void k_step_cap_forced(EngDev E, int sim, int 
 // kernels above stay the code they were for every search that does not cache
 template <bool BACKUP, bool SELECT, bool CAP, bool FORCED>
 __global__ __launch_bounds__(256) void k_step_cached(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, CAP, FORCED, true>(E, sim, g0, g1); }
+// and the plain lock-step with exact endgames (az_engine_set_exact_endgame), without and with the cache: the solver's frames, three u64
+// per frame and lane, are the block's LDS (60 KiB: one block per CU's share of 64 KiB)
+#define EXACT_STK_WORDS (AZ_EXACT_MAX_EMPTIES * AZ_SOLVE_FRAME_WORDS * 256)
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_exact(EngDev E, int sim, int g0, int g1) {
+    __shared__ u64 s_xstk[EXACT_STK_WORDS];
+    step_grp<BACKUP, SELECT, false, false, false, true>(E, sim, g0, g1, s_xstk);
+}
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_exact_cached(EngDev E, int sim, int g0, int g1) {
+    __shared__ u64 s_xstk[EXACT_STK_WORDS];
+    step_grp<BACKUP, SELECT, false, false, true, true>(E, sim, g0, g1, s_xstk);
+}
 
 // One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
 // SELECT of kt walkers.  Lane j of the game's group owns walker j's pending words (loaded / stored coalesced, handed round by
@@ -1821,6 +1861,8 @@ __global__ void k_move(EngDev E, int g0, int g1) {
     E.root_p1[g] = b.p1; E.root_m1[g] = b.m1; E.root_player[g] = (int8_t)b.player;
     E.root[g] = chosen;
     pool[chosen].parent = -1;  // mcts.py:121-123
+    // az_engine_set_exact_endgame: a solved node that becomes the root is an unevaluated, unexpanded root again (it keeps N and Q)
+    if (pool[chosen].flags & F_SOLVED) pool[chosen].flags &= (uint8_t)~(F_TERMINAL | F_SOLVED);
     E.ply[g] = ply + 1;
     atomicAdd(&E.ctr[CTR_PLIES], 1ULL);
     if (E.cap_nfast > 0) atomicAdd(&E.ctr[fast ? CTR_FAST_PLIES : CTR_FULL_PLIES], 1ULL);
@@ -1935,6 +1977,7 @@ __global__ void k_apply_moves(EngDev E, const int *actions, int n, int *status) 
             if (pool[pool[root].first + i].act == a) chosen = pool[root].first + i;
     if (chosen < 0) { chosen = 0; store_node(pool, fresh_node(0, -1, 0.0, 0)); }  // mcts.py:124-125
     pool[chosen].parent = -1;
+    if (pool[chosen].flags & F_SOLVED) pool[chosen].flags &= (uint8_t)~(F_TERMINAL | F_SOLVED);  // as k_move: a solved node kept as the root
     az_play(gd, b, a);
     E.root_p1[g] = b.p1; E.root_m1[g] = b.m1; E.root_player[g] = (int8_t)b.player;
     E.root[g] = chosen;
@@ -2324,6 +2367,10 @@ struct az_engine {
     u32 *ec_serial = nullptr;
     int *ec_claim = nullptr, *ec_hits = nullptr;
     bool graphs_ec = false;
+    // az_engine_set_exact_endgame: the per-slot counts of solved leaves and solver positions, [G] each, allocated when the mode first
+    // goes on; in force (d.x_solved == exact_solved, d.exact_max > 0) only while it is on, else d.x_solved is null
+    int *exact_solved = nullptr;
+    unsigned long long *exact_nodes = nullptr, *exact_sums = nullptr;  // exact_sums [2]: where k_exact_stats leaves the two totals
     int groups_req = 0;
     bool groups_env = false;
     hipStream_t gstream[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2425,6 +2472,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.kforced = 0.0; d.fpicks = nullptr;
     d.ec_hdr = nullptr; d.ec_pay = nullptr; d.ec_serial = nullptr; d.ec_claim = nullptr; d.ec_hits = nullptr;
     d.ec_mask = 0; d.ec_limit = 0; d.ec_stride = 0;
+    d.exact_max = 0; d.x_solved = nullptr; d.x_nodes = nullptr;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2547,7 +2595,7 @@ static int forward(az_engine *e, const Chain &c, const int *cnt, int cap, int st
     return az_sym_reduce(&d.gd, e->sym_mask, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
 }
 
-static SearchMode search_mode(const EngDev &d) { return SearchMode{d.rollout != 0, d.gm, d.K, d.nval != nullptr, d.budget != nullptr, d.kforced > 0.0}; }
+static SearchMode search_mode(const EngDev &d) { return SearchMode{d.rollout != 0, d.gm, d.K, d.nval != nullptr, d.budget != nullptr, d.kforced > 0.0, d.exact_max}; }
 
 // The one place that names the step kernels: launch `a` of the plan on chain c.  Each family is instantiated for three (backup, select)
 // pairs -- the first step, the later ones, the last backup; never <false, false> -- and the two Gumbel families for `full` on and off.
@@ -2574,6 +2622,10 @@ static void launch_step_as(const SearchPlan &p, const Chain &c, int n_sim, const
         case SF_STEP_CAP_FORCED:
             if (d.ec_hdr) hipLaunchKernelGGL((k_step_cached<B, S, true, true>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
             else hipLaunchKernelGGL((k_step_cap_forced<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            break;
+        case SF_STEP_EXACT:
+            if (d.ec_hdr) hipLaunchKernelGGL((k_step_exact_cached<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step_exact<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
             break;
         case SF_STEP_MULTI: hipLaunchKernelGGL((k_step_multi<B, S>), gg, gb, 0, c.st, d, a.t, a.kb, a.kt); break;
         case SF_STEP_GUMBEL:
@@ -2739,6 +2791,7 @@ static int refuse_beside_cap_or_forced(const az_engine *e, const char *who, cons
     const EngDev &d = e->d;
     AZ_REQUIRE(d.cap_nfast == 0, AZ_EINVAL, "%s: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served %s only; switch it off first", who, d.cap_nfast, where);
     AZ_REQUIRE(d.kforced == 0.0, AZ_EINVAL, "%s: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served %s only; switch them off first", who, d.kforced, where);
+    AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "%s: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and are served %s only; switch them off first", who, d.exact_max, where);
     return AZ_OK;
 }
 
@@ -3556,6 +3609,7 @@ extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_
         AZ_REQUIRE(p_full > 0.0 && p_full <= 1.0, AZ_EINVAL, "az_engine_set_playout_cap: p_full must be in (0, 1], got %g", p_full);
         const char *why = beyond_plain_search(e);
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_playout_cap: the playout cap is not served for %s", why);
+        AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "az_engine_set_playout_cap: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and do not combine with the playout cap; switch them off first", d.exact_max);
         if (n_fast == d.cap_nfast && p_full == d.cap_pfull) return AZ_OK;
     }
     AZ_TRY(enter(e));
@@ -3591,6 +3645,7 @@ extern "C" int az_engine_set_forced_playouts(az_engine *e, double k) {
     if (k > 0.0) {
         const char *why = beyond_plain_search(e);
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_forced_playouts: forced playouts are not served for %s", why);
+        AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "az_engine_set_forced_playouts: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and do not combine with forced playouts; switch them off first", d.exact_max);
     }
     if (k == d.kforced) return AZ_OK;
     AZ_TRY(enter(e));
@@ -3613,6 +3668,76 @@ extern "C" int az_engine_forced_playouts_stats(az_engine *e, int64_t *forced_pic
     AZ_TRY(fetch_counters(e));
     *forced_picks = (int64_t)e->h_ctr[CTR_FORCED_PICKS];
     *pruned_playouts = (int64_t)e->h_ctr[CTR_PRUNED];
+    return AZ_OK;
+}
+
+// ---- exact endgames (k_step_exact, az_solve.h) ------------------------------------------------------------------
+// the slots' own counts, summed: one block, the sums in out[0] (solved leaves) and out[1] (solver positions)
+__global__ __launch_bounds__(256) void k_exact_stats(EngDev E, unsigned long long *out) {
+    __shared__ unsigned long long s_sum[2];
+    if (threadIdx.x == 0) { s_sum[0] = 0; s_sum[1] = 0; }
+    __syncthreads();
+    unsigned long long a = 0, b = 0;
+    for (int g = threadIdx.x; g < E.G; g += blockDim.x) { a += (unsigned long long)E.x_solved[g]; b += E.x_nodes[g]; }
+    if (a) atomicAdd(&s_sum[0], a);
+    if (b) atomicAdd(&s_sum[1], b);
+    __syncthreads();
+    if (threadIdx.x == 0) { out[0] = s_sum[0]; out[1] = s_sum[1]; }
+}
+
+extern "C" int az_engine_set_exact_endgame(az_engine *e, int32_t max_empties) {
+    AZ_SETTER(e, "az_engine_set_exact_endgame");
+    EngDev &d = e->d;
+    AZ_REQUIRE(exact_endgame_ok(max_empties), AZ_EINVAL, "az_engine_set_exact_endgame: max_empties must be in [0, %d] (0 = off), got %d", AZ_EXACT_MAX_EMPTIES, max_empties);
+    if (max_empties > 0) {
+        const char *why = exact_endgame_refusal(e->cfg.evaluator, e->sym_mask != 0, e->symr_mask != 0, e->leaf_batch, d.gm, d.cap_nfast > 0, d.kforced > 0.0);
+        AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_exact_endgame: exact endgames are not served for %s", why);
+    }
+    if (max_empties == d.exact_max) return AZ_OK;
+    AZ_USABLE(e, "az_engine_set_exact_endgame");
+    AZ_TRY(enter(e));
+    {   // the leaves of a searched tree were classified under the old value: as az_engine_set_gumbel_full, fresh roots only
+        int n = 0;
+        AZ_HIP(hipMemsetAsync(e->scr_a, 0, sizeof(int), e->stream));
+        hipLaunchKernelGGL(k_count_evaluated_roots, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, e->scr_a);
+        AZ_HIP(hipGetLastError());
+        AZ_HIP(hipMemcpyAsync(&n, e->scr_a, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        AZ_HIP(hipStreamSynchronize(e->stream));
+        AZ_REQUIRE(n == 0, AZ_ESTATE, "az_engine_set_exact_endgame: max_empties would change from %d to %d while %d active slot(s) hold searched trees; "
+                   "start the trees afresh first (az_engine_set_roots / az_engine_run; Python: set_roots, reset)", d.exact_max, max_empties, n);
+    }
+    if (max_empties > 0 && !e->exact_solved) {
+        AZ_TRY(dev_alloc(e, &e->exact_solved, (size_t)d.G));
+        AZ_TRY(dev_alloc(e, &e->exact_nodes, (size_t)d.G));
+        AZ_TRY(dev_alloc(e, &e->exact_sums, 2));
+    }
+    // counts of an earlier spell of the mode must not show up in this one
+    if (max_empties > 0 && d.exact_max == 0) {
+        AZ_HIP(hipMemsetAsync(e->exact_solved, 0, sizeof(int) * (size_t)d.G, e->stream));
+        AZ_HIP(hipMemsetAsync(e->exact_nodes, 0, sizeof(unsigned long long) * (size_t)d.G, e->stream));
+    }
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    d.exact_max = max_empties;
+    d.x_solved = max_empties > 0 ? e->exact_solved : nullptr;
+    d.x_nodes = max_empties > 0 ? e->exact_nodes : nullptr;
+    // other kernels, and max_empties is a launch argument: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_exact_endgame_stats(az_engine *e, int64_t *solved_leaves, int64_t *solver_nodes) {
+    AZ_REQUIRE(e && solved_leaves && solver_nodes, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_exact_endgame_stats");
+    AZ_USABLE(e, "az_engine_exact_endgame_stats");
+    *solved_leaves = 0; *solver_nodes = 0;
+    if (!e->d.x_solved) return AZ_OK;  // off: both 0
+    AZ_TRY(enter(e));
+    unsigned long long h[2] = {0, 0};
+    hipLaunchKernelGGL(k_exact_stats, dim3(1), dim3(256), 0, e->stream, e->d, e->exact_sums);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipMemcpyAsync(h, e->exact_sums, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    *solved_leaves = (int64_t)h[0]; *solver_nodes = (int64_t)h[1];
     return AZ_OK;
 }
 

@@ -7,6 +7,7 @@
 // algorithmic bytes per position.
 #include "az_device.h"
 #include "az_host.h"
+#include "az_solve.h"
 
 AZ_D BB pack_grid(const GameDesc &gd, const int8_t *g, int player) {
     BB b = {0, 0, player};
@@ -68,6 +69,31 @@ __global__ void k_status(GameDesc gd, const int8_t *grids, const int8_t *players
     if (score) score[i] = b.player * (__popcll(b.p1) - __popcll(b.m1));
 }
 
+// az_solve_batch: one position per 16-lane group, the solver of az_solve.h (the one the engine's exact-endgame leaves go through) at the
+// ABI's empties limit.  64 threads per block keep the frame store at 18 KiB of LDS.  No barrier: a group leaves as a whole.
+#define SOLVE_TPB 64
+__global__ __launch_bounds__(SOLVE_TPB) void k_solve(GameDesc gd, const int8_t *grids, const int8_t *players, long long n, int max_empties,
+                                                     long long budget, int8_t *winner, int *action, long long *nodes) {
+    __shared__ u64 s_stk[AZ_SOLVE_MAX_EMPTIES * AZ_SOLVE_FRAME_WORDS * SOLVE_TPB];
+    const long long i = (long long)blockIdx.x * (SOLVE_TPB / AZ_SOLVE_LPG) + (threadIdx.x / AZ_SOLVE_LPG);
+    const int sub = threadIdx.x & (AZ_SOLVE_LPG - 1);
+    if (i >= n) return;
+    const BB b = pack_grid(gd, grids + i * gd.cells, players[i] > 0 ? 1 : -1);
+    int w = 0, res = AZ_UNSOLVED, a = -1;
+    unsigned long long cnt = 0;
+    if (az_status_grp(gd, b, &w, sub)) {
+        res = w;
+    } else if (__popcll(gd.valid & ~(b.p1 | b.m1)) <= max_empties) {
+        int sw = 0, sa = -1;
+        if (az_solve_grp<AZ_SOLVE_MAX_EMPTIES, SOLVE_TPB>(gd, b, sub, s_stk + threadIdx.x, true, budget, &sw, &sa, &cnt) == AZ_SOLVE_OK) { res = sw; a = sa; }
+    }
+    if (sub == 0) {
+        winner[i] = (int8_t)res;
+        action[i] = a;
+        if (nodes) nodes[i] = (long long)cnt;
+    }
+}
+
 #define AZ_TRY(x) do { int _rc = (x); if (_rc != AZ_OK) return _rc; } while (0)
 
 extern "C" int az_board_legal_batch(int game, int H, int W, const int8_t *d_grids, const int8_t *d_players,
@@ -103,6 +129,24 @@ extern "C" int az_board_status_batch(int game, int H, int W, const int8_t *d_gri
     AZ_REQUIRE(d_grids && d_players && n > 0, AZ_EINVAL, "bad arguments");
     hipLaunchKernelGGL(k_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gd, d_grids, d_players,
                        (long long)n, d_over, d_winner, d_score);
+    AZ_HIP(hipGetLastError());
+    return AZ_OK;
+}
+
+extern "C" int az_solve_batch(int game, int H, int W, const int8_t *d_grids, const int8_t *d_players, int64_t n, int32_t max_empties,
+                              int64_t node_budget, int8_t *d_winner, int32_t *d_action, int64_t *d_nodes, void *stream) {
+    GameDesc gd;
+    AZ_TRY(az_make_game_desc(game, H, W, &gd));
+    AZ_REQUIRE(max_empties >= 1 && max_empties <= AZ_SOLVE_MAX_EMPTIES, AZ_EINVAL, "max_empties must be in [1, %d], got %d", AZ_SOLVE_MAX_EMPTIES,
+               (int)max_empties);
+    AZ_REQUIRE(node_budget >= 0, AZ_EINVAL, "node_budget must be 0 (none) or positive, got %lld", (long long)node_budget);
+    AZ_REQUIRE(n >= 0, AZ_EINVAL, "bad arguments");
+    if (n == 0) return AZ_OK;
+    AZ_REQUIRE(d_grids && d_players && d_winner && d_action, AZ_EINVAL, "bad arguments");
+    const int64_t per_block = SOLVE_TPB / AZ_SOLVE_LPG;
+    AZ_REQUIRE((n + per_block - 1) / per_block <= 0x7fffffffLL, AZ_EINVAL, "n = %lld is more positions than one launch takes", (long long)n);
+    hipLaunchKernelGGL(k_solve, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SOLVE_TPB), 0, (hipStream_t)stream, gd, d_grids,
+                       d_players, (long long)n, (int)max_empties, (long long)node_budget, d_winner, d_action, (long long *)d_nodes);
     AZ_HIP(hipGetLastError());
     return AZ_OK;
 }

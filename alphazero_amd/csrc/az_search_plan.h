@@ -17,13 +17,14 @@ struct SearchMode {
     bool full;     // the Gumbel mode keeps the network's values (az_engine_set_gumbel_full in force)
     bool cap;      // the playout cap's budgets are in force
     bool forced;   // forced playouts are on
+    int exact;     // exact endgames: the empties limit of a solved leaf (az_engine_set_exact_endgame; 0: off)
 };
 
 // the kernel family of a search's lock-steps
-enum SearchFamily { SF_ROLLOUT, SF_STEP, SF_STEP_CAP, SF_STEP_FORCED, SF_STEP_CAP_FORCED, SF_STEP_MULTI, SF_STEP_GUMBEL, SF_STEP_GUMBEL_MULTI };
+enum SearchFamily { SF_ROLLOUT, SF_STEP, SF_STEP_CAP, SF_STEP_FORCED, SF_STEP_CAP_FORCED, SF_STEP_MULTI, SF_STEP_GUMBEL, SF_STEP_GUMBEL_MULTI, SF_STEP_EXACT };
 
 inline const char *search_family_name(SearchFamily f) {
-    static const char *const name[] = {"k_rollout_step", "k_step", "k_step_cap", "k_step_forced", "k_step_cap_forced", "k_step_multi", "k_step_gumbel", "k_step_gumbel_multi"};
+    static const char *const name[] = {"k_rollout_step", "k_step", "k_step_cap", "k_step_forced", "k_step_cap_forced", "k_step_multi", "k_step_gumbel", "k_step_gumbel_multi", "k_step_exact"};
     return name[f];
 }
 
@@ -68,6 +69,7 @@ inline SearchPlan plan_search(const SearchMode &m, int n_sim) {
     else if (m.gm > 0) p.family = SF_STEP_GUMBEL;
     else if (m.forced) p.family = m.cap ? SF_STEP_CAP_FORCED : SF_STEP_FORCED;
     else if (m.cap) p.family = SF_STEP_CAP;  // a slot past its budget idles: no walk, no row
+    else if (m.exact > 0) p.family = SF_STEP_EXACT;  // the plain search alone (exact_endgame_refusal): a late leaf is solved, not evaluated
     p.launches = p.L + 1;
     return p;
 }
@@ -182,7 +184,25 @@ inline bool eval_cache_in_force(int request, int evaluator, int game, int H, int
     return request == AZ_EVAL_CACHE_ON || eval_cache_auto(evaluator, game, H, W, G);
 }
 
+// ---- exact endgames (az_engine_set_exact_endgame) -----------------------------------------------------------------
+// (AZ_EXACT_MAX_EMPTIES, the largest empties limit of a solved leaf, is the frame count of k_step_exact's solver stack: az_solve.h)
+inline bool exact_endgame_ok(int max_empties) { return max_empties >= 0 && max_empties <= AZ_EXACT_MAX_EMPTIES; }
+// Where the mode is served: the plain PUCT search of a network or fake engine, one leaf per slot and lock-step, without the playout cap
+// and forced playouts (the hook is orthogonal to those two, their composed host models are not written).  The mode that refuses, as
+// the setters name it, or null.
+inline const char *exact_endgame_refusal(int evaluator, bool sym, bool sym_random, int leaf_batch, int gm, bool cap, bool forced) {
+    if (evaluator == AZ_EVAL_EXTERNAL) return "an AZ_EVAL_EXTERNAL engine (external evaluator)";
+    if (evaluator == AZ_EVAL_ROLLOUT) return "a rollout engine (AZ_EVAL_ROLLOUT)";
+    if (sym) return "the symmetry ensemble (az_engine_set_symmetry)";
+    if (sym_random) return "the random symmetry mode (az_engine_set_symmetry_random)";
+    if (leaf_batch > 1) return "leaf_batch > 1 (az_engine_set_leaf_batch)";
+    if (gm > 0) return "the Gumbel search (az_engine_set_gumbel)";
+    if (cap) return "the playout cap (az_engine_set_playout_cap)";
+    if (forced) return "forced playouts (az_engine_set_forced_playouts)";
+    return nullptr;
+}
+
 // What a captured search is keyed by.  (What else travels in the launch arguments -- K, m, the playout cap's n_fast and p_full, forced
-// playouts' k, the pools -- drops every graph when it changes: az_engine.hip, drop_graphs.)
+// playouts' k, the empties limit of exact endgames, the pools -- drops every graph when it changes: az_engine.hip, drop_graphs.)
 typedef std::tuple<int, bool, int, int, int, int> SearchKey;
 inline SearchKey search_key(const SearchPlan &p, int n_sim, int cap, int g0, int g1) { return SearchKey((int)p.family, p.full, n_sim, cap, g0, g1); }

@@ -79,6 +79,21 @@ def status_batch(game_id, H, W, grids, players):
     return over, win, score
 
 
+def solve_batch(game_id, H, W, grids, players, max_empties=_lib.SOLVE_MAX_EMPTIES, node_budget=0, with_nodes=False):
+    """Exact endgames for n positions (az_solve_batch): (winner int8, action int32[, nodes int64]) device tensors.  winner = the
+    outcome under optimal play as an absolute player id, action = the lowest action index that keeps it; a finished game reports its
+    winner and action -1; a position with more than max_empties empty cells, or one that spent node_budget, reports
+    (_lib.UNSOLVED, -1)."""
+    n = players.numel()
+    assert grids.dtype == torch.int8 and players.dtype == torch.int8 and grids.is_cuda and grids.is_contiguous()
+    win = torch.empty(n, dtype=torch.int8, device=grids.device)
+    act = torch.empty(n, dtype=torch.int32, device=grids.device)
+    nodes = torch.empty(n, dtype=torch.int64, device=grids.device) if with_nodes else None
+    check(lib().az_solve_batch(game_id, H, W, grids.data_ptr(), players.data_ptr(), n, int(max_empties), int(node_budget), win.data_ptr(),
+                               act.data_ptr(), nodes.data_ptr() if with_nodes else None, _stream_ptr()))
+    return (win, act, nodes) if with_nodes else (win, act)
+
+
 def augment_samples(game_id, H, W, samples):
     """symmetry twins of the samples with move_idx >= 2, in the reference's order (trainer.py:275-284).
     samples: dict of CUDA tensors (state int8 [S,H,W], pi float32 [S,A], z int8 [S], meta int32 [S,4]).
@@ -429,6 +444,23 @@ class SelfPlayEngine:
         picks, pruned = C.c_int64(), C.c_int64()
         check(lib().az_engine_forced_playouts_stats(self.h, C.byref(picks), C.byref(pruned)))
         return {"forced_picks": picks.value, "pruned_playouts": pruned.value}
+
+    def set_exact_endgame(self, max_empties):
+        """exact endgames (az_engine_set_exact_endgame): None = off, or E in [1, 10] -- a leaf of the search with at
+        most E empty cells is solved by alpha-beta on the device and becomes a terminal node whose winner is the outcome under
+        optimal play; it takes no row of the network batch.  Plain search of EVAL_NET / EVAL_FAKE engines (one leaf per lock-step, no
+        playout cap, no forced playouts); any other mode is a ValueError that names it.  A change over searched trees is refused:
+        set_roots() / run() first."""
+        from .endgame import parse
+        e = parse(max_empties)
+        check(lib().az_engine_set_exact_endgame(self.h, 0 if e is None else e))
+
+    def exact_endgame_stats(self):
+        """{"solved_leaves", "solver_nodes"}: the leaves solved (each node once) and the positions the solver entered for them since
+        the last run() / set_roots(); both 0 with the mode off"""
+        solved, nodes = C.c_int64(), C.c_int64()
+        check(lib().az_engine_exact_endgame_stats(self.h, C.byref(solved), C.byref(nodes)))
+        return {"solved_leaves": solved.value, "solver_nodes": nodes.value}
 
     def set_eval_cache(self, mode=None, capacity=0, stone_limit=0):
         """the leaf evaluation cache of run() (az_engine_set_eval_cache): each slot group keeps the network's

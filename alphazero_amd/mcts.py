@@ -56,6 +56,7 @@ def check_symmetry(symmetry, nn):
 MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
 
 from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full  # noqa: E402  (the Gumbel root search's spec and refusals)
+from .endgame import check_exact_endgame  # noqa: E402  (exact endgames' spec and refusals)
 
 
 def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
@@ -87,7 +88,7 @@ def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
 
 class MCT:
     def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None,
-                 leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False):
+                 leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None):
         self.n_rollouts = 0
         self.simulation_time = 0
         self.eval_method = TreeEval.to_dict()["rollout" if eval_method is None else eval_method]
@@ -127,6 +128,11 @@ class MCT:
         self.gumbel_full = gumbel_full
         self._engine_gf = False       # the gumbel_full the engine is set to
         check_gumbel_full(gumbel_full, gumbel)
+        # exact endgames (alphazero_amd.endgame: None = off, or E in 1..10): a leaf with at most E empty cells is solved, not evaluated;
+        # the plain PUCT search on HIP-routed networks only
+        self.exact_endgame = exact_endgame
+        self._engine_exact = None     # the E the engine is set to
+        check_exact_endgame(exact_endgame, self._nn, symmetry, leaf_batch, gumbel, self.eval_method == TreeEval.NEURAL)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -140,6 +146,7 @@ class MCT:
         check_symmetry(self.symmetry, nn)
         check_leaf_batch(self.leaf_batch, nn, self.symmetry)
         check_gumbel(self.gumbel, nn, self.leaf_batch)
+        check_exact_endgame(self.exact_endgame, nn, self.symmetry, self.leaf_batch, self.gumbel)
         self._nn = nn
         self._hipnet = None
         self._evaluator = None
@@ -269,6 +276,13 @@ class MCT:
             self._engine_gumbel = None
             self._engine_gb = 1
             self._engine_gf = False
+            self._engine_exact = None
+        ex = check_exact_endgame(self.exact_endgame, self._nn if neural else None, self.symmetry, self.leaf_batch, self.gumbel, neural)
+        if self._engine_exact is not None and ex is None:  # off before a mode it excludes may come on
+            self._root_key = None  # over a fresh tree only: the kept one was searched under the old value
+            self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8))
+            self._engine.set_exact_endgame(None)
+            self._engine_exact = None
         lb = check_leaf_batch(self.leaf_batch, self._nn if neural else None, self.symmetry, neural)
         if self._engine_lb != lb:
             self._engine.set_leaf_batch(lb)
@@ -286,11 +300,16 @@ class MCT:
             self._engine.set_gumbel_batch(gb)
             self._engine_gb = gb
         key = (board.grid.astype(np.int8).tobytes(), int(board.player))
+        if self._engine_exact != ex:
+            self._root_key = None  # the engine refuses a change over a searched tree: start it afresh
         if key != self._root_key:  # tree restarted from an unexplored state (mcts.py:124-125, 231-233)
             self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8),
                                    game_ids=np.array([np.random.randint(0, 2**31 - 1)], np.uint32))
             self._root_key = key
             self._used_bound = 1  # a fresh tree: the root
+        if self._engine_exact != ex:
+            self._engine.set_exact_endgame(ex)
+            self._engine_exact = ex
         if self._engine_gf != gf:  # on after set_roots: a fresh tree holds no node evaluated without its value; a kept one is refused
             self._engine.set_gumbel_full(gf)
             self._engine_gf = gf

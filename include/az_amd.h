@@ -69,6 +69,27 @@ int az_board_play_batch(int game, int H, int W, const int8_t *d_grids, const int
 int az_board_status_batch(int game, int H, int W, const int8_t *d_grids, const int8_t *d_players, int64_t n,
                           uint8_t *d_over, int8_t *d_winner, int32_t *d_score, void *stream);
 
+/* ---- exact endgames ---------------------------------------------------------------------------
+ * The outcome of n positions under optimal play by both sides (the reference has no counterpart: its players ask the network on
+ * every position).  A position is a candidate when empties = popcount(valid cells & ~(p1 | m1)) <= max_empties.
+ *   a finished game          d_winner = the winner as az_board_status_batch reports it, d_action = -1
+ *   a solved position        d_winner = the outcome, an absolute player id in {-1, 0, +1}; d_action = the LOWEST action index whose
+ *                            successor has that outcome -- a property of the position, not of the search order -- and Othello's pass
+ *                            action H*W where the side to move must pass
+ *   anything else            d_winner = AZ_UNSOLVED, d_action = -1: a position above the limit, or one for which a lane of the
+ *                            solver entered node_budget positions (0: no budget; what counts is implementation-defined) or reached
+ *                            the solver's iteration ceiling.  Never an error.
+ * d_nodes (int64 [n], may be NULL) = positions the solver entered, informational.  One 16-lane group per position: the legal moves
+ * are dealt over the lanes, each solved by an iterative alpha-beta on the window [-1, +1] with its stack in LDS (az_solve.h), the
+ * device function a search with exact endgames sends its late leaves through.
+ * AZ_EINVAL: max_empties outside [1, AZ_SOLVE_MAX_EMPTIES], a negative node_budget or n, a null d_grids / d_players / d_winner /
+ * d_action with n > 0, a game or board az_board_status_batch refuses. */
+#define AZ_SOLVE_MAX_EMPTIES 12
+#define AZ_UNSOLVED 2
+int az_solve_batch(int game, int H, int W, const int8_t *d_grids, const int8_t *d_players, int64_t n,
+                   int32_t max_empties, int64_t node_budget,
+                   int8_t *d_winner, int32_t *d_action, int64_t *d_nodes, void *stream);
+
 /* ---- policy-value network (K5/K6) ------------------------------------------------------------
  * replaces OthelloNet / Connect4Net / TicTacToeNet .forward + PolicyValueNetwork.predict
  * (othello.py:341-382, connect4.py:370-412, tictactoe.py:289-316, base.py:350-355), eval mode. */
@@ -548,6 +569,41 @@ int az_forced_prune(int32_t n_children, const int32_t *N, const double *Q, const
 #define AZ_EVAL_CACHE_ON 1
 int az_engine_set_eval_cache(az_engine *e, int32_t mode, int32_t capacity, int32_t stone_limit);
 int az_engine_eval_cache_stats(az_engine *e, int32_t *in_force, int64_t *hits);
+
+/* ---- exact endgames in the search -------------------------------------------------------------------------
+ * Near the end of a game the outcome of a position is a short alpha-beta away (az_solve_batch above): with the mode on the search
+ * backs a late leaf up with that outcome instead of the network's guess, and the leaf takes no row of the network batch.  The
+ * reference has no counterpart.  Opt-in: max_empties = 0 (the default) is off, when no launch, kernel, allocation or output bit
+ * differs from an engine that never had it on; 1 .. AZ_EXACT_MAX_EMPTIES switches it on.  Contract:
+ *   solved leaf   the leaf a simulation's walk ends on (depth >= 1) whose game is not over (az_status is tested first: a finished
+ *                 game is never marked solved) and which has empties = popcount(valid cells & ~(p1 | m1)) <= max_empties.  Its
+ *                 outcome w under optimal play by both sides is computed on the spot by az_solve.h's solver, without a budget:
+ *                 every such leaf is solved.  The node is marked as a terminal node with winner w plus the flag bit F_SOLVED,
+ *                 and from then on it IS a terminal node: no batch row, no input written, never children, backed up with
+ *                 outcome = w now and on every later visit, not counted in net_evals.  (A solve that reached the solver's
+ *                 iteration ceiling raises the engine's internal-error flag and leaves the leaf to the network.)
+ *   solved root   a solved node that becomes a root -- the played move leads to it (az_engine_run, az_engine_advance), or
+ *                 az_engine_play keeps it -- loses the terminal and the solved flag and keeps its N and Q: an unevaluated,
+ *                 unexpanded root.  The root-prior pass evaluates it (the value discarded as ever), and its children are solved in
+ *                 turn as the search reaches them.  The clearing is keyed on F_SOLVED: trees of an engine with the mode off never
+ *                 take the branch.
+ *   nothing else  PUCT, root noise, temperature, the move draw, the samples and z stay as they are.  A game depends on (seed, game
+ *                 id, max_empties) only, never on the slot, the slot group or the batch.
+ *   counters      az_engine_exact_endgame_stats: solved_leaves = the leaves solved (each node once: first-time solves;
+ *                 deterministic), solver_nodes = the positions the solver entered for them (informational: it depends on where
+ *                 the lanes of a group were stopped).  Since the last az_engine_run / az_engine_set_roots; both 0 with the mode
+ *                 off.  az_engine_stats is unchanged.
+ * Served: the plain PUCT search of AZ_EVAL_NET / AZ_EVAL_FAKE engines through az_engine_run (1, 2 or 4 slot groups),
+ * az_engine_search, _search_begin / _end, az_engine_advance and az_engine_root_readout, with the leaf evaluation cache in force or
+ * not (a leaf is tested for solving before the cache is consulted; a solved leaf is neither looked up nor inserted).  Not served
+ * (AZ_EINVAL naming the mode; and while exact endgames are on the setters of those modes refuse, naming exact endgames):
+ * leaf_batch > 1, the Gumbel search, either symmetry mode, the playout cap, forced playouts, AZ_EVAL_ROLLOUT, AZ_EVAL_EXTERNAL.
+ * AZ_EINVAL also: max_empties outside [0, AZ_EXACT_MAX_EMPTIES].  AZ_ESTATE while a search is open, and for a change of the value
+ * while an active slot holds a searched tree (its leaves were classified under the old value): start the trees afresh first
+ * (az_engine_set_roots, az_engine_run).  A change drops the cached search graphs. */
+#define AZ_EXACT_MAX_EMPTIES 10
+int az_engine_set_exact_endgame(az_engine *e, int32_t max_empties);
+int az_engine_exact_endgame_stats(az_engine *e, int64_t *solved_leaves, int64_t *solver_nodes);
 
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
