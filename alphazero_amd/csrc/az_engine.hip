@@ -15,6 +15,9 @@
 // (By a measured rule: az_engine_set_eval_cache.  The games of an az_engine_run wave start from one position under one set of weights,
 // so a slot group keeps the network's outputs by exact position -- ec_lookup_grp, leaf_output -- and a leaf found there takes no batch
 // row; the bits a slot backs up are the ones the forward would have written.)
+// (Opt-in, default off: az_engine_set_proof_backup backs proven wins, losses and draws up the tree -- MCTS-Solver: a node is proven as
+// soon as its children decide it, walks stop on proven nodes, selection and the policy target respect the proofs -- k_step_proof below,
+// propagate_proofs_grp, proof_mode / proof_count in move_policy.)
 //
 // HBM layout
 //   boards   : 2 x u64 bitboards + int8 side-to-move per slot (root and current leaf), SoA over slots
@@ -51,6 +54,7 @@
 #define F_NOISED 8
 #define F_EVALUATED 16
 #define F_SOLVED 32  // az_engine_set_exact_endgame: with F_TERMINAL, the winner was computed by the solver, not read off a finished board
+#define F_PROVEN 64  // az_engine_set_proof_backup: an expanded node whose children decide it; `win` holds the outcome
 
 #define LS_NONE 0
 #define LS_EVAL 1
@@ -154,6 +158,10 @@ struct EngDev {
     int exact_max;
     int *x_solved;
     unsigned long long *x_nodes;
+    // az_engine_set_proof_backup (k_step_proof, move_policy): pf [3][G] = per slot the interior nodes marked F_PROVEN, the walks that
+    // ended on such a node and the plies whose policy counts the proofs changed, since the last k_reset_all (the slot's own words,
+    // summed when the stats are read).  Null unless the mode is on: then no kernel touches them.  (Last: the fields above keep their place.)
+    int *pf;
 };
 // tag = ec_tag(hash, the claimer's stamp), 0 = empty: claimed by one device-scope compare-and-swap, never rewritten within a run; the
 // key is written by the claimer in the same kernel, the payload in the group's next one
@@ -294,6 +302,12 @@ AZ_D int create_children_grp(const EngDev &E, int g, Node *pool, int fc, int nod
     return k;
 }
 
+// az_engine_set_proof_backup: the proven outcome of a node by its visit count and last word -- a finished or solved position
+// (F_TERMINAL) or an interior node its children decide (F_PROVEN), once it has been backed up -- or AZ_UNSOLVED.
+AZ_D int proven_outcome(int N, u32 tail) {
+    return (N > 0 && ((tail >> 16) & (F_TERMINAL | F_PROVEN))) ? (int)(int8_t)(tail >> 24) : AZ_UNSOLVED;
+}
+
 // The children one lane scores, one per round of 16: [r] is child r * LPG + sub of the parent, its score and what the walk needs of
 // its header (N, first child, last word).
 struct Scored {
@@ -319,14 +333,19 @@ AZ_D int pick4(int v0, int v1, int v2, int v3, int r) { return r == 0 ? v0 : (r 
 // take part in the ballot; when none of them holds the maximum, `none_err` (0: nothing) is raised.  `gid` is read only where a tie is
 // drawn.  The chosen child's header is handed back by shuffle from the lane that scored it (no second memory trip); returns the
 // child's index among the parent's children.  DRAW false: ties go to the lowest index whatever tie_mode says, no Philox draw.
-template <bool DRAW = true>
+// MASKED (az_engine_set_proof_backup): bit r of `skip` takes this lane's child of round r out of the ballot (its key is -inf already,
+// so it does not set the maximum either; a voter mask, not a key: absent lanes carry -inf too and would win a ballot at -inf).
+template <bool DRAW = true, bool MASKED = false>
 AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int depth, const Scored &s, int nvote, int none_err,
-                        int sub, Node &chosen) {
+                        int sub, Node &chosen, int skip = 0) {
     double best = grp_max(fmax(fmax(s.key[0], s.key[1]), fmax(s.key[2], s.key[3])));
     u32 mask[4];
     int cnt = 0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { mask[r] = grp_ballot((r * LPG + sub) < nvote && s.key[r] == best); cnt += __popc(mask[r]); }
+    for (int r = 0; r < 4; ++r) {
+        mask[r] = grp_ballot((r * LPG + sub) < nvote && (!MASKED || !((skip >> r) & 1)) && s.key[r] == best);
+        cnt += __popc(mask[r]);
+    }
     if (none_err && cnt == 0 && sub == 0) atomicOr(E.err, none_err);
     int k = 0;
     if (DRAW && E.tie_mode == AZ_TIE_RANDOM && cnt > 1) {  // with a single maximum the draw cannot change the result
@@ -414,9 +433,12 @@ AZ_HD int forced_pruned(int n, double q, double p, int root_n, double sq, double
 // ---------------------------------------------------------------------------------------------
 // FORCED (az_engine_set_forced_playouts; the k_step_forced kernels only): with kf > 0 -- the root of a forced ply -- a child that
 // forced_playout names takes the key +inf, and *forced_pick is raised when there was one; everything behind the keys is unchanged.
-template <bool FORCED = false>
+// PROOF (az_engine_set_proof_backup; the k_step_proof kernels only): `mover` = the player to move at the parent.  A
+// child proven as a loss for the mover is no candidate -- key -inf and no vote -- unless every child is one (a root only: a node below
+// it whose children are all proven is proven itself and stops the walk); at the root a child proven as the mover's win takes +inf.
+template <bool FORCED = false, bool PROOF = false>
 AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
-                           int ply, int sim, int depth, int sub, Node &chosen, double kf = 0.0, bool *forced_pick = nullptr) {
+                           int ply, int sim, int depth, int sub, Node &chosen, double kf = 0.0, bool *forced_pick = nullptr, int mover = 0) {
     const int fc = parent.first;
     int vp = 0, vc[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -432,6 +454,8 @@ AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node 
     const double sq = sqrt((double)(parent.N + vp));
     Scored s;
     bool forced = false;
+    int loss = 0;       // PROOF: bit r = this lane's child of round r is a proven loss for the mover
+    bool live = false;  // PROOF: this lane holds a child that is not
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         Node c;
@@ -439,9 +463,21 @@ AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node 
             const double q = vc[r] == 0 ? c.Q : ((double)c.N * c.Q - (double)vc[r]) / (double)(c.N + vc[r]);
             s.key[r] = q + (c.P * sq) / (double)(1 + c.N + vc[r]);
             if (FORCED && kf > 0.0 && forced_playout(c.N, c.P, parent.N + vp, kf)) { s.key[r] = __builtin_inf(); forced = true; }
+            if (PROOF) {
+                const int cw = proven_outcome(s.N[r], s.tail[r]);
+                if (cw == -mover) loss |= 1 << r; else live = true;
+                if (depth == 0 && cw == mover) s.key[r] = __builtin_inf();
+            }
         }
     }
     if (FORCED && kf > 0.0 && grp_ballot(forced) != 0) *forced_pick = true;  // kf is uniform over the group
+    if (PROOF) {
+        if (grp_ballot(live) == 0) loss = 0;  // every child loses: all of them stay candidates
+#pragma unroll
+        for (int r = 0; r < 4; ++r) if ((loss >> r) & 1) s.key[r] = -__builtin_inf();
+        // NaN scores stay an error: they equal no maximum, and a group whose voters all hold NaN finds -inf without a voter
+        return fc + choose_max_grp<true, true>(E, E.game_id[g], ply, sim, depth, s, 4 * LPG, ERR_INTERNAL, sub, chosen, loss);
+    }
     // every lane votes, and NaN scores (a diverged network) are an error: no key equals the maximum
     return fc + choose_max_grp(E, E.game_id[g], ply, sim, depth, s, 4 * LPG, ERR_INTERNAL, sub, chosen);
 }
@@ -461,11 +497,15 @@ AZ_D int pick_child_gumbel_grp(const EngDev &E, int g, const Node *pool, const N
 // select_node's descent (mcts.py:127-171) of walker j, from wk (the root, or wherever wk stands) to its leaf.  GUMBEL: the children
 // are scored by pick_child_gumbel_grp instead of PUCT (the full Gumbel kernels only; every other kernel takes the default).
 // FORCED: the selection at depth 0 applies the forced-playout rule with kf (0: not a forced ply); below the root nothing changes.
-template <bool GUMBEL = false, bool FORCED = false>
+// PROOF (az_engine_set_proof_backup): below the root the walk stops on an F_PROVEN node as on a terminal one, and the scorer prunes
+// by the proofs; the mover at depth d is the root's player times (-1)^d (a pass is an action: the side to move alternates strictly).
+template <bool GUMBEL = false, bool FORCED = false, bool PROOF = false>
 AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], int j, int ply, int sim, int sub, Walk &wk,
                    double kf = 0.0, bool *forced_pick = nullptr) {
+    const int root_player = wk.b.player;  // PROOF: wk stands on the root when the step kernel calls
     for (;;) {
         bool fresh = false;
+        if (PROOF && wk.plen > 1 && (wk.cur.flags & F_PROVEN)) break;
         if (!(wk.cur.flags & F_EXPANDED)) {
             if (wk.cur.flags & F_TERMINAL) break;  // mcts.py:146-147
             if (!(wk.cur.flags & F_EVALUATED)) { wk.bad = true; break; }
@@ -475,8 +515,9 @@ AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], 
         }
         Node ch;
         const int c = GUMBEL ? pick_child_gumbel_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch)
-                             : pick_child_vl_grp<FORCED>(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch,
-                                                         FORCED && wk.plen == 1 ? kf : 0.0, forced_pick);
+                             : pick_child_vl_grp<FORCED, PROOF>(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch,
+                                                                FORCED && wk.plen == 1 ? kf : 0.0, forced_pick,
+                                                                PROOF ? (((wk.plen - 1) & 1) ? -root_player : root_player) : 0);
         wk.node = c; wk.cur = ch;
         if (sub == wk.plen) wk.my_path = c;
         ++wk.plen;
@@ -487,12 +528,16 @@ AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], 
 
 // What the walk ended on: LS_NONE (an internal error, reported), LS_TERM (w = the winner; a node found terminal now is marked)
 // or LS_EVAL (the leaf wants a row of the network batch).
-AZ_D int classify_leaf_grp(const EngDev &E, Node *pool, const Walk &wk, int &w, int sub) {
+// PROOF (az_engine_set_proof_backup): a walk that ended below the root on an F_PROVEN node is LS_TERM with the node's outcome, and
+// *proof_stop is raised.
+template <bool PROOF = false>
+AZ_D int classify_leaf_grp(const EngDev &E, Node *pool, const Walk &wk, int &w, int sub, bool *proof_stop = nullptr) {
     if (wk.bad) {
         if (sub == 0) atomicOr(E.err, ERR_INTERNAL);
         return LS_NONE;
     }
     if (wk.cur.flags & F_TERMINAL) { w = wk.cur.win; return LS_TERM; }
+    if (PROOF && wk.plen > 1 && (wk.cur.flags & F_PROVEN)) { w = wk.cur.win; *proof_stop = true; return LS_TERM; }
     if (az_status_grp(E.gd, wk.b, &w, sub)) {  // mcts.py:185-186
         if (sub == 0) { pool[wk.node].flags = wk.cur.flags | F_TERMINAL; pool[wk.node].win = (int8_t)w; }
         return LS_TERM;
@@ -665,6 +710,48 @@ AZ_D bool back_propagate_grp(Node *pool, int len, int my_node, Node &mine, int l
     return false;
 }
 
+// az_engine_set_proof_backup: the proofs a backup of a terminal leaf brings about.  From the leaf's parent upward,
+// one group-wide step per level: the node (one address, a broadcast), its children in four rounds of 16, three ballots.  A node of
+// mover m is proven when some child is proven with outcome m (then m), or when every child is proven (0 with a drawn child, else -m);
+// lane 0 marks it and the walk up goes on, the first node the rule does not prove ends it.  my_node = this lane's path node (paths of
+// at most LPG nodes; longer ones chase parents from the leaf, as the backup does).  The loop's condition is uniform over the group.
+// Returns the nodes newly marked; *root_win is set, and true returned in *root_marked, when the root (path position 0) is one of them.
+AZ_D int propagate_proofs_grp(Node *pool, int plen, int my_node, int leaf, int root_player, int sub, bool *root_marked, int *root_win) {
+    // the backup's stores (other lanes: the leaf's first visit among them) must be visible to the loads below
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    int marked = 0;
+    int chase = plen > LPG ? load_node(pool + leaf).parent : -1;
+    for (int pos = plen - 2; pos >= 0; --pos) {
+        const int pn = plen <= LPG ? __shfl(my_node, pos, LPG) : chase;
+        if (pn < 0) break;
+        const Node p = load_node(pool + pn);
+        if (p.nch == 0) break;  // a path node above the leaf always has children
+        const int m = (pos & 1) ? -root_player : root_player;
+        Scored s;
+        bool win = false, open = false, draw = false;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            Node c;
+            if (load_child_grp(pool, p, r, sub, s, c)) {
+                const int cw = proven_outcome(s.N[r], s.tail[r]);
+                win |= cw == m; draw |= cw == 0; open |= cw == AZ_UNSOLVED;
+            }
+        }
+        const bool any_win = grp_ballot(win) != 0, any_open = grp_ballot(open) != 0, any_draw = grp_ballot(draw) != 0;
+        if (!any_win && any_open) break;
+        const int out = any_win ? m : (any_draw ? 0 : -m);
+        if (!(p.flags & F_PROVEN)) {
+            ++marked;
+            if (sub == 0) { pool[pn].flags = p.flags | F_PROVEN; pool[pn].win = (int8_t)out; }
+            if (pos == 0) { *root_marked = true; *root_win = out; }
+            // the mark must be visible to the next level's loads (this node is a child there) and to the SELECT half
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+        chase = p.parent;
+    }
+    return marked;
+}
+
 AZ_D void reset_slot(const EngDev &E, int g, u32 game_id) {
     BB b;
     start_position(E.gd, b);
@@ -691,6 +778,7 @@ __global__ void k_reset_all(EngDev E, u32 first_id, int n_games) {
     if (g >= E.G) return;
     E.pool_sel[g] = 0;
     if (E.x_solved) { E.x_solved[g] = 0; E.x_nodes[g] = 0; }
+    if (E.pf) { E.pf[g] = 0; E.pf[E.G + g] = 0; E.pf[2 * E.G + g] = 0; }
     if (g < n_games) reset_slot(E, g, first_id + (u32)g);
     else { E.active[g] = 0; E.leaf_status[g] = LS_NONE; }
 }
@@ -762,7 +850,10 @@ __device__ unsigned long long az_step_probe[4096 * 8];
 // on the spot (az_solve.h; xstk = the block's frame store in LDS) and becomes a terminal node whose winner is the outcome.  Before the
 // cache is consulted, and before the rows are handed out: the solver holds no barrier and the group leaves it as a whole.  EXACT false
 // is the kernel as it was.
-template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false, bool EXACT = false>
+// PROOF (az_engine_set_proof_backup, k_step_proof): the backup of an LS_TERM leaf is followed by
+// propagate_proofs_grp, the walk and its scorer take the proofs into account, and a walk that ends on an F_PROVEN node is LS_TERM: no
+// row, no solve, no cache lookup.  PROOF false is the kernel as it was.
+template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false, bool EXACT = false, bool PROOF = false>
 AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
@@ -841,6 +932,14 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr
                 // the root itself may be the leaf that just got its children (first visit of an unexpanded root)
                 have_root = (leaf != node) || st != LS_EVAL;
             }
+            if (PROOF && st == LS_TERM) {  // only a terminal leaf's backup can decide a node: the dependent round trips are paid here alone
+                bool root_marked = false;
+                int root_win = 0;
+                const int marked = propagate_proofs_grp(pool, plen_prev, path_prev, leaf, b.player, sub, &root_marked, &root_win);
+                // the forwarded root was read before the walk up: it carries what the propagation has just written
+                if (root_marked && fast && SELECT) { fwd.flags |= F_PROVEN; fwd.win = (int8_t)root_win; }
+                if (marked && sub == 0) E.pf[g] += marked;
+            }
         }
         if (sub == 0) E.leaf_status[g] = LS_NONE;
         // the group's own stores (other lanes) must be visible to the loads below
@@ -858,7 +957,7 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr
     int status = LS_NONE, w = 0;
     Walk wk = {b, Node(), node, 1, sub == 0 ? node : -1, false};
     const bool walks = active && (!CAP || sim < budget);  // uniform over the game's group
-    bool forced_pick = false;
+    bool forced_pick = false, proof_stop = false;
     if (walks) {
         if (have_root) wk.cur = fwd; else wk.cur = load_node(pool + node);
         const bool noise_ply = !CAP || budget == CAP_FULL;  // a fast ply takes no root noise and leaves F_NOISED clear
@@ -870,11 +969,13 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr
         PSTAMP(4)
         const int no_walkers[MLB] = {};  // walker j = 0: nobody walked before it in this lock-step, every virtual count is 0
         if (FORCED) walk_grp<false, true>(E, g, pool, no_walkers, 0, ply, sim, sub, wk, budget == CAP_FULL ? E.kforced : 0.0, &forced_pick);
+        else if (PROOF) walk_grp<false, false, true>(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
         else walk_grp(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
         PSTAMP(5)
         E.path[(size_t)g * LPG + sub] = wk.my_path;
         if (sub == 0) { E.path_len[g] = wk.plen; if (wk.plen > LPG) atomicMax(E.max_path, wk.plen); }
-        status = classify_leaf_grp(E, pool, wk, w, sub);
+        if (PROOF) status = classify_leaf_grp<true>(E, pool, wk, w, sub, &proof_stop);
+        else status = classify_leaf_grp(E, pool, wk, w, sub);
         if (EXACT && status == LS_EVAL && wk.plen > 1 && __popcll(E.gd.valid & ~(wk.b.p1 | wk.b.m1)) <= E.exact_max) {
             int sw = 0, sa = -1;
             unsigned long long cnt = 0;
@@ -904,6 +1005,7 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr
             E.leaf[g] = wk.node; E.leaf_p1[g] = wk.b.p1; E.leaf_m1[g] = wk.b.m1; E.leaf_player[g] = (int8_t)wk.b.player;
             E.leaf_winner[g] = (int8_t)w;
             if (FORCED && forced_pick) E.fpicks[g] = fpicks + 1;
+            if (PROOF && proof_stop) E.pf[E.G + g] += 1;
         }
         E.leaf_status[g] = (int8_t)status;
         if (EC) {
@@ -947,6 +1049,27 @@ template <bool BACKUP, bool SELECT>
 __global__ __launch_bounds__(256) void k_step_exact_cached(EngDev E, int sim, int g0, int g1) {
     __shared__ u64 s_xstk[EXACT_STK_WORDS];
     step_grp<BACKUP, SELECT, false, false, true, true>(E, sim, g0, g1, s_xstk);
+}
+
+// and the plain lock-step with proof backup (az_engine_set_proof_backup), alone, with the cache, with exact endgames, with both: the
+// exact ones carry the solver's LDS as k_step_exact does
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_proof(EngDev E, int sim, int g0, int g1) {
+    step_grp<BACKUP, SELECT, false, false, false, false, true>(E, sim, g0, g1);
+}
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_proof_cached(EngDev E, int sim, int g0, int g1) {
+    step_grp<BACKUP, SELECT, false, false, true, false, true>(E, sim, g0, g1);
+}
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_proof_exact(EngDev E, int sim, int g0, int g1) {
+    __shared__ u64 s_xstk[EXACT_STK_WORDS];
+    step_grp<BACKUP, SELECT, false, false, false, true, true>(E, sim, g0, g1, s_xstk);
+}
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_proof_exact_cached(EngDev E, int sim, int g0, int g1) {
+    __shared__ u64 s_xstk[EXACT_STK_WORDS];
+    step_grp<BACKUP, SELECT, false, false, true, true, true>(E, sim, g0, g1, s_xstk);
 }
 
 // One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
@@ -1750,23 +1873,53 @@ AZ_D double forced_ply_k(const EngDev &E, u32 gid, int ply) {
     return (E.kforced > 0.0 && (E.cap_nfast == 0 || playout_cap_full(E.seed, gid, ply, E.cap_pfull))) ? E.kforced : 0.0;
 }
 
+// az_engine_set_proof_backup: how the proofs among the root's children change the counts move and policy target
+// are made of.  mover = the root's player.  1: some child is a proven win for the mover -- only such children keep their counts;
+// 2: children proven as the mover's loss count 0; 0: the raw counts -- no proven child that matters, every child a proven loss, or
+// (what the search's own pruning all but rules out) no visited child left that is not one.  *changed: some count is not the raw one.
+AZ_D int proof_mode(const Node *pool, int fc, int nc, int mover, bool *changed) {
+    bool any_win = false, any_loss = false, kept = false, cut = false;
+    for (int i = 0; i < nc; ++i) {
+        const int n = pool[fc + i].N, cw = proven_outcome(n, node_tail(pool[fc + i]));
+        any_win |= cw == mover;
+        if (cw == -mover) any_loss = true; else if (n > 0) kept = true;
+        cut |= n > 0 && cw != mover;
+    }
+    const int mode = any_win ? 1 : ((any_loss && kept) ? 2 : 0);
+    *changed = mode == 1 ? cut : mode == 2;
+    return mode;
+}
+AZ_D int proof_count(const Node *pool, int fc, int i, int pmode, int mover) {
+    const int n = pool[fc + i].N;
+    if (pmode == 0) return n;
+    const int cw = proven_outcome(n, node_tail(pool[fc + i]));
+    return pmode == 1 ? (cw == mover ? n : 0) : (cw == -mover ? 0 : n);
+}
+
 // the count the temperature formula takes for child i: the raw N, or on a forced ply (kf > 0) the pruned one (no per-thread array:
-// the second pass over the children computes it again)
-AZ_D int policy_count(const Node *pool, int fc, int i, double kf, int root_n, int cstar, double sq, double star) {
+// the second pass over the children computes it again), or under proof backup proof_count's (the two modes never meet)
+AZ_D int policy_count(const Node *pool, int fc, int i, double kf, int root_n, int cstar, double sq, double star, int pmode = 0, int mover = 0) {
+    if (pmode) return proof_count(pool, fc, i, pmode, mover);
     const int n = pool[fc + i].N;
     if (!(kf > 0.0) || i == cstar) return n;
     return forced_pruned(n, pool[fc + i].Q, pool[fc + i].P, root_n, sq, star, kf);
 }
 
 // kf: forced_ply_k of the ply (0: raw counts, the function as it always was); *pruned (when given): the sum of N - N' over the children.
+// mover: under az_engine_set_proof_backup the root's player (0: the mode is off), the counts are then proof_count's at every
+// temperature, 0 included; *proof_cut (when given): whether the proofs changed a count.
 AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc, double temp, u32 gid, int ply, u64 gmask, float *pi,
-                     double kf = 0.0, int *pruned = nullptr) {
+                     double kf = 0.0, int *pruned = nullptr, int mover = 0, bool *proof_cut = nullptr) {
     if (pruned) *pruned = 0;
+    if (proof_cut) *proof_cut = false;
     if (E.gm > 0) return gumbel_move_policy(E, pool, fc, nc, gmask, gid, ply, E.nval ? nval_of(E, pool) + root : nullptr, pi);
+    bool pcut = false;
+    const int pmode = mover != 0 ? proof_mode(pool, fc, nc, mover, &pcut) : 0;
+    if (proof_cut) *proof_cut = pcut;
     if (temp == 0.0) {  // fair_max by N
         int best = -1, cnt = 0, first = 0;
         for (int i = 0; i < nc; ++i) {
-            int n = pool[fc + i].N;
+            int n = proof_count(pool, fc, i, pmode, mover);
             if (n > best) { best = n; cnt = 1; first = i; } else if (n == best) cnt++;
         }
         int pick = first;
@@ -1774,7 +1927,7 @@ AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc
             Philox4 r = az_philox(E.seed, gid, (u32)ply, 0xFFFFu, AZ_P_TIE_MOVE, 0);
             int k = (int)(((u64)r.x * (u64)cnt) >> 32);
             for (int i = 0; i < nc; ++i)
-                if (pool[fc + i].N == best) { if (k == 0) { pick = i; break; } --k; }
+                if (proof_count(pool, fc, i, pmode, mover) == best) { if (k == 0) { pick = i; break; } --k; }
         }
         if (pi) pi[pool[fc + pick].act] = 1.0f;
         return pick;
@@ -1792,8 +1945,8 @@ AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc
     double sum = 0.0;
     int cut = 0;
     for (int i = 0; i < nc; ++i) {
-        const int ni = policy_count(pool, fc, i, kf, root_n, cstar, sq, star);
-        cut += pool[fc + i].N - ni;
+        const int ni = policy_count(pool, fc, i, kf, root_n, cstar, sq, star, pmode, mover);
+        if (!pmode) cut += pool[fc + i].N - ni;  // forced playouts' own count
         double n = (double)ni;
         sum += (temp == 1.0) ? n : az_det_pow(n, inv_temp);
     }
@@ -1805,7 +1958,7 @@ AZ_D int move_policy(const EngDev &E, const Node *pool, int root, int fc, int nc
     }
     int chosen = 0, last = 0; bool found = false;
     for (int i = 0; i < nc; ++i) {
-        double n = (double)policy_count(pool, fc, i, kf, root_n, cstar, sq, star);
+        double n = (double)policy_count(pool, fc, i, kf, root_n, cstar, sq, star, pmode, mover);
         double p = ((temp == 1.0) ? n : az_det_pow(n, inv_temp)) / sum;
         if (pi) pi[pool[fc + i].act] = (float)p;
         if (p > 0.0) last = i;
@@ -1845,7 +1998,10 @@ __global__ void k_move(EngDev E, int g0, int g1) {
     if (si >= 0) for (int a = 0; a < E.A; ++a) { pi[a] = 0.0f; vis[a] = 0; }
 
     int pruned = 0;  // az_engine_set_forced_playouts: the playouts a forced ply's target lost (0 with the mode off, on a fast ply, at temperature 0)
-    const int chosen = fc + move_policy(E, pool, root, fc, nc, temp, gid, ply, E.gmask[g], pi, fast ? 0.0 : E.kforced, &pruned);
+    bool proof_cut = false;  // az_engine_set_proof_backup: the proofs changed the counts this ply's move and target are made of
+    const int chosen = fc + move_policy(E, pool, root, fc, nc, temp, gid, ply, E.gmask[g], pi, fast ? 0.0 : E.kforced, &pruned,
+                                        E.pf ? b.player : 0, &proof_cut);
+    if (proof_cut) E.pf[2 * E.G + g] += 1;
     E.gmask[g] = 0;  // the candidates belong to the root that is left here
     int action = pool[chosen].act;
     if (si >= 0) {
@@ -2025,7 +2181,8 @@ __global__ void k_player_moves(EngDev E, double temp, int *actions) {
     const Node *pool = pool_of(E, g);
     const int root = E.root[g], fc = pool[root].first, nc = pool[root].nch;
     if (nc == 0 || !(pool[root].flags & F_EXPANDED)) return;
-    actions[g] = pool[fc + move_policy(E, pool, root, fc, nc, temp, E.game_id[g], E.ply[g], E.gmask[g], nullptr, forced_ply_k(E, E.game_id[g], E.ply[g]))].act;
+    actions[g] = pool[fc + move_policy(E, pool, root, fc, nc, temp, E.game_id[g], E.ply[g], E.gmask[g], nullptr, forced_ply_k(E, E.game_id[g], E.ply[g]),
+                                       nullptr, E.pf ? (int)E.root_player[g] : 0)].act;
 }
 
 // Root readout for slots [0, n) in one launch: everything Player.get_move returns (players.py:158-191: the move, get_action_probs,
@@ -2092,7 +2249,8 @@ __global__ __launch_bounds__(256) void k_root_readout(EngDev E, int n, const dou
         if (served && (o.pi || o.action)) {
             const int ply = E.ply[g];
             const double temp = temps ? temps[g] : linear_temp(ply, E.tmax, E.tmin);
-            act = pool[fc + move_policy(E, pool, E.root[g], fc, nc, temp, E.game_id[g], ply, E.gmask[g], o.pi ? o.pi + (size_t)g * A : nullptr, forced_ply_k(E, E.game_id[g], ply))].act;
+            act = pool[fc + move_policy(E, pool, E.root[g], fc, nc, temp, E.game_id[g], ply, E.gmask[g], o.pi ? o.pi + (size_t)g * A : nullptr, forced_ply_k(E, E.game_id[g], ply),
+                                        nullptr, E.pf ? (int)E.root_player[g] : 0)].act;
         }
         if (o.action) o.action[g] = act;
         if (o.root_N) o.root_N[g] = served ? rn.N : 0;
@@ -2371,6 +2529,10 @@ struct az_engine {
     // goes on; in force (d.x_solved == exact_solved, d.exact_max > 0) only while it is on, else d.x_solved is null
     int *exact_solved = nullptr;
     unsigned long long *exact_nodes = nullptr, *exact_sums = nullptr;  // exact_sums [2]: where k_exact_stats leaves the two totals
+    // az_engine_set_proof_backup: the per-slot counter words, [3][G], allocated when the mode first goes on; in force (d.pf == proof_ctr)
+    // only while it is on, else d.pf is null; proof_sums [3]: where k_proof_stats leaves the totals
+    int *proof_ctr = nullptr;
+    unsigned long long *proof_sums = nullptr;
     int groups_req = 0;
     bool groups_env = false;
     hipStream_t gstream[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2473,6 +2635,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.ec_hdr = nullptr; d.ec_pay = nullptr; d.ec_serial = nullptr; d.ec_claim = nullptr; d.ec_hits = nullptr;
     d.ec_mask = 0; d.ec_limit = 0; d.ec_stride = 0;
     d.exact_max = 0; d.x_solved = nullptr; d.x_nodes = nullptr;
+    d.pf = nullptr;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2595,7 +2758,7 @@ static int forward(az_engine *e, const Chain &c, const int *cnt, int cap, int st
     return az_sym_reduce(&d.gd, e->sym_mask, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
 }
 
-static SearchMode search_mode(const EngDev &d) { return SearchMode{d.rollout != 0, d.gm, d.K, d.nval != nullptr, d.budget != nullptr, d.kforced > 0.0, d.exact_max}; }
+static SearchMode search_mode(const EngDev &d) { return SearchMode{d.rollout != 0, d.gm, d.K, d.nval != nullptr, d.budget != nullptr, d.kforced > 0.0, d.exact_max, d.pf != nullptr}; }
 
 // The one place that names the step kernels: launch `a` of the plan on chain c.  Each family is instantiated for three (backup, select)
 // pairs -- the first step, the later ones, the last backup; never <false, false> -- and the two Gumbel families for `full` on and off.
@@ -2626,6 +2789,15 @@ static void launch_step_as(const SearchPlan &p, const Chain &c, int n_sim, const
         case SF_STEP_EXACT:
             if (d.ec_hdr) hipLaunchKernelGGL((k_step_exact_cached<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
             else hipLaunchKernelGGL((k_step_exact<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            break;
+        case SF_STEP_PROOF:
+            if (p.exact) {
+                if (d.ec_hdr) hipLaunchKernelGGL((k_step_proof_exact_cached<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+                else hipLaunchKernelGGL((k_step_proof_exact<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            } else {
+                if (d.ec_hdr) hipLaunchKernelGGL((k_step_proof_cached<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+                else hipLaunchKernelGGL((k_step_proof<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            }
             break;
         case SF_STEP_MULTI: hipLaunchKernelGGL((k_step_multi<B, S>), gg, gb, 0, c.st, d, a.t, a.kb, a.kt); break;
         case SF_STEP_GUMBEL:
@@ -2792,6 +2964,7 @@ static int refuse_beside_cap_or_forced(const az_engine *e, const char *who, cons
     AZ_REQUIRE(d.cap_nfast == 0, AZ_EINVAL, "%s: the playout cap is on (az_engine_set_playout_cap, n_fast = %d) and is served %s only; switch it off first", who, d.cap_nfast, where);
     AZ_REQUIRE(d.kforced == 0.0, AZ_EINVAL, "%s: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served %s only; switch them off first", who, d.kforced, where);
     AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "%s: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and are served %s only; switch them off first", who, d.exact_max, where);
+    AZ_REQUIRE(!d.pf, AZ_EINVAL, "%s: proof backup is on (az_engine_set_proof_backup) and is served %s only; switch it off first", who, where);
     return AZ_OK;
 }
 
@@ -3610,6 +3783,7 @@ extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_
         const char *why = beyond_plain_search(e);
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_playout_cap: the playout cap is not served for %s", why);
         AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "az_engine_set_playout_cap: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and do not combine with the playout cap; switch them off first", d.exact_max);
+        AZ_REQUIRE(!d.pf, AZ_EINVAL, "az_engine_set_playout_cap: proof backup is on (az_engine_set_proof_backup) and does not combine with the playout cap; switch it off first");
         if (n_fast == d.cap_nfast && p_full == d.cap_pfull) return AZ_OK;
     }
     AZ_TRY(enter(e));
@@ -3647,6 +3821,7 @@ extern "C" int az_engine_set_forced_playouts(az_engine *e, double k) {
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_forced_playouts: forced playouts are not served for %s", why);
         AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "az_engine_set_forced_playouts: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and do not combine with forced playouts; switch them off first", d.exact_max);
     }
+    if (k > 0.0) AZ_REQUIRE(!d.pf, AZ_EINVAL, "az_engine_set_forced_playouts: proof backup is on (az_engine_set_proof_backup) and does not combine with forced playouts; switch it off first");
     if (k == d.kforced) return AZ_OK;
     AZ_TRY(enter(e));
     if (k > 0.0 && !e->forced_picks) AZ_TRY(dev_alloc(e, &e->forced_picks, (size_t)d.G));
@@ -3738,6 +3913,94 @@ extern "C" int az_engine_exact_endgame_stats(az_engine *e, int64_t *solved_leave
     AZ_HIP(hipMemcpyAsync(h, e->exact_sums, sizeof(h), hipMemcpyDeviceToHost, e->stream));
     AZ_HIP(hipStreamSynchronize(e->stream));
     *solved_leaves = (int64_t)h[0]; *solver_nodes = (int64_t)h[1];
+    return AZ_OK;
+}
+
+// ---- proof backup (k_step_proof, propagate_proofs_grp, move_policy) ---------------------------------------------
+// the slots' own counts, summed: one block, out[0] = nodes marked, out[1] = walks stopped on a proven node, out[2] = plies pruned
+__global__ __launch_bounds__(256) void k_proof_stats(EngDev E, unsigned long long *out) {
+    __shared__ unsigned long long s_sum[3];
+    if (threadIdx.x < 3) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long a[3] = {0, 0, 0};
+    for (int g = threadIdx.x; g < E.G; g += blockDim.x)
+        for (int i = 0; i < 3; ++i) a[i] += (unsigned long long)E.pf[(size_t)i * E.G + g];
+    for (int i = 0; i < 3; ++i) if (a[i]) atomicAdd(&s_sum[i], a[i]);
+    __syncthreads();
+    if (threadIdx.x < 3) out[threadIdx.x] = s_sum[threadIdx.x];
+}
+
+// the proven outcome of every slot's root: a slot that holds a game whose root is decided (F_PROVEN; F_TERMINAL) has its outcome, every
+// other slot AZ_UNSOLVED.  Reads only; one thread per slot.
+__global__ void k_root_proofs(EngDev E, int8_t *out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G) return;
+    int w = AZ_UNSOLVED;
+    if (E.active[g]) {
+        const Node r = load_node(pool_of(E, g) + E.root[g]);
+        if (r.flags & (F_TERMINAL | F_PROVEN)) w = r.win;
+    }
+    out[g] = (int8_t)w;
+}
+
+extern "C" int az_engine_set_proof_backup(az_engine *e, int32_t on) {
+    AZ_SETTER(e, "az_engine_set_proof_backup");
+    EngDev &d = e->d;
+    AZ_REQUIRE(on == 0 || on == 1, AZ_EINVAL, "az_engine_set_proof_backup: on must be 0 or 1, got %d", on);
+    if (on) {
+        const char *why = proof_backup_refusal(e->cfg.evaluator, e->sym_mask != 0, e->symr_mask != 0, e->leaf_batch, d.gm, d.cap_nfast > 0, d.kforced > 0.0);
+        AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_proof_backup: proof backup is not served for %s", why);
+    }
+    if ((on != 0) == (d.pf != nullptr)) return AZ_OK;
+    AZ_USABLE(e, "az_engine_set_proof_backup");
+    AZ_TRY(enter(e));
+    {   // a searched tree holds the marks of the old setting, or none where the new one expects them: fresh roots only
+        int n = 0;
+        AZ_HIP(hipMemsetAsync(e->scr_a, 0, sizeof(int), e->stream));
+        hipLaunchKernelGGL(k_count_evaluated_roots, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, e->scr_a);
+        AZ_HIP(hipGetLastError());
+        AZ_HIP(hipMemcpyAsync(&n, e->scr_a, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        AZ_HIP(hipStreamSynchronize(e->stream));
+        AZ_REQUIRE(n == 0, AZ_ESTATE, "az_engine_set_proof_backup: proof backup would go %s while %d active slot(s) hold searched trees; "
+                   "start the trees afresh first (az_engine_set_roots / az_engine_run; Python: set_roots, reset)", on ? "on" : "off", n);
+    }
+    if (on && !e->proof_ctr) {
+        AZ_TRY(dev_alloc(e, &e->proof_ctr, 3 * (size_t)d.G));
+        AZ_TRY(dev_alloc(e, &e->proof_sums, 3));
+    }
+    // counts of an earlier spell of the mode must not show up in this one
+    if (on) AZ_HIP(hipMemsetAsync(e->proof_ctr, 0, sizeof(int) * 3 * (size_t)d.G, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    d.pf = on ? e->proof_ctr : nullptr;
+    // other kernels: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_proof_backup_stats(az_engine *e, int64_t *proven_nodes, int64_t *proof_stops, int64_t *pruned_plies) {
+    AZ_REQUIRE(e && proven_nodes && proof_stops && pruned_plies, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_proof_backup_stats");
+    AZ_USABLE(e, "az_engine_proof_backup_stats");
+    *proven_nodes = 0; *proof_stops = 0; *pruned_plies = 0;
+    if (!e->d.pf) return AZ_OK;  // off: all 0
+    AZ_TRY(enter(e));
+    unsigned long long h[3] = {0, 0, 0};
+    hipLaunchKernelGGL(k_proof_stats, dim3(1), dim3(256), 0, e->stream, e->d, e->proof_sums);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipMemcpyAsync(h, e->proof_sums, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    *proven_nodes = (int64_t)h[0]; *proof_stops = (int64_t)h[1]; *pruned_plies = (int64_t)h[2];
+    return AZ_OK;
+}
+
+extern "C" int az_engine_root_proofs(az_engine *e, int8_t *d_out) {
+    AZ_REQUIRE(e && d_out, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_root_proofs");
+    AZ_USABLE(e, "az_engine_root_proofs");
+    AZ_TRY(enter(e));
+    hipLaunchKernelGGL(k_root_proofs, grid_for(e->d.G, TB), dim3(TB), 0, e->stream, e->d, d_out);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipStreamSynchronize(e->stream));
     return AZ_OK;
 }
 

@@ -18,13 +18,14 @@ struct SearchMode {
     bool cap;      // the playout cap's budgets are in force
     bool forced;   // forced playouts are on
     int exact;     // exact endgames: the empties limit of a solved leaf (az_engine_set_exact_endgame; 0: off)
+    bool proof;    // proof backup is on (az_engine_set_proof_backup)
 };
 
 // the kernel family of a search's lock-steps
-enum SearchFamily { SF_ROLLOUT, SF_STEP, SF_STEP_CAP, SF_STEP_FORCED, SF_STEP_CAP_FORCED, SF_STEP_MULTI, SF_STEP_GUMBEL, SF_STEP_GUMBEL_MULTI, SF_STEP_EXACT };
+enum SearchFamily { SF_ROLLOUT, SF_STEP, SF_STEP_CAP, SF_STEP_FORCED, SF_STEP_CAP_FORCED, SF_STEP_MULTI, SF_STEP_GUMBEL, SF_STEP_GUMBEL_MULTI, SF_STEP_EXACT, SF_STEP_PROOF };
 
 inline const char *search_family_name(SearchFamily f) {
-    static const char *const name[] = {"k_rollout_step", "k_step", "k_step_cap", "k_step_forced", "k_step_cap_forced", "k_step_multi", "k_step_gumbel", "k_step_gumbel_multi", "k_step_exact"};
+    static const char *const name[] = {"k_rollout_step", "k_step", "k_step_cap", "k_step_forced", "k_step_cap_forced", "k_step_multi", "k_step_gumbel", "k_step_gumbel_multi", "k_step_exact", "k_step_proof"};
     return name[f];
 }
 
@@ -59,16 +60,19 @@ struct SearchPlan {
     bool root_pass;  // false only for rollout
     int L;           // lock-steps that are followed by a forward
     int launches;    // step-kernel launches: what one search adds to the engine's lockstep_iters
+    bool exact;      // SF_STEP_PROOF only: the family's kernels that carry the solver (k_step_proof_exact); the cache is, as for every
+                     // one-leaf family, a property of the chain (its table pointers), not of the plan
 };
 
 inline SearchPlan plan_search(const SearchMode &m, int n_sim) {
-    SearchPlan p = {SF_STEP, m.full, true, n_sim, 0};
+    SearchPlan p = {SF_STEP, m.full, true, n_sim, 0, false};
     if (m.rollout) { p.family = SF_ROLLOUT; p.root_pass = false; p.L = 0; p.launches = n_sim; return p; }  // one launch per simulation
     if (m.gm > 0 && m.K > 1) { p.family = SF_STEP_GUMBEL_MULTI; p.L = gumbel_locksteps(n_sim, m.gm, m.K); }  // Sequential Halving with K walkers: cut per slot by its own cursor
     else if (m.K > 1) { p.family = SF_STEP_MULTI; p.L = (n_sim + m.K - 1) / m.K; }  // up to K walkers per slot and lock-step
     else if (m.gm > 0) p.family = SF_STEP_GUMBEL;
     else if (m.forced) p.family = m.cap ? SF_STEP_CAP_FORCED : SF_STEP_FORCED;
     else if (m.cap) p.family = SF_STEP_CAP;  // a slot past its budget idles: no walk, no row
+    else if (m.proof) { p.family = SF_STEP_PROOF; p.exact = m.exact > 0; }  // one family: exact endgames under it are a property of the plan
     else if (m.exact > 0) p.family = SF_STEP_EXACT;  // the plain search alone (exact_endgame_refusal): a late leaf is solved, not evaluated
     p.launches = p.L + 1;
     return p;
@@ -202,7 +206,16 @@ inline const char *exact_endgame_refusal(int evaluator, bool sym, bool sym_rando
     return nullptr;
 }
 
-// What a captured search is keyed by.  (What else travels in the launch arguments -- K, m, the playout cap's n_fast and p_full, forced
+// ---- proof backup (az_engine_set_proof_backup) --------------------------------------------------------------------
+// Where the mode is served: where exact endgames are -- the plain PUCT search of a network or fake engine, one leaf per slot and
+// lock-step, without the playout cap and forced playouts (their composed host models are not written).  It composes with exact
+// endgames, the evaluation cache and slot groups.  The mode that refuses, as the setters name it, or null.
+inline const char *proof_backup_refusal(int evaluator, bool sym, bool sym_random, int leaf_batch, int gm, bool cap, bool forced) {
+    return exact_endgame_refusal(evaluator, sym, sym_random, leaf_batch, gm, cap, forced);
+}
+
+// What a captured search is keyed by.  (A proof search is SF_STEP_PROOF whatever exact endgames say: the family keeps its graphs apart
+// from the plain and the exact ones, and a change of the empties limit under it drops every graph like any other.)  (What else travels in the launch arguments -- K, m, the playout cap's n_fast and p_full, forced
 // playouts' k, the empties limit of exact endgames, the pools -- drops every graph when it changes: az_engine.hip, drop_graphs.)
 typedef std::tuple<int, bool, int, int, int, int> SearchKey;
 inline SearchKey search_key(const SearchPlan &p, int n_sim, int cap, int g0, int g1) { return SearchKey((int)p.family, p.full, n_sim, cap, g0, g1); }

@@ -462,6 +462,28 @@ class SelfPlayEngine:
         check(lib().az_engine_exact_endgame_stats(self.h, C.byref(solved), C.byref(nodes)))
         return {"solved_leaves": solved.value, "solver_nodes": nodes.value}
 
+    def set_proof_backup(self, on):
+        """proof backup, MCTS-Solver (az_engine_set_proof_backup): a node is proven as soon as its children decide
+        it -- some child a proven win for its mover, or every child proven -- proven nodes are not searched again, and the move
+        and the policy target leave out proven losses (or keep the proven wins alone).  Plain search of EVAL_NET / EVAL_FAKE engines,
+        with exact endgames, the evaluation cache and slot groups or without; any other mode is a ValueError that names it.  A
+        change over searched trees is refused: set_roots() / run() first."""
+        check(lib().az_engine_set_proof_backup(self.h, 1 if on else 0))
+
+    def proof_backup_stats(self):
+        """{"proven_nodes", "proof_stops", "pruned_plies"}: interior nodes marked proven, walks that ended on one, and plies whose
+        policy counts the proofs changed, since the last run() / set_roots(); all 0 with the mode off"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib().az_engine_proof_backup_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"proven_nodes": a.value, "proof_stops": b.value, "pruned_plies": c.value}
+
+    def root_proofs(self):
+        """int8 [n_slots] on the device: the proven outcome (-1, 0, +1: an absolute player id) of every slot's root, endgame.UNSOLVED
+        (2) for a root that is not decided and for a slot without a game (az_engine_root_proofs; one launch)"""
+        out = torch.empty(self.cfg.n_slots, dtype=torch.int8, device="cuda")
+        check(lib().az_engine_root_proofs(self.h, out.data_ptr()))
+        return out
+
     def set_eval_cache(self, mode=None, capacity=0, stone_limit=0):
         """the leaf evaluation cache of run() (az_engine_set_eval_cache): each slot group keeps the network's
         outputs by exact position, so a leaf another game of the wave already sent through the network takes no batch row; the

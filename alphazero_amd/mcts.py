@@ -57,6 +57,7 @@ MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
 
 from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full  # noqa: E402  (the Gumbel root search's spec and refusals)
 from .endgame import check_exact_endgame  # noqa: E402  (exact endgames' spec and refusals)
+from .proof import check_proof_backup  # noqa: E402  (proof backup's spec and refusals)
 
 
 def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
@@ -88,7 +89,7 @@ def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
 
 class MCT:
     def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None,
-                 leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None):
+                 leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None, proof_backup=False):
         self.n_rollouts = 0
         self.simulation_time = 0
         self.eval_method = TreeEval.to_dict()["rollout" if eval_method is None else eval_method]
@@ -133,6 +134,11 @@ class MCT:
         self.exact_endgame = exact_endgame
         self._engine_exact = None     # the E the engine is set to
         check_exact_endgame(exact_endgame, self._nn, symmetry, leaf_batch, gumbel, self.eval_method == TreeEval.NEURAL)
+        # proof backup (alphazero_amd.proof: a bool): a node is proven as soon as its children decide it, proven nodes are not searched
+        # again, move and action probabilities respect the proofs; the plain PUCT search on HIP-routed networks only
+        self.proof_backup = proof_backup
+        self._engine_proof = False    # whether the engine has the mode on
+        check_proof_backup(proof_backup, self._nn, symmetry, leaf_batch, gumbel, self.eval_method == TreeEval.NEURAL)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -147,6 +153,7 @@ class MCT:
         check_leaf_batch(self.leaf_batch, nn, self.symmetry)
         check_gumbel(self.gumbel, nn, self.leaf_batch)
         check_exact_endgame(self.exact_endgame, nn, self.symmetry, self.leaf_batch, self.gumbel)
+        check_proof_backup(self.proof_backup, nn, self.symmetry, self.leaf_batch, self.gumbel)
         self._nn = nn
         self._hipnet = None
         self._evaluator = None
@@ -198,12 +205,30 @@ class MCT:
             pi = r["pi"][0].cpu().numpy().astype(np.float64)
             total = float(sum(pi[int(ai)] for ai in a))
             return {_move_of(board, int(ai)): float(pi[int(ai)]) / total for ai in a}, counts
+        if self._engine_proof:
+            # the move and the policy on the counts the proofs leave (a proven win's alone, or without the proven losses), as the
+            # engine would record and play them (a one-row readout); renormalised in float64 for the caller's draw
+            r = self._engine.root_readout(temps=float(temp), n=1)
+            if temp == 0:
+                return {_move_of(board, int(r["action"][0])): 1}, counts
+            pi = r["pi"][0].cpu().numpy().astype(np.float64)
+            total = float(sum(pi[int(ai)] for ai in a))
+            return {_move_of(board, int(ai)): float(pi[int(ai)]) / total for ai in a}, counts
         if temp == 0:
             best, _ = fair_max(counts.items(), key=lambda kv: kv[1])
             return {best: 1}, counts
         powered = {m: c ** (1. / temp) for m, c in counts.items()}
         total = sum(powered.values())
         return {m: v / total for m, v in powered.items()}, counts
+
+    def root_proof(self):
+        """the proven outcome of the searched root -- the winner's player id, 0 for a draw -- or None while it is not decided
+        (proof_backup; engine.root_proofs)"""
+        from .endgame import UNSOLVED
+        if self._engine is None or self._root_key is None:
+            return None
+        w = int(self._engine.root_proofs()[0])
+        return None if w == UNSOLVED else w
 
     def change_root(self, move):
         if self._engine is None or self._root_key is None:
@@ -277,12 +302,19 @@ class MCT:
             self._engine_gb = 1
             self._engine_gf = False
             self._engine_exact = None
+            self._engine_proof = False
         ex = check_exact_endgame(self.exact_endgame, self._nn if neural else None, self.symmetry, self.leaf_batch, self.gumbel, neural)
         if self._engine_exact is not None and ex is None:  # off before a mode it excludes may come on
             self._root_key = None  # over a fresh tree only: the kept one was searched under the old value
             self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8))
             self._engine.set_exact_endgame(None)
             self._engine_exact = None
+        pb = check_proof_backup(self.proof_backup, self._nn if neural else None, self.symmetry, self.leaf_batch, self.gumbel, neural)
+        if self._engine_proof and not pb:  # likewise: off over a fresh tree, before a mode it excludes may come on
+            self._root_key = None
+            self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8))
+            self._engine.set_proof_backup(False)
+            self._engine_proof = False
         lb = check_leaf_batch(self.leaf_batch, self._nn if neural else None, self.symmetry, neural)
         if self._engine_lb != lb:
             self._engine.set_leaf_batch(lb)
@@ -300,7 +332,7 @@ class MCT:
             self._engine.set_gumbel_batch(gb)
             self._engine_gb = gb
         key = (board.grid.astype(np.int8).tobytes(), int(board.player))
-        if self._engine_exact != ex:
+        if self._engine_exact != ex or self._engine_proof != pb:
             self._root_key = None  # the engine refuses a change over a searched tree: start it afresh
         if key != self._root_key:  # tree restarted from an unexplored state (mcts.py:124-125, 231-233)
             self._engine.set_roots(board.grid.astype(np.int8)[None], np.array([board.player], np.int8),
@@ -310,6 +342,9 @@ class MCT:
         if self._engine_exact != ex:
             self._engine.set_exact_endgame(ex)
             self._engine_exact = ex
+        if self._engine_proof != pb:
+            self._engine.set_proof_backup(pb)
+            self._engine_proof = pb
         if self._engine_gf != gf:  # on after set_roots: a fresh tree holds no node evaluated without its value; a kept one is refused
             self._engine.set_gumbel_full(gf)
             self._engine_gf = gf

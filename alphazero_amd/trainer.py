@@ -63,7 +63,7 @@ class AlphaZeroTrainer:
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
                  selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, selfplay_playout_cap=None, selfplay_forced_playouts=None,
-                 selfplay_exact_endgame=None, eval_search=None, eval_opening_plies=None):
+                 selfplay_exact_endgame=None, selfplay_proof_backup=False, eval_search=None, eval_opening_plies=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -116,6 +116,11 @@ class AlphaZeroTrainer:
         # only: not with the Gumbel search, the symmetry modes, the playout cap or forced playouts.
         self.selfplay_exact_endgame = selfplay_exact_endgame
         self._check_selfplay_exact_endgame()
+        # proof backup of that wave: a bool -- proven wins, losses and draws are backed up the search tree, and the
+        # recorded policy leaves out proven losses (or keeps the proven wins alone).  The self-play engine alone; the plain PUCT wave,
+        # with selfplay_exact_endgame or without: not with the Gumbel search, the symmetry modes, the playout cap or forced playouts.
+        self.selfplay_proof_backup = selfplay_proof_backup
+        self._check_selfplay_proof_backup()
         # the search the evaluation arena plays with (BatchedArena's `search`): None (the visit-based PUCT arena), "selfplay" (the modes
         # of the self-play wave above) or a dict of arena.SEARCH_KEYS; it goes to player 1 and, with eval_opponent "previous", to the
         # opponent too.  eval_opening_plies: BatchedArena's `opening_plies`, the seeded opening that makes the rounds different games.
@@ -160,6 +165,12 @@ class AlphaZeroTrainer:
     def _check_selfplay_exact_endgame(self):
         from .endgame import check_combination
         return check_combination(self.selfplay_exact_endgame, "selfplay_exact_endgame",
+                                 {"selfplay_gumbel": self.selfplay_gumbel, "selfplay_symmetry": self.selfplay_symmetry,
+                                  "selfplay_playout_cap": self.selfplay_playout_cap, "selfplay_forced_playouts": self.selfplay_forced_playouts})
+
+    def _check_selfplay_proof_backup(self):
+        from .proof import check_combination
+        return check_combination(self.selfplay_proof_backup, "selfplay_proof_backup",
                                  {"selfplay_gumbel": self.selfplay_gumbel, "selfplay_symmetry": self.selfplay_symmetry,
                                   "selfplay_playout_cap": self.selfplay_playout_cap, "selfplay_forced_playouts": self.selfplay_forced_playouts})
 
@@ -242,6 +253,7 @@ class AlphaZeroTrainer:
         cap = self._check_selfplay_playout_cap()
         forced = self._check_selfplay_forced_playouts()
         exact = self._check_selfplay_exact_endgame()
+        proof = self._check_selfplay_proof_backup()
         from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full
         gb = check_gumbel_batch(self.selfplay_gumbel_batch, self.selfplay_gumbel)
         gf = check_gumbel_full(self.selfplay_gumbel_full, self.selfplay_gumbel)
@@ -283,6 +295,9 @@ class AlphaZeroTrainer:
         if exact is None and getattr(self._engine, "_exact_endgame", None) is not None:
             self._engine.set_exact_endgame(None)
             self._engine._exact_endgame = None
+        if not proof and getattr(self._engine, "_proof_backup", False):
+            self._engine.set_proof_backup(False)
+            self._engine._proof_backup = False
         if external:  # a fresh evaluator for the network of this wave (update_network replaces self.nn)
             self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
         elif sym is not None or self._engine._sym_mode is not None:
@@ -309,6 +324,9 @@ class AlphaZeroTrainer:
         if exact != getattr(self._engine, "_exact_endgame", None):  # ValueError for a network routed to the external evaluator
             self._engine.set_exact_endgame(exact)  # every game of the last wave is over: no active slot holds a tree
             self._engine._exact_endgame = exact
+        if proof != getattr(self._engine, "_proof_backup", False):  # ValueError for a network routed to the external evaluator
+            self._engine.set_proof_backup(proof)  # likewise: no active slot holds a tree
+            self._engine._proof_backup = proof
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

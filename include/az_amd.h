@@ -605,6 +605,51 @@ int az_engine_eval_cache_stats(az_engine *e, int32_t *in_force, int64_t *hits);
 int az_engine_set_exact_endgame(az_engine *e, int32_t max_empties);
 int az_engine_exact_endgame_stats(az_engine *e, int64_t *solved_leaves, int64_t *solver_nodes);
 
+/* ---- proof backup: MCTS-Solver (Winands, Bjornsson, Saito 2008) ---------------------------------------------
+ * A finished game, or under exact endgames a solved leaf, is a terminal node whose winner is the truth.  With the mode on that
+ * truth is backed up the tree as a proof, not only averaged into Q: a node is proven as soon as its children decide it, proven
+ * nodes are not searched again, and the move and the policy target respect the proofs.  The reference has no counterpart.
+ * Opt-in: on = 0 (the default) is off, when no launch, kernel, allocation or output bit differs from an engine that never had it
+ * on.  Outcomes are absolute player ids in {-1, 0, +1}, as az_status and the solver report them; the mover of the node at path
+ * position i (the root is 0) is root_player * (-1)^i -- an Othello pass is an action, the side to move alternates strictly.
+ *   proven node   a node that has been backed up (N > 0; an unvisited child is never proven) and is either terminal (a finished
+ *                 game, or a solved leaf of exact endgames), proven with its winner, or an expanded node p of mover m that
+ *                 carries the flag bit F_PROVEN = 64 with the outcome in its winner byte.  p is proven when some child is proven
+ *                 with outcome m -- then its outcome is m -- or when every one of its children is proven -- then 0 if some
+ *                 child's outcome is 0, else -m.
+ *   propagation   in the backup of a simulation whose leaf was terminal or proven (and of no other), after the unchanged N / Q
+ *                 update: from the leaf's parent upward the rule is applied to each path node; a node it proves is marked and
+ *                 the walk up goes on, the first node it does not prove ends it.  So between any two kernels an expanded node
+ *                 carries F_PROVEN exactly when the rule holds for its children.  N and Q arithmetic does not change: a proven
+ *                 node returns its exact outcome as the backup's reward, Q is never set to an infinity.  Re-rooting copies the
+ *                 flag and the outcome; a proven root stays proven (a solved root is cleared as under exact endgames alone).
+ *   walk          below the root a walk stops on an F_PROVEN node as on a terminal one: outcome = the node's, no network row,
+ *                 no solver call, no cache lookup.  The root never stops a walk: every root grows by exactly n_sim visits.
+ *   selection     at every depth a child proven as a loss for the parent's mover is no candidate, unless every child is one
+ *                 (a root only).  At the root a child proven as a win for the root's mover takes the key +inf.  Ties among equal
+ *                 keys are drawn as ever, among the candidates.
+ *   move, target  wherever the move and the policy target are read (az_engine_run, az_engine_advance, az_engine_root_readout,
+ *                 az_engine_player_moves): if some root child is a proven win for the root's mover only such children keep their
+ *                 visit counts; otherwise children proven as the mover's loss count 0, unless all children are such -- or no
+ *                 other child has been visited, when the counts stay as they are.  The temperature arithmetic then runs on those
+ *                 counts, at temperature 0 included.  The visits rows, az_engine_best_moves, z and the samples' states are
+ *                 untouched.
+ *   nothing else  A game depends on (seed, game id, the mode, exact endgames' max_empties) only, never on the slot, the slot
+ *                 group, the batch or the cache.
+ *   counters      az_engine_proof_backup_stats: proven_nodes = interior nodes marked, each at its marking; proof_stops = walks
+ *                 that ended on an F_PROVEN node; pruned_plies = plies played whose counts the rule changed.  Since the last
+ *                 az_engine_run / az_engine_set_roots; all 0 with the mode off.  az_engine_stats is unchanged.
+ *   root proofs   az_engine_root_proofs: d_out[slot] (device, int8 [n_slots]) = the proven outcome of the slot's root, or
+ *                 AZ_UNSOLVED for a root that is not decided and for a slot without a game.  One launch; served with the mode
+ *                 on or off (off: no interior node is ever marked).
+ * Served where exact endgames are, and together with them, the leaf evaluation cache and slot groups.  Not served (AZ_EINVAL
+ * naming the mode; and while proof backup is on the setters of those modes refuse, naming proof backup): leaf_batch > 1, the
+ * Gumbel search, either symmetry mode, the playout cap, forced playouts, AZ_EVAL_ROLLOUT, AZ_EVAL_EXTERNAL.  AZ_ESTATE while a
+ * search is open, and for a change while an active slot holds a searched tree.  A change drops the cached search graphs. */
+int az_engine_set_proof_backup(az_engine *e, int32_t on);
+int az_engine_proof_backup_stats(az_engine *e, int64_t *proven_nodes, int64_t *proof_stops, int64_t *pruned_plies);
+int az_engine_root_proofs(az_engine *e, int8_t *d_out);
+
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
  * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves
