@@ -63,7 +63,7 @@ SYMBOLS = [
     "az_last_error", "az_version", "az_board_legal_batch", "az_board_play_batch", "az_board_status_batch", "az_solve_batch",
     "az_net_create", "az_net_destroy", "az_net_set_tensor", "az_net_commit", "az_net_set_tensor_device", "az_net_commit_device", "az_net_forward", "az_net_forward_dyn", "az_net_set_lanes", "az_net_forward_lane", "az_net_forward_sym", "az_net_forward_sym_codes",
     "az_net_action_size",
-    "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_trunk_prefetch", "az_net_trunk_stores", "az_net_stage_lane", "az_net_stage_plan", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
+    "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_trunk_prefetch", "az_net_trunk_stores", "az_net_stage_lane", "az_net_stage_plan", "az_net_gemm_rows", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
     "az_engine_get_stats", "az_engine_samples", "az_engine_set_roots", "az_engine_search", "az_engine_search_begin", "az_engine_search_end", "az_engine_pair", "az_engine_set_groups", "az_engine_groups", "az_engine_advance",
     "az_engine_root_children", "az_engine_root_readout", "az_engine_nodes_used", "az_engine_grow_pools", "az_engine_play", "az_augment_count", "az_augment",
     "az_engine_set_sides", "az_engine_best_moves", "az_engine_player_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator", "az_engine_set_symmetry", "az_engine_set_symmetry_random", "az_engine_set_leaf_batch", "az_engine_collisions",
@@ -114,6 +114,7 @@ def lib():
     L.az_net_trunk_prefetch.argtypes = [vp, C.c_int, C.c_int]
     L.az_net_trunk_stores.argtypes = [vp, C.c_int, C.c_int]
     L.az_net_stage_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
+    L.az_net_gemm_rows.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.az_net_stage_lane.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     L.az_net_profile.argtypes = [vp, C.c_int]
     L.az_net_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]

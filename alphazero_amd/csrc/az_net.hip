@@ -23,6 +23,8 @@
 //   k_gemm<...>    : LDS-tiled f32 MFMA GEMM with bias(+ReLU) epilogue for fc1 / fc2.
 //   k_gemm_ring<...>: k_gemm's 64 x 64 tile with a ring of K tiles in LDS: the MFMA chain runs across tile boundaries (one wave per SIMD
 //                    beside another chain's kernels).
+//                    Both take 16 or 32 rows per block on 16x16x4 chains where the launch's row bands still cover the device row count
+//                    (gemm_rows_narrow: the first and last plies of a self-play wave).
 //   k_heads        : policy+value GEMM (N padded to 16) fused with softmax / tanh.
 //   k_mlp          : the 316-parameter TicTacToe MLP, one thread per board.
 #include <math.h>
@@ -36,6 +38,7 @@
 #include "az_device.h"
 #include <hip/hip_ext.h>
 #include "az_host.h"
+#include "az_net_plan.h"  // which kernel serves a stage, every AZ_* switch of this file (NetTuning), and the rules the kernels share with the host
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -1604,6 +1607,121 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(1, WPB
 #undef LOAD_W16
 }
 
+// The count-following row forms of the 64 x 64 tile (StagePlan::gemm_rows, gemm_rows_per_block): a block of k_gemm /
+// k_gemm_ring whose launch carries few rows takes ROWS = 16 or 32 of them and the tile's 64 columns.  The four waves split the COLUMNS:
+// wave w owns the 16-column tile at 16 w and ROWS / 16 row tiles on the same B fragment, one v_mfma_f32_16x16x4_f32 accumulator each --
+// k advances by 4 every 32 cycles, where the 64-row path's single 32x32x2 accumulator advances by 2 every 64.
+//   * A: K chunks of KC = 2048 / ROWS k in two LDS buffers of [ROWS][KC + 4] floats (17 KB, inside either kernel's request; the row
+//     stride is 4 mod 64 banks: conflict-free fragment reads).  Two register sets: chunk c + 1 is written into the other buffer in the
+//     middle of chunk c and its registers are refilled with chunk c + 3; one barrier per chunk publishes it.
+//   * B: every weight is used by ONE wave, once (twice from a register in the 32-row form), so it never touches LDS: a lane loads its
+//     B[k][n] straight from the [K][N] matrix, PF k-steps (1024 cycles of MFMAs) ahead, on a 32-bit byte offset that walks K.
+//   * The tile loop is fully unrolled, for the reason given at k_gemm.  Chain per output: bias, then k ascending in 16x16x4 steps -- the
+//     chain of k_dense_frag / k_heads2, the same bits as the 32x32x2 chain and the oracle.
+template <int ROWS, bool RELU, int KT>
+__device__ __forceinline__ void gemm_rows_narrow(const float *__restrict__ A, const float *__restrict__ Bw, const float *__restrict__ bias,
+                                                 float *__restrict__ C, int M, int N, int bm0, int bn0, float *lds) {
+    static_assert(ROWS == 16 || ROWS == 32, "one or two 16-row tiles per wave");
+    constexpr int K = KT * 32, RT = ROWS / 16, KC = 2048 / ROWS, XSTR = KC + 4, NC = K / KC, SPC = KC / 4, NS = K / 4, PF = 32 / RT, FRD = 4;
+    static_assert(NC >= 2 && NS > PF, "two register sets of chunks; the B ring is filled before the first step");
+    // the thread id through an ordered no-op: nothing derived from it is shared with the 64-row path, whose registers stay what they were
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int wave = tid >> 6, lane = tid & 63, m = lane & 15, kq = lane >> 4;
+    const int cn = bn0 + 16 * wave + m;
+    // B: step g reads row 4 g + kq of the matrix at column cn
+    const unsigned bstep = 16u * N;  // 4 k of N floats
+    unsigned bo = 4u * (kq * N + cn);
+    float bq[PF];
+#define NARROW_LDB(dst)                                                                                  \
+    {                                                                                                    \
+        dst = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(Bw) + bo);                 \
+        bo += bstep;                                                                                     \
+        asm("" : "+v"(bo));                                                                              \
+    }
+    // A staging: per chunk a thread carries two 4-float pieces (rows srow and srow + ROWS / 2, k quad sq); chunk u rests in register set
+    // u % 2 (sa* / sb*), and the chunks are walked in pairs so that every set is named, not indexed
+    constexpr int QPR = KC / 4;  // 16-byte pieces per row of a chunk
+    const int srow = tid / QPR, sq = tid % QPR;
+    int gr0 = bm0 + srow, gr1 = gr0 + ROWS / 2;
+    gr0 = gr0 < M ? gr0 : M - 1;
+    gr1 = gr1 < M ? gr1 : M - 1;
+    unsigned ao0 = 4u * (gr0 * K + 4 * sq), ao1 = 4u * (gr1 * K + 4 * sq);  // byte offsets that walk K: the launch holds 4 M K below 2^32 (gemm_rows_shape)
+    float *sp = lds + srow * XSTR + 4 * sq;
+    float4 sa0, sa1, sb0, sb1;
+#define NARROW_LDA(r0, r1)                                                                               \
+    {                                                                                                    \
+        r0 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(A) + ao0);                 \
+        r1 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(A) + ao1);                 \
+        ao0 += 4u * KC; ao1 += 4u * KC;                                                                  \
+        asm("" : "+v"(ao0), "+v"(ao1));                                                                  \
+    }
+#define NARROW_STA(r0, r1, buf)                                                                          \
+    {                                                                                                    \
+        *reinterpret_cast<float4 *>(sp + (buf) * ROWS * XSTR) = r0;                                      \
+        *reinterpret_cast<float4 *>(sp + (buf) * ROWS * XSTR + (ROWS / 2) * XSTR) = r1;                  \
+    }
+    NARROW_LDA(sa0, sa1)
+    NARROW_LDA(sb0, sb1)
+#pragma unroll
+    for (int p = 0; p < PF; ++p) NARROW_LDB(bq[p])
+    f32x4 acc[RT];
+    {
+        const float bv = bias[cn];
+#pragma unroll
+        for (int t = 0; t < RT; ++t) acc[t] = (f32x4){bv, bv, bv, bv};
+    }
+    NARROW_STA(sa0, sa1, 0)
+    if (2 < NC) NARROW_LDA(sa0, sa1)
+    __syncthreads();
+    const float *xa = lds + m * XSTR + kq;  // A fragment of step s of a chunk, row tile t: xa[t * 16 * XSTR + 4 * s]
+    // chunk c from buffer c % 2; in its middle chunk c + 1 (registers r0, r1) goes to the other buffer -- last read before the barrier
+    // behind chunk c - 1 -- and the registers are refilled with chunk c + 3; the barrier behind the chunk publishes chunk c + 1
+#define NARROW_CHUNK(c, r0, r1)                                                                          \
+    {                                                                                                    \
+        const float *xc = xa + ((c) % 2) * ROWS * XSTR;                                                  \
+        float afr[FRD][RT];                                                                              \
+        _Pragma("unroll") for (int p = 0; p < FRD - 1; ++p)                                              \
+            _Pragma("unroll") for (int t = 0; t < RT; ++t) afr[p][t] = xc[t * 16 * XSTR + 4 * p];        \
+        _Pragma("unroll") for (int s = 0; s < SPC; ++s) {                                                \
+            const int g = (c) * SPC + s;                                                                 \
+            if (s + FRD - 1 < SPC) {                                                                     \
+                _Pragma("unroll") for (int t = 0; t < RT; ++t) afr[(s + FRD - 1) % FRD][t] = xc[t * 16 * XSTR + 4 * (s + FRD - 1)]; \
+            }                                                                                            \
+            const float b = bq[g % PF];                                                                  \
+            if (g + PF < NS) NARROW_LDB(bq[g % PF])                                                      \
+            if (s == SPC / 2 && (c) + 1 < NC) {                                                          \
+                NARROW_STA(r0, r1, ((c) + 1) % 2)                                                        \
+                if ((c) + 3 < NC) NARROW_LDA(r0, r1)                                                     \
+            }                                                                                            \
+            __builtin_amdgcn_sched_barrier(0);                                                           \
+            _Pragma("unroll") for (int t = 0; t < RT; ++t) acc[t] = MFMA(afr[s % FRD][t], b, acc[t]);    \
+            __builtin_amdgcn_sched_barrier(0);                                                           \
+        }                                                                                                \
+        if ((c) + 1 < NC) __syncthreads();                                                               \
+    }
+    static_assert(NC % 2 == 0, "chunks are walked in pairs");
+#pragma unroll
+    for (int c = 0; c < NC; c += 2) {
+        NARROW_CHUNK(c, sb0, sb1)
+        NARROW_CHUNK(c + 1, sa0, sa1)
+    }
+#undef NARROW_CHUNK
+#undef NARROW_LDB
+#undef NARROW_LDA
+#undef NARROW_STA
+    // C layout of 16x16x4: column lane & 15, rows 4 (lane >> 4) + r
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = bm0 + 16 * t + 4 * kq + r;
+            float v = acc[t][r];
+            if (RELU) v = v > 0.0f ? v : 0.0f;
+            if (row < M) C[(size_t)row * N + cn] = v;
+        }
+}
+
 // C[M][N] = act(A[M][K] * Bw[K][N] + bias[N]);  K % 32 == 0, N % BN == 0.
 // f32 MFMA 32x32x2 (sustains ~150 TFLOP/s from a single in-place accumulator chain on this chip; the
 // 16x16x4 shape cycling over many accumulators measured 10-25 % lower: tools/micro/mfma_peak2.hip).
@@ -1613,7 +1731,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(1, WPB
 template <int BM, int BN, int WM, int WN, bool RELU, int KT>
 __global__ __launch_bounds__(256, 2) void k_gemm(const float *__restrict__ A, const float *__restrict__ Bw,
                                               const float *__restrict__ bias, float *__restrict__ C, int M, int N, int K,
-                                              const int *__restrict__ dyn_count) {
+                                              int rows_follow, const int *__restrict__ dyn_count) {  // rows_follow beside K: one load fetches both
     if (dyn_count) { int c = *dyn_count; M = c < M ? c : M; }
     // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (b and b+8 share an L2), so the
     // linear id is remapped to give every XCD a contiguous run of row bands.  Speed only.
@@ -1621,7 +1739,18 @@ __global__ __launch_bounds__(256, 2) void k_gemm(const float *__restrict__ A, co
     int bid = (int)blockIdx.y * nbx + (int)blockIdx.x;
     if (nb % 8 == 0) bid = (bid % 8) * (nb / 8) + bid / 8;
     const int tile_y = bid / nbx, tile_x = bid % nbx;
-    if (tile_y * BM >= M) return;  // whole block beyond the rows filled this step (uniform exit)
+    // rows of a block: BM, or where the launch asks for it (rows_follow) the narrowest form whose bands cover the device count
+    int rows = BM;
+    if constexpr (gemm_rows_tile(BM, BN, KT * 32, 0)) rows = gemm_rows_per_block((int)gridDim.y, M, rows_follow);
+    if (tile_y * rows >= M) return;  // whole block beyond the rows filled this step (uniform exit)
+    if constexpr (gemm_rows_tile(BM, BN, KT * 32, 0)) {
+        extern __shared__ __attribute__((aligned(16))) float gsm_rows[];
+        if (__builtin_expect(rows != BM, 0)) {  // unlikely: the narrow forms lie behind the 64-row path, which stays the fall-through of the prologue as it was
+            if (rows == 16) gemm_rows_narrow<16, RELU, KT>(A, Bw, bias, C, M, N, tile_y * 16, tile_x * BN, gsm_rows);
+            else gemm_rows_narrow<32, RELU, KT>(A, Bw, bias, C, M, N, tile_y * 32, tile_x * BN, gsm_rows);
+            return;
+        }
+    }
     constexpr int BK = 32, WAVES_N = BN / WN, TM = WM / 32, TN = WN / 32;
     static_assert((BM / WM) * WAVES_N == 4 && TM >= 1 && TN >= 1, "4 waves per block, 32x32 MFMA tiles");
     constexpr int ASTR = BK + 1;  // (m + k) mod 32 : conflict-free A-fragment reads (32 rows, one k)
@@ -1805,7 +1934,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm(const float *__restrict__ A, co
 // The tile loop is fully unrolled (KT = K / 32 >= 2), for the reason given above.  Same chain: bias, then k ascending.
 template <bool RELU, int KT>
 __global__ __launch_bounds__(256, 2) void k_gemm_ring(const float *__restrict__ A, const float *__restrict__ Bw, const float *__restrict__ bias,
-                                                    float *__restrict__ C, int M, int N, const int *__restrict__ dyn_count) {
+                                                    float *__restrict__ C, int M, int N, int rows_follow, const int *__restrict__ dyn_count) {
     static_assert(KT >= 2, "NSET tiles are staged before the first MFMA");
     if (dyn_count) { int c = *dyn_count; M = c < M ? c : M; }
     constexpr int BM = 64, BN = 64, BK = 16, K = KT * 32, T = K / BK, NBUF = 3, NSET = 4, FRD = 4, KS = BK / 2, ASTR = BK + 1, BSTR = BN;
@@ -1813,8 +1942,17 @@ __global__ __launch_bounds__(256, 2) void k_gemm_ring(const float *__restrict__ 
     int bid = (int)blockIdx.y * nbx + (int)blockIdx.x;
     if (nb % 8 == 0) bid = (bid % 8) * (nb / 8) + bid / 8;  // XCD-aware tile order, as k_gemm
     const int tile_y = bid / nbx, tile_x = bid % nbx;
-    if (tile_y * BM >= M) return;  // whole block beyond the rows filled this step (uniform exit)
+    int rows = BM;  // as k_gemm: the narrowest row form whose bands cover the device count, where the launch asks for it
+    if constexpr (gemm_rows_tile(BM, BN, K, 1)) rows = gemm_rows_per_block((int)gridDim.y, M, rows_follow);
+    if (tile_y * rows >= M) return;  // whole block beyond the rows filled this step (uniform exit)
     extern __shared__ __attribute__((aligned(16))) float gsm[];
+    if constexpr (gemm_rows_tile(BM, BN, K, 1)) {
+        if (__builtin_expect(rows != BM, 0)) {  // laid out behind the 64-row path, as in k_gemm
+            if (rows == 16) gemm_rows_narrow<16, RELU, KT>(A, Bw, bias, C, M, N, tile_y * 16, tile_x * BN, gsm);
+            else gemm_rows_narrow<32, RELU, KT>(A, Bw, bias, C, M, N, tile_y * 32, tile_x * BN, gsm);
+            return;
+        }
+    }
     float *As = gsm;                       // [NBUF][BM][ASTR]
     float *Bs = gsm + NBUF * BM * ASTR;    // [NBUF][BK][BSTR]   (NBUF*BM*ASTR is a multiple of 4 floats: 16-byte aligned)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -3259,7 +3397,6 @@ __global__ __launch_bounds__(256) void k_qdense_small(const float *__restrict__ 
 // host side
 // ---------------------------------------------------------------------------------------------
 #include <atomic>
-#include "az_net_plan.h"  // which kernel serves a stage, and every AZ_* switch of this file (NetTuning)
 
 static bool use_qdense(int game) { return net_tuning().dense_i8 && game == AZ_OTHELLO; }
 
@@ -3939,6 +4076,7 @@ struct Dense {  // C[M][N] = act(A[M][K] Bw[K][N] + bias); Bq: Bw in k_dense_fra
     int M, N, K;
     bool relu;
     const int *dyn;
+    int rows_follow;  // k_gemm's 64 x 64 tile: StagePlan::gemm_rows, set by launch_dense
 };
 
 template <int BM, int BN, int WM, int WN, int KT>
@@ -3946,8 +4084,8 @@ static int gemm_launch(LaunchCtx &c, const Dense &a) {
     constexpr int lds = gemm_lds_bytes<BM, BN>();
     AZ_TRY((lds_attr<&k_gemm<BM, BN, WM, WN, true, KT>, &k_gemm<BM, BN, WM, WN, false, KT>>(lds)));
     dim3 grid(a.N / BN, (a.M + BM - 1) / BM);
-    if (a.relu) AZ_LAUNCH(c, (k_gemm<BM, BN, WM, WN, true, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
-    else AZ_LAUNCH(c, (k_gemm<BM, BN, WM, WN, false, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.dyn);
+    if (a.relu) AZ_LAUNCH(c, (k_gemm<BM, BN, WM, WN, true, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.rows_follow, a.dyn);
+    else AZ_LAUNCH(c, (k_gemm<BM, BN, WM, WN, false, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.K, a.rows_follow, a.dyn);
     return AZ_OK;
 }
 
@@ -3970,8 +4108,8 @@ static int gemm_ring_launch(LaunchCtx &c, const Dense &a) {
     constexpr int lds = gemm_ring_lds_bytes();
     AZ_TRY((lds_attr<&k_gemm_ring<true, KT>, &k_gemm_ring<false, KT>>(lds)));
     dim3 grid(a.N / 64, (a.M + 63) / 64);
-    if (a.relu) AZ_LAUNCH(c, (k_gemm_ring<true, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.dyn);
-    else AZ_LAUNCH(c, (k_gemm_ring<false, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.dyn);
+    if (a.relu) AZ_LAUNCH(c, (k_gemm_ring<true, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.rows_follow, a.dyn);
+    else AZ_LAUNCH(c, (k_gemm_ring<false, KT>), grid, dim3(256), lds, a.A, a.Bw, a.bias, a.C, a.M, a.N, a.rows_follow, a.dyn);
     return AZ_OK;
 }
 
@@ -4009,7 +4147,9 @@ static int frag_go(LaunchCtx &c, const Dense &a) {
 }
 
 // fc1 / fc2 in float32 on the kernel plan_dense chose
-static int launch_dense(LaunchCtx &c, const StagePlan &p, const Dense &a) {
+static int launch_dense(LaunchCtx &c, const StagePlan &p, const Dense &a0) {
+    Dense a = a0;
+    a.rows_follow = p.gemm_rows;
     AZ_REQUIRE(a.K % 32 == 0, AZ_EINVAL, "GEMM K=%d is not a multiple of 32", a.K);
     switch (p.kernel) {
         case K_DENSE_FRAG: return frag_go(c, a);
@@ -4135,8 +4275,8 @@ static int run_stage(az_net *n, LaunchCtx &c, int stage, const float *d_input, i
         case K_QDENSE_SMALL: case K_QGEMM: return launch_qdense(n, c, p, stage, B, dyn);
         case K_HEADS_SMALL: case K_HEADS: case K_HEADS2: return launch_heads(n, c, p, B, d_probs, d_value, dyn);
         default:  // K_DENSE_FRAG, K_DENSE_SMALL, K_GEMM, K_GEMM_SOLO, K_GEMM_SOLO_T
-            return launch_dense(c, p, stage == 1 ? Dense{c.feat, n->fc1w, n->fc1wq, n->fc1b, c.h1, B, n->F1, n->FIN, true, dyn}
-                                                 : Dense{c.h1, n->fc2w, n->fc2wq, n->fc2b, c.h2, B, n->F2, n->F1, true, dyn});
+            return launch_dense(c, p, stage == 1 ? Dense{c.feat, n->fc1w, n->fc1wq, n->fc1b, c.h1, B, n->F1, n->FIN, true, dyn, 0}
+                                                 : Dense{c.h1, n->fc2w, n->fc2wq, n->fc2b, c.h2, B, n->F2, n->F1, true, dyn, 0});
     }
 }
 
@@ -4330,10 +4470,22 @@ extern "C" int az_net_stage_plan(const az_net *n, int stage, int B, int beside, 
             snprintf(buf, (size_t)cap, "%s form=%d lds_blocks=%d prefetch=%d stores=%d", k, p.quad_form, p.lds_blocks, p.quad_prefetch, p.quad_stores);
             break;
         case K_TRUNK_Q: case K_TRUNK2: snprintf(buf, (size_t)cap, "%s %s waves=%d", k, p.wino ? "wino" : "direct", p.waves); break;
-        case K_GEMM: snprintf(buf, (size_t)cap, "%s %dx%d form=%d", k, p.bm, p.bn, p.gemm_form); break;
+        case K_GEMM: snprintf(buf, (size_t)cap, "%s %dx%d form=%d rows=%s", k, p.bm, p.bn, p.gemm_form, p.gemm_rows ? "count" : "64"); break;
         default: snprintf(buf, (size_t)cap, "%s", k);
     }
     return AZ_OK;
+}
+
+// Rows per block of fc1 (stage 1) / fc2 (stage 2) of a launch of B boards whose device count is `count` (clamped to B): 16 / 32 / 64 on
+// k_gemm's 64 x 64 tile (gemm_rows_per_block with the launch's bands and the plan's gemm_rows), the tile's height on its other tiles,
+// 0 where the stage runs another kernel.  For the tools and tests that say which row form a (launch, count) runs.
+extern "C" int az_net_gemm_rows(const az_net *n, int stage, int B, int beside, int count) {
+    if (!n || B <= 0 || (stage != 1 && stage != 2) || n->game == AZ_TICTACTOE) return 0;
+    const StagePlan p = plan_stage(net_dims(n), net_tuning(), stage, B, beside);
+    if (p.kernel != K_GEMM) return 0;
+    if (p.bm != 64 || p.bn != 64) return p.bm;
+    const int m = count < 0 ? 0 : (count < B ? count : B);
+    return gemm_rows_per_block((B + 63) / 64, m, p.gemm_rows);
 }
 
 // ONE stage of az_net_forward_lane: the launch the forward would make for that stage, on the lane's activation rows as they stand

@@ -5,6 +5,14 @@
 #include <limits.h>
 #include <stdlib.h>
 
+#ifndef AZ_PLAN_HD  // a rule the kernels apply too (az_search_plan.h has the same)
+#if defined(__HIPCC__)
+#define AZ_PLAN_HD __host__ __device__ inline
+#else
+#define AZ_PLAN_HD inline
+#endif
+#endif
+
 #ifndef AZ_OTHELLO  // the games, as az_device.h numbers them
 #define AZ_OTHELLO 0
 #define AZ_CONNECT4 1
@@ -31,6 +39,7 @@ struct NetTuning {
     int dense_frag_max;       // AZ_DENSE_FRAG_MAX (-1: 1024 rows, 2048 for K >= 1024): rows up to which k_dense_frag runs; 0 = never
     int gemm_tile;            // AZ_GEMM_TILE (0: by size): k_gemm's tile 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 64x128 (A/B)
     int gemm_form;            // AZ_GEMM_FORM (-1: by regime, see plan_dense): 0 = k_gemm's double-buffer form everywhere, 1 = the ring form wherever it exists (A/B)
+    int gemm_rows;            // AZ_GEMM_ROWS (-1: by regime, see plan_dense): 0 = 64 rows per block of k_gemm's 64 x 64 tile whatever the device row count, 1 = the count-following row forms wherever they exist (A/B)
     int qd_small_max;         // AZ_QD_SMALL_MAX (512): rows up to which k_qdense_small serves a fixed-point layer; 0 = never
     int qg_cfg;               // AZ_QG_CFG (0: by size): k_qgemm's tile plan 1 .. 5, see plan_dense (A/B; every plan gives the same bits)
     int heads_small_max;      // AZ_HEADS_SMALL_MAX (-1: 128, 0 for OthelloNet): rows up to which k_heads_small runs (A/B)
@@ -55,6 +64,7 @@ inline const NetTuning &net_tuning() {
         v.gemm_solo = net_env("AZ_GEMM_SOLO", -1); v.dense_frag_max = net_env("AZ_DENSE_FRAG_MAX", -1); v.gemm_tile = net_env("AZ_GEMM_TILE", 0);
         v.gemm_form = net_env("AZ_GEMM_FORM", -1); v.trunk_quad_prefetch = net_env("AZ_TRUNK_QUAD_PREFETCH", -1);
         v.trunk_quad_stores = net_env("AZ_TRUNK_QUAD_STORES", -1);
+        v.gemm_rows = getenv("AZ_GEMM_ROWS") ? (net_env("AZ_GEMM_ROWS", 0) ? 1 : 0) : -1;
         v.qd_small_max = net_env("AZ_QD_SMALL_MAX", 512); v.qg_cfg = net_env("AZ_QG_CFG", 0);
         v.heads_small_max = net_env("AZ_HEADS_SMALL_MAX", -1); v.heads_v1 = net_env("AZ_HEADS_V1", 0) != 0; v.heads_rh = net_env("AZ_HEADS_RH", 0);
         v.tail_v1 = net_env("AZ_TAIL_V1", 0) != 0; v.no_fused_tail = net_env("AZ_NO_FUSED_TAIL", 0) != 0; v.tail_r8_from = net_env("AZ_TAIL_R8_FROM", INT_MAX);
@@ -86,6 +96,7 @@ struct StagePlan {
     int lds_blocks;    // k_trunk, k_trunk_quad: blocks per CU the LDS request is padded to (outside 1..8: the kernel's natural size)
     int bm, bn;        // k_gemm: the workgroup tile (0: N fits none)
     int gemm_form;     // k_gemm: 0 = LDS double buffer, the chain stops at every K tile; 1 = LDS ring, the chain runs through (k_gemm_ring)
+    int gemm_rows;     // k_gemm's 64 x 64 tile: 1 = the rows of a block follow the device row count (gemm_rows_per_block), 0 = 64 whatever the count
     int qg[4];         // k_qgemm: the tile plan <NWM, NWN, WM, WN>
     int nt, rh;        // k_heads, k_heads2: 16-column tiles; k_heads2: 16-row tiles per block
     int tail_r;        // k_tail_small: R (4 R rows per workgroup)
@@ -97,6 +108,22 @@ constexpr bool frag_shape(int N, int K) { return N % 64 == 0 && K % 128 == 0 && 
 constexpr int gemm_unrolled_kt(int K) { return (K == 1024 || K == 512 || K == 192 || K == 128 || K == 64) ? K / 32 : 0; }
 // k_gemm's ring form exists for the 64 x 64 tile with an unrolled tile loop
 constexpr bool gemm_ring_shape(int bm, int bn, int K) { return bm == 64 && bn == 64 && gemm_unrolled_kt(K) >= 2; }
+// The count-following row forms of the 64 x 64 tile exist for OthelloNet 8x8's unrolled K: 512 and 1024 in the double-buffer form, 1024
+// in the ring form (with them k_gemm_ring<16> would leave the 80 registers of its six waves per SIMD, so it stays as it was).  They
+// address the rows and the weights by 32-bit byte offsets: 4 B K and 4 K N below 2^32.
+constexpr bool gemm_rows_tile(int bm, int bn, int K, int form) { return bm == 64 && bn == 64 && (K == 1024 || (K == 512 && form == 0)); }
+constexpr bool gemm_rows_shape(int bm, int bn, int B, int N, int K, int form) {
+    return gemm_rows_tile(bm, bn, K, form) && (long long)K * N < (1LL << 30) && (long long)K * B < (1LL << 30);
+}
+// Rows per block of a launch of k_gemm's 64 x 64 tile with gy row bands, of which the device count fills m rows (clamped to the
+// launch): the narrowest of 16 / 32 / 64 whose bands cover the count.  Kernel and host share it: the kernel maps its blocks by it,
+// az_net_gemm_rows reports it.  follow = StagePlan::gemm_rows; a launch without a device count has m = its own rows, and runs 64.
+AZ_PLAN_HD int gemm_rows_per_block(int gy, int m, int follow) {
+    if (!follow) return 64;
+    if ((m + 15) / 16 <= gy) return 16;
+    if ((m + 31) / 32 <= gy) return 32;
+    return 64;
+}
 // 8x8, 6x6 and 7x6 planes run the tuned kernels; every other plane between 5x5 and 8x8 -- Connect4Net on the board sizes the engine
 // plays -- runs k_trunk (one board per wave, direct form) at any batch size
 constexpr bool plane_tuned(int CH, int CW) { return (CH == 8 && CW == 8) || (CH == 6 && CW == 6) || (CH == 7 && CW == 6); }
@@ -216,6 +243,13 @@ inline StagePlan plan_dense(const NetDims &d, const NetTuning &t, int stage, int
         p.bm = bm; p.bn = bn;
         const bool measured = d.game == AZ_OTHELLO && d.CH == 8 && d.CW == 8 && beside && bm == 64 && bn == 64 && mb64 * (N / 64) <= 256;
         p.gemm_form = gemm_ring_shape(bm, bn, K) && (t.gemm_form >= 0 ? t.gemm_form == 1 : measured) ? 1 : 0;
+        // The rows of a block.  A replayed graph fixes a group's launch at 2048 rows; the lock-steps of a wave's first
+        // and last plies fill a few hundred of them, and a block of this tile walks its whole K on ONE 32x32x2 chain however few blocks
+        // run.  With the count-following forms a block takes 16 or 32 rows where the launch's bands still cover the count, on 16x16x4
+        // chains four times / twice shorter; above that the 64-row path as it was.  The rule is the measured shape and no more:
+        // OthelloNet 8x8, beside launches of this tile (either form).  Lone launches, other nets and planes: AZ_GEMM_ROWS=1 only.
+        const bool rows_measured = d.game == AZ_OTHELLO && d.CH == 8 && d.CW == 8 && beside && bm == 64 && bn == 64;
+        p.gemm_rows = gemm_rows_shape(bm, bn, B, N, K, p.gemm_form) && (t.gemm_rows >= 0 ? t.gemm_rows == 1 : rows_measured) ? 1 : 0;
         return is(K_GEMM);
     };
     if (tile == 1 && N % 128 == 0) return tiled(128, 128);

@@ -225,6 +225,11 @@ class HipNet:
         check(lib().az_net_stage_plan(self.h, stage, B, int(beside), buf, 128))
         return buf.value.decode()
 
+    def gemm_rows(self, stage, B, beside, count):
+        """rows per block of fc1 / fc2 of a launch of B boards whose device count is `count`: 16 / 32 / 64 on k_gemm's 64 x 64 tile,
+        the tile's height on its other tiles, 0 on another kernel (az_net_gemm_rows)"""
+        return int(lib().az_net_gemm_rows(self.h, stage, B, int(beside), int(count)))
+
     def trunk_stores(self, B, beside):
         """True where that trunk runs the prefetching form with vector stores of conv3's planes and conv4's features"""
         return bool(lib().az_net_trunk_stores(self.h, B, int(beside)))

@@ -163,8 +163,14 @@ int az_net_trunk_prefetch(const az_net *net, int B, int beside);
  * as 16-byte stores), else 0 (AZ_TRUNK_QUAD_STORES: unset = by regime, 0 = never, 1 = wherever the prefetching form runs); the same bits */
 int az_net_trunk_stores(const az_net *net, int B, int beside);
 /* The plan of stage 0..3 of a launch of B boards (beside as in az_net_forward_lane) as text: the kernel by its own name and the
- * plan's fields for it, e.g. "k_trunk_quad form=2 lds_blocks=0 prefetch=1 stores=1", "k_gemm 64x64 form=1".  For tools' output. */
+ * plan's fields for it, e.g. "k_trunk_quad form=2 lds_blocks=0 prefetch=1 stores=1", "k_gemm 64x64 form=1 rows=count" (rows=count: the
+ * rows of a block follow the device row count, see az_net_gemm_rows; rows=64: they do not).  For tools' output. */
 int az_net_stage_plan(const az_net *net, int stage, int B, int beside, char *buf, int cap);
+/* Rows per block of fc1 (stage 1) / fc2 (stage 2) of a launch of B boards of which the device count fills `count`: 16, 32 or 64 on
+ * k_gemm's 64 x 64 tile -- the narrowest form whose ceil(B / 64) row bands cover the count, where the plan lets the rows follow it
+ * (AZ_GEMM_ROWS: unset = by regime, 0 = 64 everywhere, 1 = wherever the narrow forms exist) -- the tile's height on k_gemm's other
+ * tiles, 0 where the stage runs another kernel.  Every form gives the same bits.  (ABI 115) */
+int az_net_gemm_rows(const az_net *net, int stage, int B, int beside, int count);
 /* One stage (0 trunk, 1 fc1, 2 fc2, 3 heads) of az_net_forward_lane with the same arguments: exactly the launch the forward makes for
  * that stage, reading the lane's activation rows as they stand.  For tools that time one stage beside another on two streams.
  * Only stage 3 writes d_probs / d_value (the fused tails: stage 1); they are required for every stage so that the call is the

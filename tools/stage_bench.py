@@ -1,4 +1,6 @@
-"""Stage times (az_net_time_stage) of a conv net over row counts.  usage: python tools/stage_bench.py othello8|othello6|connect4 [rows ...]"""
+"""Stage times (az_net_time_stage) of a conv net over row counts, and for the sizes whose fc1 / fc2 run k_gemm the rows per block that a
+beside launch of that size runs at a device count of an eighth, a half and all of its rows (az_net_gemm_rows; AZ_GEMM_ROWS).
+usage: python tools/stage_bench.py othello8|othello6|connect4 [rows ...]"""
 import os
 import sys
 
@@ -21,6 +23,10 @@ def main():
         t = [1e3 * hnet.time_stage(s, B, 200) for s in (0, 1, -1)]
         print(f"{B:>6} " + " ".join(f"{x:8.1f}" for x in t) + "   " + ", ".join(hnet.stage_kernel(s, B) for s in (0, 1))
               + (" (k_trunk_quad, prefetching form" + (", vector stores)" if hnet.trunk_stores(B, 0) else ")") if hnet.trunk_prefetch(B, 0) else ""), flush=True)
+        forms = [(("fc1", "fc2")[s - 1], hnet.stage_plan(s, B, 1), [hnet.gemm_rows(s, B, 1, c) for c in (max(1, B // 8), max(1, B // 2), B)]) for s in (1, 2)]
+        for name, plan, rows in forms:
+            if rows[0]:
+                print(f"{'':>6} beside: {name} {plan}, rows per block at counts {max(1, B // 8)} / {max(1, B // 2)} / {B}: " + " / ".join(map(str, rows)), flush=True)
 
 
 if __name__ == "__main__":
