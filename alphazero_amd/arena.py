@@ -67,11 +67,15 @@ class Arena:
 
 
 SEARCH_KEYS = ("symmetry", "leaf_batch", "gumbel", "gumbel_batch", "gumbel_full")
+# and the settings of the PUCT search itself, which are no search mode of their own: "puct" (alphazero_amd.puct: None, c_init or a dict of
+# c_init, c_base, fpu), served in the plain PUCT search only
+SPEC_KEYS = SEARCH_KEYS + ("puct",)
 
 
 def check_search(search, player, what="search"):
-    """the search modes of one tree player of BatchedArena: None, or a dict with any of SEARCH_KEYS, which take the values of
-    BatchedAlphaZeroPlayer's keywords and its checks (mcts.check_symmetry / check_leaf_batch, gumbel.check_gumbel / _batch / _full).
+    """the search modes of one tree player of BatchedArena: None, or a dict with any of SPEC_KEYS, which take the values of
+    BatchedAlphaZeroPlayer's keywords and its checks (mcts.check_symmetry / check_leaf_batch, gumbel.check_gumbel / _batch / _full,
+    puct.check_puct).
     Returns None or the dict with every key filled in; ValueError -- before any device work -- for anything else, for a `player` that
     has no tree ("random", "greedy") and for a mode the player's kind cannot run (rollout "mcts", a network routed to the external
     evaluator).  `player` None: a network not known yet -- the checks that need none."""
@@ -80,13 +84,13 @@ def check_search(search, player, what="search"):
     if search is None:
         return None
     if not isinstance(search, dict):
-        raise ValueError(f"{what}: expected None or a dict with any of {list(SEARCH_KEYS)}, got {search!r}")
-    unknown = sorted(set(search) - set(SEARCH_KEYS), key=str)
+        raise ValueError(f"{what}: expected None or a dict with any of {list(SPEC_KEYS)}, got {search!r}")
+    unknown = sorted(set(search) - set(SPEC_KEYS), key=str)
     if unknown:
-        raise ValueError(f"{what}: unknown keys {unknown}; expected {list(SEARCH_KEYS)}")
+        raise ValueError(f"{what}: unknown keys {unknown}; expected {list(SPEC_KEYS)}")
     if player in ("random", "greedy"):
         raise ValueError(f"{what}: player '{player}' has no search tree to take search modes")
-    spec = {"symmetry": None, "leaf_batch": None, "gumbel": None, "gumbel_batch": 1, "gumbel_full": False}
+    spec = {"symmetry": None, "leaf_batch": None, "gumbel": None, "gumbel_batch": 1, "gumbel_full": False, "puct": None}
     spec.update(search)
     neural = player != "mcts"  # "fake", the closed-form test network, is searched as a network is
     nn = None if isinstance(player, str) else player
@@ -96,6 +100,8 @@ def check_search(search, player, what="search"):
     check_gumbel(spec["gumbel"], nn, spec["leaf_batch"], neural)
     check_gumbel_batch(spec["gumbel_batch"], spec["gumbel"], spec["symmetry"])
     check_gumbel_full(spec["gumbel_full"], spec["gumbel"])
+    from .puct import check_puct
+    check_puct(spec["puct"], nn, spec["symmetry"], spec["leaf_batch"], spec["gumbel"], neural=neural)
     return spec
 
 
@@ -117,8 +123,8 @@ class BatchedArena:
     `opponent` is "random", "greedy", "mcts" or another network (evaluation against a previous network).
     Returns the reference's stats dict.
 
-    `search` / `opponent_search` (check_search: symmetry, leaf_batch, gumbel, gumbel_batch, gumbel_full, as BatchedAlphaZeroPlayer takes
-    them) put player 1's / the opponent's tree search in those modes; a tree player then plays the move of its mode
+    `search` / `opponent_search` (check_search: symmetry, leaf_batch, gumbel, gumbel_batch, gumbel_full, puct, as BatchedAlphaZeroPlayer
+    takes them) put player 1's / the opponent's tree search in those modes; a tree player then plays the move of its mode
     (SelfPlayEngine.player_moves: the Gumbel move in the Gumbel mode).  `opening_plies` = k seeds the first k plies (passes count) of
     every round: a visit-based tree player samples its move from the visit counts (temperature 1, the AZ_P_MOVE_SAMPLE draw of seed,
     game id and ply) while the root's ply is < k and plays the most visited one from ply k on; a Gumbel player searches and moves with
@@ -194,6 +200,8 @@ class BatchedArena:
                 eng.set_gumbel_batch(gb)
             if spec["gumbel_full"]:
                 eng.set_gumbel_full(True)
+        if spec is not None and spec["puct"] is not None:
+            eng.set_puct(spec["puct"])
         return eng
 
     def play_games(self, n_rounds, start_player=None, return_stats=True, shard=True, record_moves=False):

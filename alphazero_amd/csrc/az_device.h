@@ -74,11 +74,28 @@ AZ_D float az_det_tanhf(float x) {
     return x < 0.0f ? -t : t;
 }
 
-AZ_D double az_det_log(double x) {
+// the bits of a double and back, on either side: the device's own casts there, a copy on the host (az_det_log below is host code too:
+// az_puct_c of the C ABI is the arithmetic the kernels run)
+AZ_HD u64 az_f64_bits(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (u64)__double_as_longlong(x);
+#else
+    u64 u; __builtin_memcpy(&u, &x, sizeof(u)); return u;
+#endif
+}
+AZ_HD double az_f64_of_bits(u64 u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __longlong_as_double((long long)u);
+#else
+    double x; __builtin_memcpy(&x, &u, sizeof(x)); return x;
+#endif
+}
+
+AZ_HD double az_det_log(double x) {
     if (!(x > 0.0)) return -__builtin_inf();
-    u64 u = (u64)__double_as_longlong(x);
+    u64 u = az_f64_bits(x);
     int e = (int)((u >> 52) & 0x7ff) - 1023;
-    double m = __longlong_as_double((long long)((u & 0x000fffffffffffffULL) | 0x3ff0000000000000ULL));
+    double m = az_f64_of_bits((u & 0x000fffffffffffffULL) | 0x3ff0000000000000ULL);
     if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
     double s = (m - 1.0) / (m + 1.0);
     double z = s * s;

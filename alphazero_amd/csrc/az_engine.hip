@@ -18,6 +18,8 @@
 // (Opt-in, default off: az_engine_set_proof_backup backs proven wins, losses and draws up the tree -- MCTS-Solver: a node is proven as
 // soon as its children decide it, walks stop on proven nodes, selection and the policy target respect the proofs -- k_step_proof below,
 // propagate_proofs_grp, proof_mode / proof_count in move_policy.)
+// (Opt-in, default off: az_engine_set_puct frees PUCT's exploration constant, its growth with the parent's visits and the Q an
+// unvisited child is assumed to have (first-play urgency) -- k_step_puct below, puct_c / puct_fpu_q / puct_key.)
 //
 // HBM layout
 //   boards   : 2 x u64 bitboards + int8 side-to-move per slot (root and current leaf), SoA over slots
@@ -162,6 +164,10 @@ struct EngDev {
     // ended on such a node and the plies whose policy counts the proofs changed, since the last k_reset_all (the slot's own words,
     // summed when the stats are read).  Null unless the mode is on: then no kernel touches them.  (Last: the fields above keep their place.)
     int *pf;
+    // az_engine_set_puct (k_step_puct): the exploration constant's c_init and c_base (0: no growth) and first-play
+    // urgency's reduction (negative: off).  Read by the k_step_puct kernels alone, which are launched only while the triple is not the
+    // neutral (1.0, 0, off).  (After pf: the fields above keep their place.)
+    double puct_cinit, puct_cbase, puct_fpu;
 };
 // tag = ec_tag(hash, the claimer's stamp), 0 = empty: claimed by one device-scope compare-and-swap, never rewritten within a run; the
 // key is written by the claimer in the same kernel, the payload in the group's next one
@@ -218,6 +224,16 @@ AZ_D double grp_max(double v) {  // over the game's 16 lanes, by DPP (az_device.
     v = fmax(v, __longlong_as_double((long long)az_dpp64<AZ_DPP_SWAP2>((u64)__double_as_longlong(v))));
     v = fmax(v, __longlong_as_double((long long)az_dpp64<AZ_DPP_HMIRROR>((u64)__double_as_longlong(v))));
     v = fmax(v, __longlong_as_double((long long)az_dpp64<AZ_DPP_MIRROR>((u64)__double_as_longlong(v))));
+    return v;
+}
+// The sum over the game's 16 lanes as a pairwise tree with strides 1, 2, 4, 8, by grp_max's DPP steps: after the two quad steps the four
+// lanes of a quad hold one value, so the half mirror (lane 7 - i: the other quad) hands over what lane i ^ 4 holds, and the row mirror
+// what lane i ^ 8 does.  Double addition commutes: every lane ends with the same bits (az_engine_set_puct's vis).
+AZ_D double grp_sum_f64(double v) {
+    v = v + __longlong_as_double((long long)az_dpp64<AZ_DPP_SWAP1>((u64)__double_as_longlong(v)));
+    v = v + __longlong_as_double((long long)az_dpp64<AZ_DPP_SWAP2>((u64)__double_as_longlong(v)));
+    v = v + __longlong_as_double((long long)az_dpp64<AZ_DPP_HMIRROR>((u64)__double_as_longlong(v)));
+    v = v + __longlong_as_double((long long)az_dpp64<AZ_DPP_MIRROR>((u64)__double_as_longlong(v)));
     return v;
 }
 AZ_D u64 grp_sum_u64(u64 v) {
@@ -335,9 +351,11 @@ AZ_D int pick4(int v0, int v1, int v2, int v3, int r) { return r == 0 ? v0 : (r 
 // child's index among the parent's children.  DRAW false: ties go to the lowest index whatever tie_mode says, no Philox draw.
 // MASKED (az_engine_set_proof_backup): bit r of `skip` takes this lane's child of round r out of the ballot (its key is -inf already,
 // so it does not set the maximum either; a voter mask, not a key: absent lanes carry -inf too and would win a ballot at -inf).
-template <bool DRAW = true, bool MASKED = false>
+// CARRYQ (az_engine_set_puct): cq0 .. cq3 = the Q of this lane's child of round 0 .. 3 (by value, as the picks below); the chosen
+// child's comes back in chosen.Q by one more 64-bit shuffle (first-play urgency reads the parent's Q at the next level).
+template <bool DRAW = true, bool MASKED = false, bool CARRYQ = false>
 AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int depth, const Scored &s, int nvote, int none_err,
-                        int sub, Node &chosen, int skip = 0) {
+                        int sub, Node &chosen, int skip = 0, double cq0 = 0.0, double cq1 = 0.0, double cq2 = 0.0, double cq3 = 0.0) {
     double best = grp_max(fmax(fmax(s.key[0], s.key[1]), fmax(s.key[2], s.key[3])));
     u32 mask[4];
     int cnt = 0;
@@ -367,6 +385,7 @@ AZ_D int choose_max_grp(const EngDev &E, const u32 &gid, int ply, int sim, int d
     chosen.first = __shfl(pick4(s.first[0], s.first[1], s.first[2], s.first[3], rsel), lsel, LPG);
     set_node_tail(chosen, (u32)__shfl(pick4((int)s.tail[0], (int)s.tail[1], (int)s.tail[2], (int)s.tail[3], rsel), lsel, LPG));
     chosen.Q = 0.0; chosen.P = 0.0; chosen.parent = 0;  // not needed by the walk
+    if (CARRYQ) chosen.Q = __shfl(rsel == 0 ? cq0 : (rsel == 1 ? cq1 : (rsel == 2 ? cq2 : cq3)), lsel, LPG);
     return rsel * LPG + lsel;
 }
 
@@ -417,6 +436,24 @@ AZ_HD int forced_pruned(int n, double q, double p, int root_n, double sq, double
 }
 
 // ---------------------------------------------------------------------------------------------
+// PUCT exploration settings (az_engine_set_puct; the contract stands in include/az_amd.h).  Every operation is one
+// IEEE double operation in the order written (-ffp-contract=off), sqrt the correctly rounded one, log az_det_log.  The two rules as
+// host-callable arithmetic (az_puct_c / az_puct_key are these on the host):
+//   c    the exploration constant under a parent of parent_n visits
+//   qu   the Q an unvisited child is assumed to have under first-play urgency (fpu >= 0): parent_q the parent's stored Q, vis the prior
+//        mass of the parent's visited children; one value per parent, so the kernel takes its square root once per tree level
+//   key  a child's score: sq = sqrt((double)parent.N), c and qu as above (qu is read only where the child is unvisited and fpu >= 0)
+// ---------------------------------------------------------------------------------------------
+AZ_HD double puct_c(int parent_n, double c_init, double c_base) {
+    return c_base > 0.0 ? c_init + az_det_log(((1.0 + (double)parent_n) + c_base) / c_base) : c_init;
+}
+AZ_HD double puct_fpu_q(double parent_q, double vis, double fpu) { return (-parent_q) - fpu * sqrt(vis); }
+AZ_HD double puct_key(double q_child, double p_child, int n_child, double sq, double c, double qu, double fpu) {
+    const double q = (n_child > 0 || fpu < 0.0) ? q_child : qu;
+    return q + ((c * p_child) * sq) / (double)(1 + n_child);
+}
+
+// ---------------------------------------------------------------------------------------------
 // PUCT selection (mcts.py:44-46, 137) for k_step and k_step_multi.  k_step is walker j = 0 of a lock-step of one: no virtual count.
 // leaf_batch = K > 1 (az_engine_set_leaf_batch): K simulations per slot and lock-step, kept apart by virtual loss.
 // The reference searches strictly one simulation after the other (mcts.py:127-171 select_node, 197-223 back_propagate,
@@ -436,10 +473,38 @@ AZ_HD int forced_pruned(int n, double q, double p, int root_n, double sq, double
 // PROOF (az_engine_set_proof_backup; the k_step_proof kernels only): `mover` = the player to move at the parent.  A
 // child proven as a loss for the mover is no candidate -- key -inf and no vote -- unless every child is one (a root only: a node below
 // it whose children are all proven is proven itself and stops the walk); at the root a child proven as the mover's win takes +inf.
-template <bool FORCED = false, bool PROOF = false>
+// PUCT (az_engine_set_puct; the k_step_puct kernels only): the keys are puct_key's under the engine's c_init, c_base
+// and fpu; parent.Q is the parent's real Q, and the chosen child's travels on in chosen.Q.  One walker per lock-step (leaf_batch > 1 is
+// refused): no virtual count.  The children are loaded first, all four rounds, because an unvisited child's key reads the prior mass
+// of the visited ones: four additions in the lane, four DPP steps over the group.
+template <bool FORCED = false, bool PROOF = false, bool PUCT = false>
 AZ_D int pick_child_vl_grp(const EngDev &E, int g, const Node *pool, const Node &parent, int pnode, const int (&vpath)[MLB], int j,
                            int ply, int sim, int depth, int sub, Node &chosen, double kf = 0.0, bool *forced_pick = nullptr, int mover = 0) {
     const int fc = parent.first;
+    if (PUCT) {
+        const double sq = sqrt((double)parent.N);
+        const double cc = puct_c(parent.N, E.puct_cinit, E.puct_cbase), fpu = E.puct_fpu;
+        Scored s;
+        Node c0, c1, c2, c3;  // named, not an array: nothing here is indexed by a variable (choose_max_grp's note on scratch)
+        c0.Q = c1.Q = c2.Q = c3.Q = 0.0; c0.P = c1.P = c2.P = c3.P = 0.0;
+        const bool h0 = load_child_grp(pool, parent, 0, sub, s, c0), h1 = load_child_grp(pool, parent, 1, sub, s, c1);
+        const bool h2 = load_child_grp(pool, parent, 2, sub, s, c2), h3 = load_child_grp(pool, parent, 3, sub, s, c3);
+        double qu = 0.0;
+        if (fpu >= 0.0) {  // uniform over the engine
+            double vis = 0.0;
+            vis = vis + ((h0 && s.N[0] > 0) ? c0.P : 0.0);
+            vis = vis + ((h1 && s.N[1] > 0) ? c1.P : 0.0);
+            vis = vis + ((h2 && s.N[2] > 0) ? c2.P : 0.0);
+            vis = vis + ((h3 && s.N[3] > 0) ? c3.P : 0.0);
+            qu = puct_fpu_q(parent.Q, grp_sum_f64(vis), fpu);
+        }
+        if (h0) s.key[0] = puct_key(c0.Q, c0.P, s.N[0], sq, cc, qu, fpu);
+        if (h1) s.key[1] = puct_key(c1.Q, c1.P, s.N[1], sq, cc, qu, fpu);
+        if (h2) s.key[2] = puct_key(c2.Q, c2.P, s.N[2], sq, cc, qu, fpu);
+        if (h3) s.key[3] = puct_key(c3.Q, c3.P, s.N[3], sq, cc, qu, fpu);
+        return fc + choose_max_grp<true, false, true>(E, E.game_id[g], ply, sim, depth, s, 4 * LPG, ERR_INTERNAL, sub, chosen, 0,
+                                                      c0.Q, c1.Q, c2.Q, c3.Q);
+    }
     int vp = 0, vc[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < MLB; ++i) {
@@ -499,7 +564,8 @@ AZ_D int pick_child_gumbel_grp(const EngDev &E, int g, const Node *pool, const N
 // FORCED: the selection at depth 0 applies the forced-playout rule with kf (0: not a forced ply); below the root nothing changes.
 // PROOF (az_engine_set_proof_backup): below the root the walk stops on an F_PROVEN node as on a terminal one, and the scorer prunes
 // by the proofs; the mover at depth d is the root's player times (-1)^d (a pass is an action: the side to move alternates strictly).
-template <bool GUMBEL = false, bool FORCED = false, bool PROOF = false>
+// PUCT (az_engine_set_puct): the scorer is pick_child_vl_grp's PUCT one; wk.cur then carries every node's real Q down the walk.
+template <bool GUMBEL = false, bool FORCED = false, bool PROOF = false, bool PUCT = false>
 AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], int j, int ply, int sim, int sub, Walk &wk,
                    double kf = 0.0, bool *forced_pick = nullptr) {
     const int root_player = wk.b.player;  // PROOF: wk stands on the root when the step kernel calls
@@ -515,9 +581,9 @@ AZ_D void walk_grp(const EngDev &E, int g, Node *pool, const int (&vpath)[MLB], 
         }
         Node ch;
         const int c = GUMBEL ? pick_child_gumbel_grp(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch)
-                             : pick_child_vl_grp<FORCED, PROOF>(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch,
-                                                                FORCED && wk.plen == 1 ? kf : 0.0, forced_pick,
-                                                                PROOF ? (((wk.plen - 1) & 1) ? -root_player : root_player) : 0);
+                             : pick_child_vl_grp<FORCED, PROOF, PUCT>(E, g, pool, wk.cur, wk.node, vpath, j, ply, sim, wk.plen - 1, sub, ch,
+                                                                      FORCED && wk.plen == 1 ? kf : 0.0, forced_pick,
+                                                                      PROOF ? (((wk.plen - 1) & 1) ? -root_player : root_player) : 0);
         wk.node = c; wk.cur = ch;
         if (sub == wk.plen) wk.my_path = c;
         ++wk.plen;
@@ -683,6 +749,8 @@ AZ_D void apply_root_noise_grp(const EngDev &E, int g, Node *pool, int root, con
 // is updated by its own lane in one memory round trip (reward sign alternates from the leaf up);
 // paths longer than 16 nodes fall back to chasing parent pointers.  `mine` = this lane's path node (already
 // loaded), returns true when the fast path ran (lane 0 then holds the root with its N already incremented).
+// KEEPQ (az_engine_set_puct): `mine` takes the Q it has just written too (the forwarded root's real Q).
+template <bool KEEPQ = false>
 AZ_D bool back_propagate_grp(Node *pool, int len, int my_node, Node &mine, int leaf, int player_to_play, double outcome, int sub) {
     double reward;
     if (fabs(outcome) < 1e-4) reward = 0.0;
@@ -693,6 +761,7 @@ AZ_D bool back_propagate_grp(Node *pool, int len, int my_node, Node &mine, int l
             const double r = (reward == 0.0) ? 0.0 : ((up & 1) ? -reward : reward);
             pool[my_node].Q = ((double)mine.N * mine.Q + r) / (double)(mine.N + 1);
             pool[my_node].N = mine.N + 1;
+            if (KEEPQ) mine.Q = ((double)mine.N * mine.Q + r) / (double)(mine.N + 1);
             mine.N += 1;
         }
         return true;
@@ -853,7 +922,9 @@ __device__ unsigned long long az_step_probe[4096 * 8];
 // PROOF (az_engine_set_proof_backup, k_step_proof): the backup of an LS_TERM leaf is followed by
 // propagate_proofs_grp, the walk and its scorer take the proofs into account, and a walk that ends on an F_PROVEN node is LS_TERM: no
 // row, no solve, no cache lookup.  PROOF false is the kernel as it was.
-template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false, bool EXACT = false, bool PROOF = false>
+// PUCT (az_engine_set_puct, k_step_puct): the walk scores by puct_key, and the root this kernel's backup forwards to
+// its own walk carries the Q that backup has just written (first-play urgency reads it).  PUCT false is the kernel as it was.
+template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false, bool EXACT = false, bool PROOF = false, bool PUCT = false>
 AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
@@ -923,12 +994,13 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr
         }
         PSTAMP(2)
         if (ok) {
-            bool fast = back_propagate_grp(pool, plen_prev, path_prev, mine, leaf, lb.player, outcome, sub);
+            bool fast = back_propagate_grp<PUCT>(pool, plen_prev, path_prev, mine, leaf, lb.player, outcome, sub);
             if (fast && SELECT) {  // lane 0 holds the root (path[0]) with its new visit count: forward it
                 fwd.N = __shfl(mine.N, 0, LPG);
                 fwd.first = __shfl(mine.first, 0, LPG);
                 set_node_tail(fwd, (u32)__shfl((int)node_tail(mine), 0, LPG));
                 fwd.Q = 0.0; fwd.P = 0.0; fwd.parent = -1;
+                if (PUCT) fwd.Q = __shfl(mine.Q, 0, LPG);
                 // the root itself may be the leaf that just got its children (first visit of an unexpanded root)
                 have_root = (leaf != node) || st != LS_EVAL;
             }
@@ -970,6 +1042,7 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr
         const int no_walkers[MLB] = {};  // walker j = 0: nobody walked before it in this lock-step, every virtual count is 0
         if (FORCED) walk_grp<false, true>(E, g, pool, no_walkers, 0, ply, sim, sub, wk, budget == CAP_FULL ? E.kforced : 0.0, &forced_pick);
         else if (PROOF) walk_grp<false, false, true>(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
+        else if (PUCT) walk_grp<false, false, false, true>(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
         else walk_grp(E, g, pool, no_walkers, 0, ply, sim, sub, wk);
         PSTAMP(5)
         E.path[(size_t)g * LPG + sub] = wk.my_path;
@@ -1070,6 +1143,16 @@ template <bool BACKUP, bool SELECT>
 __global__ __launch_bounds__(256) void k_step_proof_exact_cached(EngDev E, int sim, int g0, int g1) {
     __shared__ u64 s_xstk[EXACT_STK_WORDS];
     step_grp<BACKUP, SELECT, false, false, true, true, true>(E, sim, g0, g1, s_xstk);
+}
+
+// and the plain lock-step under exploration settings other than (1.0, 0, off) (az_engine_set_puct), without and with the cache
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_puct(EngDev E, int sim, int g0, int g1) {
+    step_grp<BACKUP, SELECT, false, false, false, false, false, true>(E, sim, g0, g1);
+}
+template <bool BACKUP, bool SELECT>
+__global__ __launch_bounds__(256) void k_step_puct_cached(EngDev E, int sim, int g0, int g1) {
+    step_grp<BACKUP, SELECT, false, false, true, false, false, true>(E, sim, g0, g1);
 }
 
 // One lock-step of K walkers per slot: BACKUP of the kb walkers the previous lock-step selected (their rows are evaluated), then
@@ -2636,6 +2719,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.ec_mask = 0; d.ec_limit = 0; d.ec_stride = 0;
     d.exact_max = 0; d.x_solved = nullptr; d.x_nodes = nullptr;
     d.pf = nullptr;
+    d.puct_cinit = 1.0; d.puct_cbase = 0.0; d.puct_fpu = -1.0;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2758,7 +2842,9 @@ static int forward(az_engine *e, const Chain &c, const int *cnt, int cap, int st
     return az_sym_reduce(&d.gd, e->sym_mask, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
 }
 
-static SearchMode search_mode(const EngDev &d) { return SearchMode{d.rollout != 0, d.gm, d.K, d.nval != nullptr, d.budget != nullptr, d.kforced > 0.0, d.exact_max, d.pf != nullptr}; }
+// az_engine_set_puct: the exploration settings are anything but the neutral (1.0, 0, off)
+static bool puct_on(const EngDev &d) { return !puct_neutral(d.puct_cinit, d.puct_cbase, d.puct_fpu); }
+static SearchMode search_mode(const EngDev &d) { return SearchMode{d.rollout != 0, d.gm, d.K, d.nval != nullptr, d.budget != nullptr, d.kforced > 0.0, d.exact_max, d.pf != nullptr, puct_on(d)}; }
 
 // The one place that names the step kernels: launch `a` of the plan on chain c.  Each family is instantiated for three (backup, select)
 // pairs -- the first step, the later ones, the last backup; never <false, false> -- and the two Gumbel families for `full` on and off.
@@ -2798,6 +2884,10 @@ static void launch_step_as(const SearchPlan &p, const Chain &c, int n_sim, const
                 if (d.ec_hdr) hipLaunchKernelGGL((k_step_proof_cached<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
                 else hipLaunchKernelGGL((k_step_proof<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
             }
+            break;
+        case SF_STEP_PUCT:
+            if (d.ec_hdr) hipLaunchKernelGGL((k_step_puct_cached<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            else hipLaunchKernelGGL((k_step_puct<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
             break;
         case SF_STEP_MULTI: hipLaunchKernelGGL((k_step_multi<B, S>), gg, gb, 0, c.st, d, a.t, a.kb, a.kt); break;
         case SF_STEP_GUMBEL:
@@ -2965,6 +3055,7 @@ static int refuse_beside_cap_or_forced(const az_engine *e, const char *who, cons
     AZ_REQUIRE(d.kforced == 0.0, AZ_EINVAL, "%s: forced playouts are on (az_engine_set_forced_playouts, k = %g) and are served %s only; switch them off first", who, d.kforced, where);
     AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "%s: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and are served %s only; switch them off first", who, d.exact_max, where);
     AZ_REQUIRE(!d.pf, AZ_EINVAL, "%s: proof backup is on (az_engine_set_proof_backup) and is served %s only; switch it off first", who, where);
+    AZ_REQUIRE(!puct_on(d), AZ_EINVAL, "%s: PUCT exploration settings are on (az_engine_set_puct, c_init = %g, c_base = %g, fpu = %g) and are served %s only; switch them off first", who, d.puct_cinit, d.puct_cbase, d.puct_fpu, where);
     return AZ_OK;
 }
 
@@ -3784,6 +3875,7 @@ extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_playout_cap: the playout cap is not served for %s", why);
         AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "az_engine_set_playout_cap: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and do not combine with the playout cap; switch them off first", d.exact_max);
         AZ_REQUIRE(!d.pf, AZ_EINVAL, "az_engine_set_playout_cap: proof backup is on (az_engine_set_proof_backup) and does not combine with the playout cap; switch it off first");
+        AZ_REQUIRE(!puct_on(d), AZ_EINVAL, "az_engine_set_playout_cap: PUCT exploration settings are on (az_engine_set_puct) and do not combine with the playout cap; switch them off first");
         if (n_fast == d.cap_nfast && p_full == d.cap_pfull) return AZ_OK;
     }
     AZ_TRY(enter(e));
@@ -3822,6 +3914,7 @@ extern "C" int az_engine_set_forced_playouts(az_engine *e, double k) {
         AZ_REQUIRE(d.exact_max == 0, AZ_EINVAL, "az_engine_set_forced_playouts: exact endgames are on (az_engine_set_exact_endgame, max_empties = %d) and do not combine with forced playouts; switch them off first", d.exact_max);
     }
     if (k > 0.0) AZ_REQUIRE(!d.pf, AZ_EINVAL, "az_engine_set_forced_playouts: proof backup is on (az_engine_set_proof_backup) and does not combine with forced playouts; switch it off first");
+    if (k > 0.0) AZ_REQUIRE(!puct_on(d), AZ_EINVAL, "az_engine_set_forced_playouts: PUCT exploration settings are on (az_engine_set_puct) and do not combine with forced playouts; switch them off first");
     if (k == d.kforced) return AZ_OK;
     AZ_TRY(enter(e));
     if (k > 0.0 && !e->forced_picks) AZ_TRY(dev_alloc(e, &e->forced_picks, (size_t)d.G));
@@ -3867,6 +3960,7 @@ extern "C" int az_engine_set_exact_endgame(az_engine *e, int32_t max_empties) {
     if (max_empties > 0) {
         const char *why = exact_endgame_refusal(e->cfg.evaluator, e->sym_mask != 0, e->symr_mask != 0, e->leaf_batch, d.gm, d.cap_nfast > 0, d.kforced > 0.0);
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_exact_endgame: exact endgames are not served for %s", why);
+        AZ_REQUIRE(!puct_on(d), AZ_EINVAL, "az_engine_set_exact_endgame: PUCT exploration settings are on (az_engine_set_puct) and do not combine with exact endgames; switch them off first");
     }
     if (max_empties == d.exact_max) return AZ_OK;
     AZ_USABLE(e, "az_engine_set_exact_endgame");
@@ -3950,6 +4044,7 @@ extern "C" int az_engine_set_proof_backup(az_engine *e, int32_t on) {
     if (on) {
         const char *why = proof_backup_refusal(e->cfg.evaluator, e->sym_mask != 0, e->symr_mask != 0, e->leaf_batch, d.gm, d.cap_nfast > 0, d.kforced > 0.0);
         AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_proof_backup: proof backup is not served for %s", why);
+        AZ_REQUIRE(!puct_on(d), AZ_EINVAL, "az_engine_set_proof_backup: PUCT exploration settings are on (az_engine_set_puct) and do not combine with proof backup; switch them off first");
     }
     if ((on != 0) == (d.pf != nullptr)) return AZ_OK;
     AZ_USABLE(e, "az_engine_set_proof_backup");
@@ -4002,6 +4097,42 @@ extern "C" int az_engine_root_proofs(az_engine *e, int8_t *d_out) {
     AZ_HIP(hipGetLastError());
     AZ_HIP(hipStreamSynchronize(e->stream));
     return AZ_OK;
+}
+
+// ---- PUCT exploration settings (k_step_puct, puct_c, puct_key) ---------------------------------------------------
+extern "C" int az_engine_set_puct(az_engine *e, double c_init, double c_base, double fpu) {
+    AZ_SETTER(e, "az_engine_set_puct");
+    EngDev &d = e->d;
+    AZ_REQUIRE(puct_c_init_ok(c_init), AZ_EINVAL, "az_engine_set_puct: c_init must be finite and in (0, 64], got %g", c_init);
+    AZ_REQUIRE(puct_c_base_ok(c_base), AZ_EINVAL, "az_engine_set_puct: c_base must be 0 (no growth) or finite and in [1, 1e9], got %g", c_base);
+    AZ_REQUIRE(puct_fpu_ok(fpu), AZ_EINVAL, "az_engine_set_puct: fpu must be negative (off) or finite and in [0, 4], got %g", fpu);
+    if (fpu < 0.0) fpu = -1.0;  // the canonical off
+    if (!puct_neutral(c_init, c_base, fpu)) {
+        const char *why = puct_refusal(e->cfg.evaluator, e->sym_mask != 0, e->symr_mask != 0, e->leaf_batch, d.gm, d.cap_nfast > 0, d.kforced > 0.0,
+                                       d.exact_max, d.pf != nullptr);
+        AZ_REQUIRE(!why, AZ_EINVAL, "az_engine_set_puct: PUCT exploration settings are not served for %s", why);
+    }
+    if (c_init == d.puct_cinit && c_base == d.puct_cbase && fpu == d.puct_fpu) return AZ_OK;
+    AZ_TRY(enter(e));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    d.puct_cinit = c_init; d.puct_cbase = c_base; d.puct_fpu = fpu;
+    // other kernels, and the three settings travel by value in the launch arguments: nothing captured before may be replayed
+    drop_graphs(e);
+    return AZ_OK;
+}
+
+extern "C" int az_engine_puct(az_engine *e, double *c_init, double *c_base, double *fpu) {
+    AZ_REQUIRE(e && c_init && c_base && fpu, AZ_EINVAL, "null argument");
+    *c_init = e->d.puct_cinit; *c_base = e->d.puct_cbase; *fpu = e->d.puct_fpu;
+    return AZ_OK;
+}
+
+extern "C" double az_puct_c(int32_t parent_n, double c_init, double c_base) { return puct_c(parent_n, c_init, c_base); }
+
+extern "C" double az_puct_key(double q_child, double p_child, int32_t n_child, int32_t parent_n, double parent_q, double vis,
+                              double c_init, double c_base, double fpu) {
+    return puct_key(q_child, p_child, n_child, sqrt((double)parent_n), puct_c(parent_n, c_init, c_base),
+                    fpu >= 0.0 ? puct_fpu_q(parent_q, vis, fpu) : 0.0, fpu);
 }
 
 // ---- leaf evaluation cache (k_step_cached) ------------------------------------------------------------------------

@@ -19,13 +19,14 @@ struct SearchMode {
     bool forced;   // forced playouts are on
     int exact;     // exact endgames: the empties limit of a solved leaf (az_engine_set_exact_endgame; 0: off)
     bool proof;    // proof backup is on (az_engine_set_proof_backup)
+    bool puct;     // the exploration settings are not the neutral (1.0, 0, off) (az_engine_set_puct)
 };
 
 // the kernel family of a search's lock-steps
-enum SearchFamily { SF_ROLLOUT, SF_STEP, SF_STEP_CAP, SF_STEP_FORCED, SF_STEP_CAP_FORCED, SF_STEP_MULTI, SF_STEP_GUMBEL, SF_STEP_GUMBEL_MULTI, SF_STEP_EXACT, SF_STEP_PROOF };
+enum SearchFamily { SF_ROLLOUT, SF_STEP, SF_STEP_CAP, SF_STEP_FORCED, SF_STEP_CAP_FORCED, SF_STEP_MULTI, SF_STEP_GUMBEL, SF_STEP_GUMBEL_MULTI, SF_STEP_EXACT, SF_STEP_PROOF, SF_STEP_PUCT };
 
 inline const char *search_family_name(SearchFamily f) {
-    static const char *const name[] = {"k_rollout_step", "k_step", "k_step_cap", "k_step_forced", "k_step_cap_forced", "k_step_multi", "k_step_gumbel", "k_step_gumbel_multi", "k_step_exact", "k_step_proof"};
+    static const char *const name[] = {"k_rollout_step", "k_step", "k_step_cap", "k_step_forced", "k_step_cap_forced", "k_step_multi", "k_step_gumbel", "k_step_gumbel_multi", "k_step_exact", "k_step_proof", "k_step_puct"};
     return name[f];
 }
 
@@ -74,6 +75,7 @@ inline SearchPlan plan_search(const SearchMode &m, int n_sim) {
     else if (m.cap) p.family = SF_STEP_CAP;  // a slot past its budget idles: no walk, no row
     else if (m.proof) { p.family = SF_STEP_PROOF; p.exact = m.exact > 0; }  // one family: exact endgames under it are a property of the plan
     else if (m.exact > 0) p.family = SF_STEP_EXACT;  // the plain search alone (exact_endgame_refusal): a late leaf is solved, not evaluated
+    else if (m.puct) p.family = SF_STEP_PUCT;  // the plain search alone (puct_refusal): k_step's lock-steps with puct_key's scores
     p.launches = p.L + 1;
     return p;
 }
@@ -212,6 +214,22 @@ inline const char *exact_endgame_refusal(int evaluator, bool sym, bool sym_rando
 // endgames, the evaluation cache and slot groups.  The mode that refuses, as the setters name it, or null.
 inline const char *proof_backup_refusal(int evaluator, bool sym, bool sym_random, int leaf_batch, int gm, bool cap, bool forced) {
     return exact_endgame_refusal(evaluator, sym, sym_random, leaf_batch, gm, cap, forced);
+}
+
+// ---- PUCT exploration settings (az_engine_set_puct) ----------------------------------------------------------------
+// The ranges of the three settings, and the triple that is the mode off: c_init = 1.0, c_base = 0 (no growth), fpu negative (off).
+inline bool puct_c_init_ok(double c_init) { return c_init > 0.0 && c_init <= 64.0; }                       // NaN fails every compare
+inline bool puct_c_base_ok(double c_base) { return c_base == 0.0 || (c_base >= 1.0 && c_base <= 1e9); }
+inline bool puct_fpu_ok(double fpu) { return fpu < 0.0 || (fpu >= 0.0 && fpu <= 4.0); }
+inline bool puct_neutral(double c_init, double c_base, double fpu) { return c_init == 1.0 && c_base == 0.0 && fpu < 0.0; }
+// Where the mode is served: the plain PUCT search of a network or fake engine, one leaf per slot and lock-step, with slot groups and
+// the evaluation cache or without.  Every other mode is a follow-up (their composed host models are not written): the mode that
+// refuses, as the setters name it, or null.
+inline const char *puct_refusal(int evaluator, bool sym, bool sym_random, int leaf_batch, int gm, bool cap, bool forced, int exact, bool proof) {
+    if (const char *why = exact_endgame_refusal(evaluator, sym, sym_random, leaf_batch, gm, cap, forced)) return why;
+    if (exact > 0) return "exact endgames (az_engine_set_exact_endgame)";
+    if (proof) return "proof backup (az_engine_set_proof_backup)";
+    return nullptr;
 }
 
 // What a captured search is keyed by.  (A proof search is SF_STEP_PROOF whatever exact endgames say: the family keeps its graphs apart

@@ -489,6 +489,26 @@ class SelfPlayEngine:
         check(lib().az_engine_root_proofs(self.h, out.data_ptr()))
         return out
 
+    def set_puct(self, spec=None, c_base=None, fpu=None):
+        """the PUCT exploration settings (az_engine_set_puct): `spec` as alphazero_amd.puct takes it -- None (off: the
+        reference's PUCT), a number (c_init) or a dict of c_init, c_base, fpu -- or the three values themselves,
+        set_puct(c_init, c_base, fpu) (fpu None or negative: off).  The exploration constant of a node with N visits is c_init +
+        log((1 + N + c_base) / c_base) (c_base 0: c_init), an unvisited child's Q is the parent's value - fpu * sqrt(the prior mass of
+        the visited children).  (1.0, 0, off) is the mode off.  Plain search of EVAL_NET / EVAL_FAKE engines, with slot groups and the
+        evaluation cache or without; any other mode is a ValueError that names it.  The settings may change between two searches."""
+        from .puct import parse
+        if c_base is not None or fpu is not None:
+            spec = {"c_init": 1.0 if spec is None else spec, "c_base": 0.0 if c_base is None else c_base, "fpu": fpu}
+        c_init, c_base, fpu = parse(spec)
+        check(lib().az_engine_set_puct(self.h, c_init, c_base, fpu))
+
+    @property
+    def puct(self):
+        """(c_init, c_base, fpu) in force; fpu -1.0: off.  (1.0, 0.0, -1.0) is the mode off"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        check(lib().az_engine_puct(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return (a.value, b.value, c.value)
+
     def set_eval_cache(self, mode=None, capacity=0, stone_limit=0):
         """the leaf evaluation cache of run() (az_engine_set_eval_cache): each slot group keeps the network's
         outputs by exact position, so a leaf another game of the wave already sent through the network takes no batch row; the

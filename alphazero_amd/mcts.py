@@ -58,6 +58,7 @@ MAX_LEAF_BATCH = 16  # AZ_MAX_LEAF_BATCH (include/az_amd.h)
 from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full  # noqa: E402  (the Gumbel root search's spec and refusals)
 from .endgame import check_exact_endgame  # noqa: E402  (exact endgames' spec and refusals)
 from .proof import check_proof_backup  # noqa: E402  (proof backup's spec and refusals)
+from .puct import OFF as PUCT_OFF, check_puct, is_on as puct_is_on  # noqa: E402  (the PUCT exploration settings' spec and refusals)
 
 
 def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
@@ -89,7 +90,7 @@ def check_leaf_batch(leaf_batch, nn, symmetry=None, neural=True):
 
 class MCT:
     def __init__(self, eval_method=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, symmetry=None,
-                 leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None, proof_backup=False):
+                 leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None, proof_backup=False, puct=None):
         self.n_rollouts = 0
         self.simulation_time = 0
         self.eval_method = TreeEval.to_dict()["rollout" if eval_method is None else eval_method]
@@ -139,6 +140,11 @@ class MCT:
         self.proof_backup = proof_backup
         self._engine_proof = False    # whether the engine has the mode on
         check_proof_backup(proof_backup, self._nn, symmetry, leaf_batch, gumbel, self.eval_method == TreeEval.NEURAL)
+        # the PUCT exploration settings (alphazero_amd.puct: None, c_init or a dict of c_init, c_base, fpu): the exploration constant, its
+        # growth with the parent's visits and first-play urgency; the plain PUCT search on HIP-routed networks only
+        self.puct = puct
+        self._engine_puct = PUCT_OFF  # the triple the engine is set to
+        check_puct(puct, self._nn, symmetry, leaf_batch, gumbel, exact_endgame, proof_backup, self.eval_method == TreeEval.NEURAL)
 
     # ------------------------------------------------------------------ reference surface
     @property
@@ -154,6 +160,7 @@ class MCT:
         check_gumbel(self.gumbel, nn, self.leaf_batch)
         check_exact_endgame(self.exact_endgame, nn, self.symmetry, self.leaf_batch, self.gumbel)
         check_proof_backup(self.proof_backup, nn, self.symmetry, self.leaf_batch, self.gumbel)
+        check_puct(self.puct, nn, self.symmetry, self.leaf_batch, self.gumbel, self.exact_endgame, self.proof_backup)
         self._nn = nn
         self._hipnet = None
         self._evaluator = None
@@ -303,6 +310,12 @@ class MCT:
             self._engine_gf = False
             self._engine_exact = None
             self._engine_proof = False
+            self._engine_puct = PUCT_OFF
+        pu = check_puct(self.puct, self._nn if neural else None, self.symmetry, self.leaf_batch, self.gumbel, self.exact_endgame,
+                        self.proof_backup, neural)
+        if self._engine_puct != pu and not puct_is_on(pu):  # off before a mode it excludes may come on (no node depends on the settings)
+            self._engine.set_puct(None)
+            self._engine_puct = pu
         ex = check_exact_endgame(self.exact_endgame, self._nn if neural else None, self.symmetry, self.leaf_batch, self.gumbel, neural)
         if self._engine_exact is not None and ex is None:  # off before a mode it excludes may come on
             self._root_key = None  # over a fresh tree only: the kept one was searched under the old value
@@ -345,6 +358,9 @@ class MCT:
         if self._engine_proof != pb:
             self._engine.set_proof_backup(pb)
             self._engine_proof = pb
+        if self._engine_puct != pu:  # on, or other values: after every mode it excludes has gone off; the kept tree stays
+            self._engine.set_puct({"c_init": pu[0], "c_base": pu[1], "fpu": pu[2]})
+            self._engine_puct = pu
         if self._engine_gf != gf:  # on after set_roots: a fresh tree holds no node evaluated without its value; a kept one is refused
             self._engine.set_gumbel_full(gf)
             self._engine_gf = gf

@@ -10,6 +10,7 @@ from .base import Player
 from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full
 from .endgame import check_exact_endgame
 from .proof import check_proof_backup
+from .puct import check_puct, is_on as puct_is_on
 from .mcts import MCT, _action_of, _move_of, check_leaf_batch, check_symmetry
 from .utils import fair_max
 
@@ -84,16 +85,23 @@ class MCTSPlayer(Player):
 
 class AlphaZeroPlayer(MCTSPlayer):
     def __init__(self, n_sim=None, compute_time=None, nn=None, dirichlet_alpha=None, dirichlet_epsilon=None, verbose=False,
-                 symmetry=None, leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None, proof_backup=False):
+                 symmetry=None, leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None, proof_backup=False,
+                 puct=None):
         super().__init__(n_sim=n_sim, compute_time=compute_time, verbose=verbose)
         check_gumbel(gumbel, nn, leaf_batch, True, compute_time)
         check_gumbel_batch(gumbel_batch, gumbel, symmetry)
         check_gumbel_full(gumbel_full, gumbel)
         check_exact_endgame(exact_endgame, nn, symmetry, leaf_batch, gumbel)
         check_proof_backup(proof_backup, nn, symmetry, leaf_batch, gumbel)
+        check_puct(puct, nn, symmetry, leaf_batch, gumbel, exact_endgame, proof_backup)
         self.mct = MCT(eval_method="neural", nn=nn, dirichlet_alpha=dirichlet_alpha, dirichlet_epsilon=dirichlet_epsilon,
                        symmetry=symmetry, leaf_batch=leaf_batch, gumbel=gumbel, gumbel_batch=gumbel_batch, gumbel_full=gumbel_full,
-                       exact_endgame=exact_endgame, proof_backup=proof_backup)
+                       exact_endgame=exact_endgame, proof_backup=proof_backup, puct=puct)
+
+    @property
+    def puct(self):
+        """the PUCT exploration settings (alphazero_amd.puct; None: off)"""
+        return self.mct.puct
 
     @property
     def proof_backup(self):
@@ -136,20 +144,21 @@ class AlphaZeroPlayer(MCTSPlayer):
                                dirichlet_alpha=self.mct.dirichlet_alpha, dirichlet_epsilon=self.mct.dirichlet_epsilon,
                                verbose=self.verbose, symmetry=self.mct.symmetry, leaf_batch=self.mct.leaf_batch,
                                gumbel=self.mct.gumbel, gumbel_batch=self.mct.gumbel_batch, gumbel_full=self.mct.gumbel_full,
-                               exact_endgame=self.mct.exact_endgame, proof_backup=self.mct.proof_backup)
+                               exact_endgame=self.mct.exact_endgame, proof_backup=self.mct.proof_backup, puct=self.mct.puct)
 
     def reset(self):
         old = self.mct
         self.mct = MCT(eval_method="neural", nn=old.nn, dirichlet_alpha=old.dirichlet_alpha,
                        dirichlet_epsilon=old.dirichlet_epsilon, symmetry=old.symmetry, leaf_batch=old.leaf_batch, gumbel=old.gumbel,
                        gumbel_batch=old.gumbel_batch, gumbel_full=old.gumbel_full, exact_endgame=old.exact_endgame,
-                       proof_backup=old.proof_backup)
+                       proof_backup=old.proof_backup, puct=old.puct)
         # keep the uploaded weights and the device tree storage: a reset only drops the tree
         self.mct._hipnet, self.mct._engine, self.mct._engine_board = old._hipnet, old._engine, old._engine_board
         self.mct._engine_lb, self.mct._engine_gumbel, self.mct._engine_gb = old._engine_lb, old._engine_gumbel, old._engine_gb
         self.mct._engine_gf = old._engine_gf
         self.mct._engine_exact = old._engine_exact
         self.mct._engine_proof = old._engine_proof
+        self.mct._engine_puct = old._engine_puct
         self.mct._evaluator = old._evaluator  # the carried engine calls it (external evaluation, evaluators.route)
         if self.mct._engine is not None:
             self.mct._plies = 0
@@ -179,6 +188,7 @@ class BatchedMCTSPlayer(Player):
         self.gumbel, self.gumbel_batch, self.gumbel_full = None, 1, False
         self.exact_endgame = None
         self.proof_backup = False
+        self.puct = None
         self._seed = int(np.random.randint(0, 2**31 - 1)) if seed is None else int(seed)
         self._engine = None           # n_slots device trees
         self._engine_board = None     # (game, H, W) the engine was built for
@@ -274,6 +284,8 @@ class BatchedMCTSPlayer(Player):
             self._engine.set_exact_endgame(check_exact_endgame(self.exact_endgame, self.nn, self.symmetry, self.leaf_batch, self.gumbel))
         if neural and check_proof_backup(self.proof_backup, self.nn, self.symmetry, self.leaf_batch, self.gumbel):
             self._engine.set_proof_backup(True)
+        if neural and puct_is_on(check_puct(self.puct, self.nn, self.symmetry, self.leaf_batch, self.gumbel, self.exact_endgame, self.proof_backup)):
+            self._engine.set_puct(self.puct)
         self._engine_board = (first.game, H, W)
 
     def _sync(self, boards, first):
@@ -369,7 +381,8 @@ class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
     _eval_method = "neural"
 
     def __init__(self, n_sim=None, nn=None, n_slots=1, dirichlet_alpha=None, dirichlet_epsilon=None, seed=None, verbose=False,
-                 symmetry=None, leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None, proof_backup=False):
+                 symmetry=None, leaf_batch=None, gumbel=None, gumbel_batch=1, gumbel_full=False, exact_endgame=None, proof_backup=False,
+                 puct=None):
         super().__init__(n_sim=n_sim, n_slots=n_slots, seed=seed, verbose=verbose)
         self.nn, self.dirichlet_alpha, self.dirichlet_epsilon = nn, dirichlet_alpha, dirichlet_epsilon
         # leaf evaluations averaged over the board's symmetries (alphazero_amd.symmetry; None: off); HIP-routed networks only
@@ -396,6 +409,10 @@ class BatchedAlphaZeroPlayer(BatchedMCTSPlayer):
         # move and the policy on the counts the proofs leave; the plain PUCT search on HIP-routed networks only
         self.proof_backup = proof_backup
         check_proof_backup(proof_backup, nn, symmetry, leaf_batch, gumbel)
+        # the PUCT exploration settings (alphazero_amd.puct: None, c_init or a dict of c_init, c_base, fpu); the plain PUCT search on
+        # HIP-routed networks only
+        self.puct = puct
+        check_puct(puct, nn, symmetry, leaf_batch, gumbel, exact_endgame, proof_backup)
 
 
 PLAYERS_SET = {"human", "random", "greedy", "mcts", "alphazero"}

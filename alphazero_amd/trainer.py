@@ -63,7 +63,7 @@ class AlphaZeroTrainer:
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
                  selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, selfplay_playout_cap=None, selfplay_forced_playouts=None,
-                 selfplay_exact_endgame=None, selfplay_proof_backup=False, eval_search=None, eval_opening_plies=None):
+                 selfplay_exact_endgame=None, selfplay_proof_backup=False, selfplay_puct=None, eval_search=None, eval_opening_plies=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -121,6 +121,11 @@ class AlphaZeroTrainer:
         # with selfplay_exact_endgame or without: not with the Gumbel search, the symmetry modes, the playout cap or forced playouts.
         self.selfplay_proof_backup = selfplay_proof_backup
         self._check_selfplay_proof_backup()
+        # the PUCT exploration settings of that wave: None (off), c_init or a dict of c_init, c_base, fpu
+        # (alphazero_amd.puct).  The plain PUCT wave only: not with the Gumbel search, the symmetry modes, the playout cap, forced
+        # playouts, exact endgames or proof backup.  eval_search "selfplay" hands them to the evaluation arena too.
+        self.selfplay_puct = selfplay_puct
+        self._check_selfplay_puct()
         # the search the evaluation arena plays with (BatchedArena's `search`): None (the visit-based PUCT arena), "selfplay" (the modes
         # of the self-play wave above) or a dict of arena.SEARCH_KEYS; it goes to player 1 and, with eval_opponent "previous", to the
         # opponent too.  eval_opening_plies: BatchedArena's `opening_plies`, the seeded opening that makes the rounds different games.
@@ -137,6 +142,8 @@ class AlphaZeroTrainer:
                 raise ValueError(f"eval_search={spec!r}: expected None, 'selfplay' or a dict of search modes")
             spec = {"symmetry": self.selfplay_symmetry, "gumbel": self.selfplay_gumbel, "gumbel_batch": self.selfplay_gumbel_batch,
                     "gumbel_full": self.selfplay_gumbel_full}
+            if self.selfplay_puct is not None:
+                spec["puct"] = self.selfplay_puct
         check_search(spec, nn, "eval_search")
         return spec
 
@@ -173,6 +180,13 @@ class AlphaZeroTrainer:
         return check_combination(self.selfplay_proof_backup, "selfplay_proof_backup",
                                  {"selfplay_gumbel": self.selfplay_gumbel, "selfplay_symmetry": self.selfplay_symmetry,
                                   "selfplay_playout_cap": self.selfplay_playout_cap, "selfplay_forced_playouts": self.selfplay_forced_playouts})
+
+    def _check_selfplay_puct(self):
+        from .puct import check_combination
+        return check_combination(self.selfplay_puct, "selfplay_puct",
+                                 {"selfplay_gumbel": self.selfplay_gumbel, "selfplay_symmetry": self.selfplay_symmetry,
+                                  "selfplay_playout_cap": self.selfplay_playout_cap, "selfplay_forced_playouts": self.selfplay_forced_playouts,
+                                  "selfplay_exact_endgame": self.selfplay_exact_endgame, "selfplay_proof_backup": self.selfplay_proof_backup})
 
     def _check_selfplay_symmetry(self):
         from .symmetry import parse
@@ -254,6 +268,7 @@ class AlphaZeroTrainer:
         forced = self._check_selfplay_forced_playouts()
         exact = self._check_selfplay_exact_endgame()
         proof = self._check_selfplay_proof_backup()
+        puct = self._check_selfplay_puct()
         from .gumbel import check_gumbel, check_gumbel_batch, check_gumbel_full
         gb = check_gumbel_batch(self.selfplay_gumbel_batch, self.selfplay_gumbel)
         gf = check_gumbel_full(self.selfplay_gumbel_full, self.selfplay_gumbel)
@@ -298,6 +313,9 @@ class AlphaZeroTrainer:
         if not proof and getattr(self._engine, "_proof_backup", False):
             self._engine.set_proof_backup(False)
             self._engine._proof_backup = False
+        from .puct import is_on as puct_is_on
+        if not puct_is_on(puct) and self._engine.puct != puct:  # off before a mode it excludes may come on
+            self._engine.set_puct(None)
         if external:  # a fresh evaluator for the network of this wave (update_network replaces self.nn)
             self._engine.set_evaluator(make_evaluator(self.nn, self.game, H, W))
         elif sym is not None or self._engine._sym_mode is not None:
@@ -327,6 +345,8 @@ class AlphaZeroTrainer:
         if proof != getattr(self._engine, "_proof_backup", False):  # ValueError for a network routed to the external evaluator
             self._engine.set_proof_backup(proof)  # likewise: no active slot holds a tree
             self._engine._proof_backup = proof
+        if self._engine.puct != puct:  # ValueError for a network routed to the external evaluator
+            self._engine.set_puct({"c_init": puct[0], "c_base": puct[1], "fpu": puct[2]})
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):

@@ -656,6 +656,47 @@ int az_engine_set_proof_backup(az_engine *e, int32_t on);
 int az_engine_proof_backup_stats(az_engine *e, int64_t *proven_nodes, int64_t *proof_stops, int64_t *pruned_plies);
 int az_engine_root_proofs(az_engine *e, int8_t *d_out);
 
+/* ---- PUCT exploration settings: c_init, c_base and first-play urgency ----------------------------------------
+ * The search scores a child as Q + P sqrt(N_parent) / (1 + N): PUCT with the exploration constant fixed at 1 and an unvisited
+ * child's Q fixed at 0, as the reference has it (Node.PUCT(c_puct=1.0), Q = 0 at construction).  These settings free both: the
+ * constant, its growth with the parent's visits as the AlphaZero pseudocode writes it (Silver et al. 2018:
+ * c(s) = log((1 + N(s) + c_base) / c_base) + c_init), and first-play urgency, the value an unvisited child is assumed to have
+ * (Leela Chess Zero, KataGo: the parent's value minus a reduction that grows with the prior mass already visited).
+ *   c_init   finite, in (0, 64].
+ *   c_base   0: no growth.  Otherwise finite, in [1, 1e9].
+ *   fpu      any negative value: off, an unvisited child's Q is 0 as in the reference (canonical: -1, what az_engine_puct then
+ *            reports).  Otherwise finite, in [0, 4].
+ * The triple (1.0, 0, off) is the mode off, the default: no launch, kernel or output bit differs from an engine that never had
+ * another triple.  Every operation below is one IEEE double operation in the order written, no contraction; sqrt is the correctly
+ * rounded one, LOG is the library's az_det_log, which det_log of alphazero_amd/gumbel.py follows bit for bit on the host.
+ * For a parent p with children c_0 .. c_{k-1} (k <= 64), at every depth, the root included:
+ *   sq    = sqrt((double)p.N)
+ *   c     = c_base > 0 ? c_init + LOG(((1.0 + (double)p.N) + c_base) / c_base) : c_init
+ *   vis   only when fpu >= 0.  Lane s of the game's 16 holds the children r * 16 + s, r = 0 .. 3:
+ *           part_s = (((0.0 + t_0) + t_1) + t_2) + t_3,  t_r = c.P if that child exists and has c.N > 0, else 0.0;
+ *         then a pairwise tree over the lanes with strides 1, 2, 4, 8 in that order: part_s = part_s + part_{s ^ stride}
+ *         (addition commutes: every lane ends with the same bits); vis = part_0.
+ *   q     of a child: c.Q if c.N > 0 or fpu < 0, else (-p.Q) - fpu * sqrt(vis).  p.Q is the parent's stored Q: a node's Q is kept
+ *         in the frame of the player who moved into it, so -p.Q is the mover's own estimate; the root's stored Q likewise.
+ *   key   = q + ((c * c.P) * sq) / (double)(1 + c.N)
+ * The walk's break rules (a fresh node, N == 0), the tie rule (the AZ_P_TIE_SELECT draw of that (ply, sim, depth) under
+ * AZ_TIE_RANDOM, the lowest index under AZ_TIE_LOWEST), root noise, the backup, the move, the policy target, visits, the readouts
+ * and the temperature do not change.  A game depends on (seed, game id, the triple) only, never on the slot, the slot group, the
+ * batch or the cache.
+ * Served in the plain PUCT search of AZ_EVAL_NET and AZ_EVAL_FAKE engines (k_step_puct, k_step_puct_cached), in az_engine_run and
+ * on the az_engine_set_roots / _search / _advance / _root_readout / _player_moves route, with slot groups and the leaf evaluation
+ * cache.  Not served (AZ_EINVAL naming the mode; and while the settings are on the setters of those modes refuse, naming these):
+ * AZ_EVAL_EXTERNAL, AZ_EVAL_ROLLOUT, either symmetry mode, leaf_batch > 1, the Gumbel search, the playout cap, forced playouts,
+ * exact endgames, proof backup.  AZ_ESTATE while a search is open.  The settings may change between two searches of one tree (no
+ * node depends on them); a change drops the cached search graphs.
+ * az_puct_c and az_puct_key are c and key above as host arithmetic, the very functions the kernels call (az_puct_key computes sq
+ * and c from parent_n; vis is read only where n_child == 0 and fpu >= 0). */
+int az_engine_set_puct(az_engine *e, double c_init, double c_base, double fpu);
+int az_engine_puct(az_engine *e, double *c_init, double *c_base, double *fpu);
+double az_puct_c(int32_t parent_n, double c_init, double c_base);
+double az_puct_key(double q_child, double p_child, int32_t n_child, int32_t parent_n, double parent_q, double vis,
+                   double c_init, double c_base, double fpu);
+
 /* ---- external evaluator: any PolicyValueNetwork / any object with evaluate() -----------------------------
  * The reference's MCT calls nn.evaluate(board) for every non-terminal leaf and for a fresh root (mcts.py:182-195, 231-233;
  * base.py:350-367).  An engine created with evaluator = AZ_EVAL_EXTERNAL (net may be NULL) hands each batch of pending leaves
