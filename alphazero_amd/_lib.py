@@ -63,7 +63,7 @@ SYMBOLS = [
     "az_last_error", "az_version", "az_board_legal_batch", "az_board_play_batch", "az_board_status_batch", "az_solve_batch",
     "az_net_create", "az_net_destroy", "az_net_set_tensor", "az_net_commit", "az_net_set_tensor_device", "az_net_commit_device", "az_net_forward", "az_net_forward_dyn", "az_net_set_lanes", "az_net_forward_lane", "az_net_forward_sym", "az_net_forward_sym_codes",
     "az_net_action_size",
-    "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_trunk_prefetch", "az_net_trunk_stores", "az_net_stage_lane", "az_net_stage_plan", "az_net_gemm_rows", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
+    "az_net_flops_per_board", "az_net_time_stage", "az_net_stage_kernel", "az_net_trunk_prefetch", "az_net_trunk_stores", "az_net_stage_lane", "az_net_forward_lane_fc2", "az_net_heads_view", "az_net_stage_plan", "az_net_gemm_rows", "az_net_profile", "az_net_profiling", "az_net_profile_read", "az_net_profile_overhead", "az_engine_create", "az_engine_destroy", "az_engine_run",
     "az_engine_get_stats", "az_engine_samples", "az_engine_set_roots", "az_engine_search", "az_engine_search_begin", "az_engine_search_end", "az_engine_pair", "az_engine_set_groups", "az_engine_groups", "az_engine_advance",
     "az_engine_root_children", "az_engine_root_readout", "az_engine_nodes_used", "az_engine_grow_pools", "az_engine_play", "az_augment_count", "az_augment",
     "az_engine_set_sides", "az_engine_best_moves", "az_engine_player_moves", "az_engine_baseline_moves", "az_engine_root_status", "az_engine_set_evaluator", "az_engine_set_symmetry", "az_engine_set_symmetry_random", "az_engine_set_leaf_batch", "az_engine_collisions",
@@ -71,7 +71,7 @@ SYMBOLS = [
     "az_engine_set_gumbel_full", "az_engine_root_value",
     "az_engine_set_playout_cap", "az_engine_playout_cap_stats", "az_playout_cap_full",
     "az_engine_set_forced_playouts", "az_engine_forced_playouts_stats", "az_forced_playout", "az_forced_prune",
-    "az_engine_set_eval_cache", "az_engine_eval_cache_stats",
+    "az_engine_set_eval_cache", "az_engine_eval_cache_stats", "az_engine_step_heads",
     "az_engine_set_exact_endgame", "az_engine_exact_endgame_stats",
     "az_engine_set_proof_backup", "az_engine_proof_backup_stats", "az_engine_root_proofs",
     "az_engine_set_puct", "az_engine_puct", "az_puct_c", "az_puct_key",
@@ -117,6 +117,8 @@ def lib():
     L.az_net_stage_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
     L.az_net_gemm_rows.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.az_net_stage_lane.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    L.az_net_forward_lane_fc2.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+    L.az_net_heads_view.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
     L.az_net_profile.argtypes = [vp, C.c_int]
     L.az_net_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.az_net_profile_overhead.argtypes = [vp, C.POINTER(C.c_double)]
@@ -159,6 +161,7 @@ def lib():
     L.az_engine_forced_playouts_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.az_engine_set_eval_cache.argtypes = [vp, i32, i32, i32]
     L.az_engine_eval_cache_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+    L.az_engine_step_heads.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.az_engine_set_exact_endgame.argtypes = [vp, i32]
     L.az_engine_exact_endgame_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.az_engine_set_proof_backup.argtypes = [vp, i32]
@@ -195,7 +198,7 @@ def lib():
 
 # the sources a measurement depends on: counter files of the network kernels stay valid while only the engine or the training step
 # changes, and the other way round
-CSRC_COMPONENTS = {"net": ("az_net.hip",), "engine": ("az_engine.hip", "az_solve.h"), "train": ("az_train.hip",)}
+CSRC_COMPONENTS = {"net": ("az_net.hip",), "engine": ("az_engine.hip", "az_solve.h", "az_heads_block.h"), "train": ("az_train.hip",)}
 _CSRC_SHARED = ("az_device.h", "az_host.h", "Makefile")  # az_common.hip (version number, error string) holds no kernel code
 
 

@@ -49,6 +49,7 @@
 #include "az_solve.h"
 #include "az_host.h"
 #include "az_search_plan.h"  // up here for the evaluation cache's key arithmetic, which the step kernels share with the host (ec_*)
+#include "az_heads_block.h"  // the heads of one block's 16 rows (k_step_heads)
 
 #define F_EXPANDED 1
 #define F_TERMINAL 2
@@ -168,6 +169,11 @@ struct EngDev {
     // urgency's reduction (negative: off).  Read by the k_step_puct kernels alone, which are launched only while the triple is not the
     // neutral (1.0, 0, off).  (After pf: the fields above keep their place.)
     double puct_cinit, puct_cbase, puct_fpu;
+    // the heads inside the step kernel (k_step_heads): the chain's fc2 rows (the net lane's h2), the head matrix in
+    // k_heads2's fragment order and the padded bias; sh_nt = the 16-column tiles of the padded logits (5 or 3).  Null unless the form is
+    // in force (az_engine_run alone sets them): then no kernel touches them.  (Last: the fields above keep their place.)
+    const float *sh_h2, *sh_wq, *sh_hb;
+    int sh_nt;
 };
 // tag = ec_tag(hash, the claimer's stamp), 0 = empty: claimed by one device-scope compare-and-swap, never rewritten within a run; the
 // key is written by the claimer in the same kernel, the payload in the group's next one
@@ -662,13 +668,15 @@ AZ_D int ec_lookup_grp(const EngDev &E, const BB &b, u32 stamp, int sub, int *cl
 }
 
 // The network's output for the leaf a slot selected in the previous lock-step: row `row` of the batch, or the payload of the table
-// entry the row stands for (ec_row_of_entry; only with az_engine_set_eval_cache in force).  *v = the value.
-AZ_D const float *leaf_output(const EngDev &E, int row, float *v) {
+// entry the row stands for (ec_row_of_entry; only with az_engine_set_eval_cache in force).  *v = the value.  A third kind of row, in
+// k_step_heads alone: blk_pr = the priors the block has just computed for the slot's batch row into its LDS, blk_v their value.
+AZ_D const float *leaf_output(const EngDev &E, int row, float *v, const float *blk_pr = nullptr, float blk_v = 0.0f) {
     if (ec_row_is_entry(row)) {
         const float *pay = E.ec_pay + (size_t)ec_entry_of_row(row) * E.ec_stride;
         *v = pay[E.A];
         return pay;
     }
+    if (blk_pr) { *v = blk_v; return blk_pr; }
     *v = E.value[row];
     return E.probs + (size_t)row * E.A;
 }
@@ -924,7 +932,12 @@ __device__ unsigned long long az_step_probe[4096 * 8];
 // row, no solve, no cache lookup.  PROOF false is the kernel as it was.
 // PUCT (az_engine_set_puct, k_step_puct): the walk scores by puct_key, and the root this kernel's backup forwards to
 // its own walk carries the Q that backup has just written (first-play urgency reads it).  PUCT false is the kernel as it was.
-template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false, bool EXACT = false, bool PROOF = false, bool PUCT = false>
+// HEADS (k_step_heads): the 16-column tiles of the net's padded logits, 0 = off.  The forward before this kernel
+// stopped behind fc2: the block computes the heads of its own slots' rows (heads_block16) in front of the backup and reads priors and
+// values from its LDS; E.probs / E.value are neither written nor read.  A slot brings a row if its leaf is LS_EVAL with a batch row
+// (row_prev >= 0: not a cache hit); every thread of the block reaches the routine, whose barriers lie in front of every divergent
+// branch below.  HEADS 0 is the kernel as it was.
+template <bool BACKUP, bool SELECT, bool CAP, bool FORCED, bool EC = false, bool EXACT = false, bool PROOF = false, bool PUCT = false, int HEADS = 0>
 AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr) {
     const int g = g0 + blockIdx.x * GPB + (threadIdx.x >> 4), sub = threadIdx.x & (LPG - 1);
     // this step's leaves are compacted into rows [0, batch_cnt[sim & 1]); the other counter (read by the
@@ -967,17 +980,25 @@ AZ_D void step_grp(const EngDev &E, int sim, int g0, int g1, u64 *xstk = nullptr
     Node fwd;
     bool have_root = false;
     PSTAMP(1)
+    Node mine;
+    const bool on_path = plen_prev <= LPG && sub < plen_prev;
+    const float *blk_pr = nullptr;
+    float blk_v = 0.0f;
+    if (HEADS > 0) {
+        // the path nodes are requested in front of the heads: their round trip runs beside the staging of the rows
+        if (BACKUP && st != LS_NONE && on_path) mine = load_node(pool + path_prev);
+        heads_block16<(HEADS > 0 ? HEADS : 1)>(E.sh_h2, (BACKUP && st == LS_EVAL && row_prev >= 0) ? row_prev : -1, E.sh_wq, E.sh_hb, E.A, &blk_pr, &blk_v);
+    }
     if (BACKUP && st != LS_NONE) {
         // path nodes and the network row are fetched together (second round trip)
-        Node mine;
-        const bool on_path = plen_prev <= LPG && sub < plen_prev;
-        if (on_path) mine = load_node(pool + path_prev);
+        if (HEADS == 0 && on_path) mine = load_node(pool + path_prev);
         double outcome;
         bool ok = true;
         if (st == LS_EVAL) {
             float v = 0.0f;
-            const float *pr = E.probs + (size_t)row_prev * E.A;
-            if (EC) pr = leaf_output(E, row_prev, &v);
+            const float *pr = HEADS > 0 ? nullptr : E.probs + (size_t)row_prev * E.A;
+            if (HEADS > 0) pr = leaf_output(E, row_prev, &v, blk_pr, blk_v);
+            else if (EC) pr = leaf_output(E, row_prev, &v);
             else v = E.value[row_prev];
             int k = create_children_grp(E, g, pool, n_nodes, leaf, lb, pr, sub);
             if (EC && ec_prev >= 0) {  // the slot won its claim in the previous kernel: its batch row becomes the entry's payload
@@ -1110,6 +1131,10 @@ __global__ __launch_bounds__(256) void k_step_cap_forced(EngDev E, int sim, int 
 // kernels above stay the code they were for every search that does not cache
 template <bool BACKUP, bool SELECT, bool CAP, bool FORCED>
 __global__ __launch_bounds__(256) void k_step_cached(EngDev E, int sim, int g0, int g1) { step_grp<BACKUP, SELECT, CAP, FORCED, true>(E, sim, g0, g1); }
+// and the plain one-leaf lock-step with the heads computed inside, without the cache and with it: the two forms
+// that hold a backup -- a ply's first step has none and stays k_step / k_step_cached.  NT: the tiles of the padded logits (5: 80, 3: 48)
+template <bool SELECT, bool EC, int NT>
+__global__ __launch_bounds__(256) void k_step_heads(EngDev E, int sim, int g0, int g1) { step_grp<true, SELECT, false, false, EC, false, false, false, NT>(E, sim, g0, g1); }
 // and the plain lock-step with exact endgames (az_engine_set_exact_endgame), without and with the cache: the solver's frames, three u64
 // per frame and lane, are the block's LDS (60 KiB: one block per CU's share of 64 KiB)
 #define EXACT_STK_WORDS (AZ_EXACT_MAX_EMPTIES * AZ_SOLVE_FRAME_WORDS * 256)
@@ -2608,6 +2633,12 @@ struct az_engine {
     u32 *ec_serial = nullptr;
     int *ec_claim = nullptr, *ec_hits = nullptr;
     bool graphs_ec = false;
+    // the heads inside the step kernel: the request of AZ_ENGINE_STEP_HEADS (-1: unset, the measured rule; 0: never;
+    // 1: wherever served), whether the last az_engine_run ran the form, and the pointers the captured searches of each chain carry by
+    // value (a search with other ones drops every graph first)
+    int sh_req = -1;
+    bool sh_used = false;
+    const void *graphs_sh[AZ_MAX_GROUPS][3] = {};
     // az_engine_set_exact_endgame: the per-slot counts of solved leaves and solver positions, [G] each, allocated when the mode first
     // goes on; in force (d.x_solved == exact_solved, d.exact_max > 0) only while it is on, else d.x_solved is null
     int *exact_solved = nullptr;
@@ -2720,6 +2751,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.exact_max = 0; d.x_solved = nullptr; d.x_nodes = nullptr;
     d.pf = nullptr;
     d.puct_cinit = 1.0; d.puct_cbase = 0.0; d.puct_fpu = -1.0;
+    d.sh_h2 = nullptr; d.sh_wq = nullptr; d.sh_hb = nullptr; d.sh_nt = 0;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2752,6 +2784,10 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     if (rc == AZ_OK) {  // AZ_ENGINE_EVAL_CACHE, likewise: 0 = never, 1 = wherever the cache is served (eval_cache_in_force)
         const char *c = getenv("AZ_ENGINE_EVAL_CACHE");
         if (c && (c[0] == '0' || c[0] == '1') && c[1] == 0) { e->ec_req = c[0] == '1' ? AZ_EVAL_CACHE_ON : AZ_EVAL_CACHE_OFF; e->ec_env = true; }
+    }
+    if (rc == AZ_OK) {  // AZ_ENGINE_STEP_HEADS, likewise: 0 = never, 1 = wherever the form is served (step_heads_in_force)
+        const char *c = getenv("AZ_ENGINE_STEP_HEADS");
+        if (c && (c[0] == '0' || c[0] == '1') && c[1] == 0) e->sh_req = c[0] - '0';
     }
     if (rc != AZ_OK) { az_engine_destroy(e); return rc; }
     if (hipStreamSynchronize(e->stream) != hipSuccess) { az_engine_destroy(e); az_set_error("stream sync failed"); return AZ_EHIP; }
@@ -2835,6 +2871,8 @@ static int forward(az_engine *e, const Chain &c, const int *cnt, int cap, int st
         AZ_TRY(az_net_forward_dyn(e->net, e->sym_in, cnt, cap, e->sym_p, e->sym_v, e->stream));
         return az_sym_unpick(&d.gd, e->sym_code, e->sym_p, e->sym_v, cnt, cap, d.probs, d.value, e->stream);
     }
+    // k_step_heads follows a lock-step's forward: the forward stops behind fc2 (the root-prior pass keeps its heads: k_root_init reads them)
+    if (d.sh_h2 && step >= 0) return az_net_forward_lane_fc2(e->net, c.idx, c.beside ? 1 : 0, d.nn_in, cnt, cap, c.st);
     if (e->sym_mask == 0) return az_net_forward_lane(e->net, c.idx, c.beside ? 1 : 0, d.nn_in, cnt, cap, d.probs, d.value, c.st);
     // ensemble over the board's symmetries: twins of the pending rows -> the network on sym_n * count rows -> mapped back and averaged
     AZ_TRY(az_sym_expand(&d.gd, e->sym_mask, d.nn_in, cnt, cap, e->sym_in, e->sym_cnt, e->stream));
@@ -2857,7 +2895,17 @@ static void launch_step_as(const SearchPlan &p, const Chain &c, int n_sim, const
         case SF_ROLLOUT: hipLaunchKernelGGL(k_rollout_step, gg, gb, 0, c.st, d, a.t); break;
         // the four one-leaf families: with the evaluation cache's pointers set (az_engine_run alone sets them) their cached instantiation
         case SF_STEP:
-            if (d.ec_hdr) hipLaunchKernelGGL((k_step_cached<B, S, false, false>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+            // with the heads' pointers set (az_engine_run alone sets them) the steps that hold a backup compute the heads themselves
+            if (B && d.sh_h2) {
+                if (d.sh_nt == 5) {
+                    if (d.ec_hdr) hipLaunchKernelGGL((k_step_heads<S, true, 5>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+                    else hipLaunchKernelGGL((k_step_heads<S, false, 5>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+                } else {
+                    if (d.ec_hdr) hipLaunchKernelGGL((k_step_heads<S, true, 3>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+                    else hipLaunchKernelGGL((k_step_heads<S, false, 3>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
+                }
+            }
+            else if (d.ec_hdr) hipLaunchKernelGGL((k_step_cached<B, S, false, false>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
             else hipLaunchKernelGGL((k_step<B, S>), gg, gb, 0, c.st, d, a.t, c.g0, c.g1);
             break;
         case SF_STEP_CAP:
@@ -2953,6 +3001,14 @@ static int do_search(az_engine *e, int n_sim, const Chain *grp = nullptr) {
     // another family, or the full instantiation of a Gumbel one, launches other kernels: the key keeps their graphs apart
     // (and a captured search holds the evaluation cache's pointers, or null ones, by value: one with the other setting replays none of them)
     if ((d.ec_hdr != nullptr) != e->graphs_ec) { drop_graphs(e); e->graphs_ec = d.ec_hdr != nullptr; }
+    // and the heads' pointers of k_step_heads, or null ones: the lane's rows move with az_net_set_lanes, the form goes with the switch
+    {
+        const void **have = e->graphs_sh[c.idx];
+        if (have[0] != d.sh_h2 || have[1] != d.sh_wq || have[2] != d.sh_hb) {
+            drop_graphs(e);
+            have[0] = d.sh_h2; have[1] = d.sh_wq; have[2] = d.sh_hb;
+        }
+    }
     const SearchKey key = search_key(plan, n_sim, cap, c.g0, c.g1);
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) {
@@ -3129,6 +3185,8 @@ static int run_grouped(az_engine *e, int n, int32_t n_games, long long max_iters
         widest = ch[i].g1 - ch[i].g0 > widest ? ch[i].g1 - ch[i].g0 : widest;
     }
     if (e->cfg.evaluator == AZ_EVAL_NET) AZ_TRY(az_net_set_lanes(e->net, n, widest));
+    if (e->d.sh_h2)  // k_step_heads reads the fc2 rows of its own chain's lane (they exist from here on)
+        for (int i = 0; i < n; ++i) AZ_TRY(az_net_heads_view(e->net, i, &ch[i].d.sh_h2, nullptr, nullptr, nullptr, nullptr));
     AZ_HIP(hipEventRecord(e->ev_grp, e->stream));  // behind k_reset_all
     int rc = AZ_OK, n_open = 0;
     for (int i = 0; i < n && rc == AZ_OK; ++i) {
@@ -3197,6 +3255,29 @@ static void ec_detach(az_engine *e) {
     d.ec_mask = 0; d.ec_limit = 0; d.ec_stride = 0;
 }
 
+// ---- the heads inside the step kernel (k_step_heads) ---------------------------------------------------------------
+// whether the next az_engine_run computes the heads in its step kernels: the request (unset: the rule) where the form is served
+static bool step_heads_on(const az_engine *e) {
+    const EngDev &d = e->d;
+    int nh = 0, f2 = 0;
+    const bool shape = e->cfg.evaluator == AZ_EVAL_NET && e->net && az_net_heads_view(e->net, 0, nullptr, nullptr, nullptr, &nh, &f2) == AZ_OK;
+    const SearchMode m = search_mode(d);
+    const bool plain = beyond_plain_search(e) == nullptr && !m.cap && !m.forced && m.exact == 0 && !m.proof && !m.puct;
+    return step_heads_in_force(e->sh_req, e->cfg.evaluator, e->cfg.game, e->cfg.H, e->cfg.W, d.G, plain, shape, e->net && az_net_profiling(e->net));
+}
+// a run in that form: the engine's device view points at lane 0's rows and the net's head weights until the run returns (sh_detach)
+static int sh_attach(az_engine *e) {
+    EngDev &d = e->d;
+    int nh = 0, f2 = 0;
+    AZ_TRY(az_net_heads_view(e->net, 0, &d.sh_h2, &d.sh_wq, &d.sh_hb, &nh, &f2));
+    d.sh_nt = nh / 16;
+    return AZ_OK;
+}
+static void sh_detach(az_engine *e) {
+    EngDev &d = e->d;
+    d.sh_h2 = nullptr; d.sh_wq = nullptr; d.sh_hb = nullptr; d.sh_nt = 0;
+}
+
 static int run_games(az_engine *e, uint32_t first_game_id, int32_t n_games);
 
 extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_games) {
@@ -3205,6 +3286,7 @@ extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_gam
     AZ_NOT_IN_CALLBACK(e, "az_engine_run");
     const int rc = run_games(e, first_game_id, n_games);
     ec_detach(e);
+    sh_detach(e);
     return rc;
 }
 
@@ -3223,6 +3305,8 @@ static int run_games(az_engine *e, uint32_t first_game_id, int32_t n_games) {
         return AZ_EINVAL;
     }
     if (eval_cache_on(e)) AZ_TRY(ec_attach(e, n_groups));
+    e->sh_used = step_heads_on(e);
+    if (e->sh_used) AZ_TRY(sh_attach(e));
     hipLaunchKernelGGL(k_reset_all, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, (u32)first_game_id, (int)n_games);
     long long max_iters = ((long long)n_games / d.G + 2) * (long long)d.max_plies + 8;
     e->active_bound = n_games < d.G ? n_games : d.G;
@@ -4170,6 +4254,14 @@ extern "C" int az_engine_eval_cache_stats(az_engine *e, int32_t *in_force, int64
     AZ_TRY(fetch_counters(e));
     *in_force = eval_cache_on(e) ? 1 : 0;
     *hits = (int64_t)e->h_ctr[CTR_CACHE_HITS];
+    return AZ_OK;
+}
+
+// whether the next az_engine_run would compute the heads in its step kernels, and whether the last one did
+extern "C" int az_engine_step_heads(az_engine *e, int32_t *in_force, int32_t *used) {
+    AZ_REQUIRE(e && in_force && used, AZ_EINVAL, "null argument");
+    *in_force = step_heads_on(e) ? 1 : 0;
+    *used = e->sh_used ? 1 : 0;
     return AZ_OK;
 }
 

@@ -4335,8 +4335,9 @@ extern "C" int az_net_profile_read(az_net *n, double *ms_total, int64_t *launche
 }
 
 // the forward on the activation rows of `lane`; beside: see LaunchCtx
-static int forward_impl(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream, int lane = 0, int beside = 0) {
-    AZ_REQUIRE(n && d_input && d_probs && d_value, AZ_EINVAL, "null argument");
+// (n_stages = 3: the forward stops behind fc2 -- az_net_forward_lane_fc2; d_probs / d_value are not touched)
+static int forward_impl(az_net *n, const float *d_input, int B, const int *dyn, float *d_probs, float *d_value, void *stream, int lane = 0, int beside = 0, int n_stages = 4) {
+    AZ_REQUIRE(n && d_input && (n_stages < 4 || (d_probs && d_value)), AZ_EINVAL, "null argument");
     const bool mlp = n->game == AZ_TICTACTOE;  // no activation rows: a lane is a name only
     const int n_lanes = mlp ? n->mlp_lanes : (int)n->lanes.size() + 1;
     AZ_REQUIRE(lane >= 0 && lane < n_lanes, AZ_EINVAL, "lane %d of %d (az_net_set_lanes)", lane, n_lanes);
@@ -4347,13 +4348,13 @@ static int forward_impl(az_net *n, const float *d_input, int B, const int *dyn, 
     const LaunchCtx lane_ctx = {(hipStream_t)stream, beside, rows.feat, rows.h1, rows.h2};
     if (!n->prof || mlp) {  // k_mlp is not profiled
         LaunchCtx c = lane_ctx;
-        for (int s = 0; s < 4; ++s) AZ_TRY(run_stage(n, c, s, d_input, B, dyn, d_probs, d_value));
+        for (int s = 0; s < n_stages; ++s) AZ_TRY(run_stage(n, c, s, d_input, B, dyn, d_probs, d_value));
         return AZ_OK;
     }
     if (n->prof_used == PROF_SLOTS) AZ_TRY(prof_harvest(n));
     hipEvent_t *ev = n->prof_ev.data() + (size_t)n->prof_used * 8;
     int slots = 0, has = 0;
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < n_stages; ++s) {
         LaunchCtx c = lane_ctx;
         c.ev_start = ev[2 * s]; c.ev_stop = ev[2 * s + 1];
         int slot = 0;
@@ -4380,6 +4381,34 @@ extern "C" int az_net_forward_lane(az_net *n, int lane, int beside, const float 
                                    float *d_value, void *stream) {
     AZ_REQUIRE(d_count, AZ_EINVAL, "null count pointer");
     return forward_impl(n, d_input, max_B, d_count, d_probs, d_value, stream, lane, beside);
+}
+
+// whether a consumer can compute the heads itself from a lane's fc2 rows: a conv net on float dense layers whose heads k_heads2 has an
+// instantiation for (F2 = 512, 80 or 48 padded logits: OthelloNet)
+static bool heads_view_shape(const az_net *n) { return n->game != AZ_TICTACTOE && !n->qd_on && n->F2 == 512 && (n->NH == 80 || n->NH == 48) && n->hwq; }
+
+// az_net_forward_lane without its last stage: trunk, fc1, fc2 on the lane's rows; the lane's fc2 rows [0, *d_count) are the result
+// (az_net_heads_view hands them out).  For a consumer that computes the heads itself (k_step_heads).
+extern "C" int az_net_forward_lane_fc2(az_net *n, int lane, int beside, const float *d_input, const int32_t *d_count, int max_B, void *stream) {
+    AZ_REQUIRE(n && d_count, AZ_EINVAL, "null argument");
+    AZ_REQUIRE(heads_view_shape(n), AZ_EINVAL, "az_net_forward_lane_fc2: this net's heads are not served outside the forward (az_net_heads_view)");
+    return forward_impl(n, d_input, max_B, d_count, nullptr, nullptr, stream, lane, beside, 3);
+}
+
+// What such a consumer needs, each where the pointer is not null: the lane's fc2 rows (rows x F2 floats, written by every forward on
+// the lane), the head matrix in k_heads2's fragment order [F2/16][NH/16][64 lanes][4], the padded bias [NH], NH and F2.  The rows'
+// pointer changes with az_net_set_lanes (a lane's rows may be replaced); the weights' pointers live as long as the net, their contents
+// change with az_net_commit / az_net_commit_device.  AZ_EINVAL: a net whose heads are not served this way, or a lane that does not exist.
+extern "C" int az_net_heads_view(az_net *n, int lane, const float **d_h2, const float **d_hwq, const float **d_hb, int32_t *NH, int32_t *F2) {
+    AZ_REQUIRE(n, AZ_EINVAL, "null net");
+    AZ_REQUIRE(heads_view_shape(n), AZ_EINVAL, "az_net_heads_view: the heads of this net (F2 = %d, %d padded logits) are not served outside the forward", n->F2, n->NH);
+    AZ_REQUIRE(lane >= 0 && lane <= (int)n->lanes.size(), AZ_EINVAL, "lane %d of %d (az_net_set_lanes)", lane, (int)n->lanes.size() + 1);
+    if (d_h2) *d_h2 = lane > 0 ? n->lanes[lane - 1].h2 : n->h2;
+    if (d_hwq) *d_hwq = n->hwq;
+    if (d_hb) *d_hb = n->hb;
+    if (NH) *NH = n->NH;
+    if (F2) *F2 = n->F2;
+    return AZ_OK;
 }
 
 extern "C" int az_net_set_lanes(az_net *n, int n_lanes, int rows) {

@@ -190,6 +190,30 @@ inline bool eval_cache_in_force(int request, int evaluator, int game, int H, int
     return request == AZ_EVAL_CACHE_ON || eval_cache_auto(evaluator, game, H, W, G);
 }
 
+// ---- the heads inside the step kernel (k_step_heads) ---------------------------------------------------------------
+// Where the form is served at all: az_engine_run's plain PUCT search of a network engine -- one leaf per slot and lock-step, no
+// symmetry mode, no playout cap, forced playouts, exact endgames, proof backup or PUCT settings (`plain`: none of them; the external,
+// fake and rollout evaluators and the Gumbel search are beyond the plain search already) -- a net whose heads k_heads2 has an
+// instantiation for (`heads2_shape`), and never under az_net_profile: the profiled step keeps describing the five separate launches.
+inline bool step_heads_served(int evaluator, bool plain, bool heads2_shape, bool profiled) { return evaluator == AZ_EVAL_NET && plain && heads2_shape && !profiled; }
+
+// The measured rule (profiles/r30_step_heads.txt): the shapes az_engine_run runs the form at where nothing was asked for.  As
+// groups_auto: on only where the slowest of three fused runs beat the fastest of three unfused ones by more than their spread; every
+// shape that was not measured, or did not pass, keeps the five launches.
+inline bool step_heads_auto(int evaluator, int game, int H, int W, int G) {
+    if (evaluator != AZ_EVAL_NET) return false;
+    // 512 slots (one group) +2.3 %, 4096 (2 x 2048) +2.0 %; 32768 (2 x 16384: 1024 blocks per step launch, no idle CU to fill) -0.1 %: off.
+    // 8192 .. 32767 were not measured and stay off, as in groups_auto.
+    if (game == AZ_GAME_OTHELLO && H == 8 && W == 8) return G >= 512 && G < 8192;
+    return false;  // everything else: not measured
+}
+
+// request: AZ_ENGINE_STEP_HEADS -- -1 unset (the rule), 0 never, 1 wherever served
+inline bool step_heads_in_force(int request, int evaluator, int game, int H, int W, int G, bool plain, bool heads2_shape, bool profiled) {
+    if (!step_heads_served(evaluator, plain, heads2_shape, profiled) || request == 0) return false;
+    return request == 1 || step_heads_auto(evaluator, game, H, W, G);
+}
+
 // ---- exact endgames (az_engine_set_exact_endgame) -----------------------------------------------------------------
 // (AZ_EXACT_MAX_EMPTIES, the largest empties limit of a solved leaf, is the frame count of k_step_exact's solver stack: az_solve.h)
 inline bool exact_endgame_ok(int max_empties) { return max_empties >= 0 && max_empties <= AZ_EXACT_MAX_EMPTIES; }

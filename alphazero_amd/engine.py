@@ -525,6 +525,14 @@ class SelfPlayEngine:
         check(lib().az_engine_eval_cache_stats(self.h, C.byref(on), C.byref(hits)))
         return {"in_force": bool(on.value), "cache_hits": hits.value}
 
+    def step_heads(self):
+        """{"in_force", "used"}: whether the next run() would compute the policy / value heads inside its step kernels (k_step_heads;
+        AZ_ENGINE_STEP_HEADS, read when the engine is created: unset = the measured rule, 0 = never, 1 = wherever served), and whether
+        the last run() did"""
+        on, used = C.c_int32(), C.c_int32()
+        check(lib().az_engine_step_heads(self.h, C.byref(on), C.byref(used)))
+        return {"in_force": bool(on.value), "used": bool(used.value)}
+
     @staticmethod
     def forced_playout(n, p, root_n, k):
         """the forced test of a root child with n visits and prior p under a root of root_n visits: True = forced (az_forced_playout:

@@ -178,6 +178,17 @@ int az_net_gemm_rows(const az_net *net, int stage, int B, int beside, int count)
  * AZ_EINVAL: a null argument, a stage outside 0..3, the TicTacToe MLP (one stage), a lane or row count az_net_forward_lane refuses. */
 int az_net_stage_lane(az_net *net, int lane, int beside, int stage, const float *d_input, const int32_t *d_count, int max_B,
                       float *d_probs, float *d_value, void *stream);
+/* For a consumer that computes the policy / value heads itself from a lane's fc2 rows (the search step kernel k_step_heads).  (ABI 117)
+ * az_net_forward_lane_fc2: az_net_forward_lane without its last stage -- trunk, fc1, fc2 on the lane's rows; rows [0, *d_count) of the
+ * lane's fc2 activations are the result.
+ * az_net_heads_view: what the consumer reads, each where the pointer is not null -- the lane's fc2 rows (F2 floats each), the head
+ * matrix in k_heads2's MFMA fragment order [F2/16][NH/16][64 lanes][4], the padded bias [NH], NH (the padded logits: A priors, the
+ * value logit at A) and F2.  The rows' pointer changes with az_net_set_lanes; the weights' pointers live as long as the net and their
+ * contents change with az_net_commit / az_net_commit_device, so a holder by value sees every later commit.
+ * Both: AZ_EINVAL for a net whose heads k_heads2 has no instantiation for (served: F2 = 512 with 80 or 48 padded logits, OthelloNet, on
+ * float dense layers) and for a lane that does not exist. */
+int az_net_forward_lane_fc2(az_net *net, int lane, int beside, const float *d_input, const int32_t *d_count, int max_B, void *stream);
+int az_net_heads_view(az_net *net, int lane, const float **d_h2, const float **d_hwq, const float **d_hb, int32_t *NH, int32_t *F2);
 /* Live measurement (the idiom of timers.py:53-76 applied per kernel): while enabled, every forward brackets its stage
  * launches with a start and a stop event each (hipExtLaunchKernelGGL).  ms_total[8] / launches[8], one slot per kernel family so that a slot's mean is the
  * figure rocprofv3 lists for that kernel: k_trunk2, fc1 and fc2 on the tiled GEMMs (k_gemm / k_gemm_solo; Connect4Net's fused tail
@@ -575,6 +586,18 @@ int az_forced_prune(int32_t n_children, const int32_t *N, const double *Q, const
 #define AZ_EVAL_CACHE_ON 1
 int az_engine_set_eval_cache(az_engine *e, int32_t mode, int32_t capacity, int32_t stone_limit);
 int az_engine_eval_cache_stats(az_engine *e, int32_t *in_force, int64_t *hits);
+
+/* The heads inside the search step kernel (ABI 117).  Where the form is in force az_engine_run's lock-step forwards
+ * stop behind fc2 and the step kernels that hold a backup (k_step_heads) compute the policy / value heads of their own slots' rows
+ * themselves, with k_heads2's arithmetic: four launches per lock-step for five, the same samples bit for bit.
+ *   switch   AZ_ENGINE_STEP_HEADS in the environment, read when the engine is created: unset = the measured rule (az_search_plan.h:
+ *            step_heads_auto), 0 = never, 1 = wherever served.
+ *   served   az_engine_run (any slot groups, the evaluation cache on or off) of an AZ_EVAL_NET engine in the plain PUCT search whose
+ *            net az_net_heads_view serves.  Not served, whatever the switch says: the playout cap, forced playouts, exact endgames,
+ *            proof backup, PUCT settings, the Gumbel search, leaf_batch > 1, either symmetry mode, the external, fake and rollout
+ *            evaluators; az_engine_search / _search_begin / az_engine_advance (the arena); a run whose net is under az_net_profile.
+ * az_engine_step_heads: in_force = whether the next az_engine_run would run the form, used = whether the last one did. */
+int az_engine_step_heads(az_engine *e, int32_t *in_force, int32_t *used);
 
 /* ---- exact endgames in the search -------------------------------------------------------------------------
  * Near the end of a game the outcome of a position is a short alpha-beta away (az_solve_batch above): with the mode on the search
