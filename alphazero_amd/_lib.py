@@ -75,6 +75,7 @@ SYMBOLS = [
     "az_engine_set_exact_endgame", "az_engine_exact_endgame_stats",
     "az_engine_set_proof_backup", "az_engine_proof_backup_stats", "az_engine_root_proofs",
     "az_engine_set_puct", "az_engine_puct", "az_puct_c", "az_puct_key",
+    "az_engine_set_resign", "az_engine_resign_stats", "az_engine_game_log", "az_engine_resign_values", "az_resign_value", "az_resign_holdout",
     "az_trainer_create", "az_trainer_destroy", "az_trainer_load", "az_trainer_store", "az_trainer_begin", "az_trainer_set_lr",
     "az_trainer_steps", "az_trainer_check", "az_trainer_debug", "az_trainer_buffer",
 ]
@@ -173,6 +174,12 @@ def lib():
     L.az_puct_c.restype = C.c_double
     L.az_puct_key.argtypes = [C.c_double, C.c_double, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
     L.az_puct_key.restype = C.c_double
+    L.az_engine_set_resign.argtypes = [vp, C.c_double, i32, i32, C.c_double]
+    L.az_engine_resign_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.az_engine_game_log.argtypes = [vp, C.POINTER(i64), C.POINTER(vp), C.POINTER(vp)]
+    L.az_engine_resign_values.argtypes = [vp, vp]
+    L.az_resign_value.argtypes = [i32, vp, vp, C.POINTER(C.c_double)]
+    L.az_resign_holdout.argtypes = [C.c_uint32, C.c_uint32, C.c_double]
     L.az_forced_playout.argtypes = [i32, C.c_double, i32, C.c_double]
     L.az_forced_prune.argtypes = [i32, vp, vp, vp, i32, C.c_double, vp]
     L.az_augment_count.argtypes = [C.c_int, vp, i64, C.POINTER(i64), vp]

@@ -78,6 +78,7 @@ enum { CTR_SAMPLES = 0, CTR_GAMES_DONE, CTR_NET_EVALS, CTR_NEXT_GAME, CTR_TOTAL_
        CTR_FULL_PLIES, CTR_FAST_PLIES,  // az_engine_set_playout_cap: the plies k_move played after a full / a fast search (counted while the mode is on)
        CTR_FORCED_PICKS, CTR_PRUNED,    // az_engine_set_forced_playouts: root selections with a forced child / playouts pruned from the recorded targets
        CTR_CACHE_HITS,                  // az_engine_set_eval_cache: leaves answered from the group's table (they count in CTR_NET_EVALS too)
+       CTR_RESIGNED, CTR_HOLDOUT_GAMES, CTR_HOLDOUT_TRIG, CTR_HOLDOUT_FP,  // az_engine_set_resign: counted by k_move when a game ends
        CTR_COUNT };
 // entries beyond CTR_COUNT live as long as the engine (k_reset_all clears [0, CTR_COUNT) only)
 enum { CTR_COLLISIONS = CTR_COUNT, CTR_ALLOC };
@@ -174,7 +175,26 @@ struct EngDev {
     // in force (az_engine_run alone sets them): then no kernel touches them.  (Last: the fields above keep their place.)
     const float *sh_h2, *sh_wq, *sh_hb;
     int sh_nt;
+    // az_engine_set_resign (k_move): the settings, the per-slot windows and the game log, in device memory.  One
+    // pointer, not the fields themselves: EngDev, an argument of every kernel, grows by eight bytes, and off is one null test.  (The
+    // mode-off headline measured 0.2 % under the parent's with the fields here and with the pointer alike; the cause is not found:
+    // DESIGN section 37.)  Null unless the mode is on AND the launch is az_engine_run's (rs_attach): k_move, and reset_slot under it and under
+    // k_reset_all, read it and no other kernel does.  (Last: the fields above keep their place.)
+    const struct ResignDev *rs;
 };
+// rs_k = the window length, rs_v = v_resign, rs_minply, rs_phold = the holdout share.  rs_win [G][2][AZ_RESIGN_MAX_K] = per slot and
+// side the last tested values as a ring, rs_cnt [G][2] = how many were pushed; gl_rows [gl_n][8] / gl_low [gl_n][2] = the game log of
+// the run, indexed by game id - first game id.
+struct ResignDev {
+    double rs_v, rs_phold;
+    int rs_k, rs_minply;
+    double *rs_win;
+    int *rs_cnt;
+    int *gl_rows;
+    double *gl_low;
+    int gl_n;
+};
+#define AZ_RESIGN_MAX_K 4
 // tag = ec_tag(hash, the claimer's stamp), 0 = empty: claimed by one device-scope compare-and-swap, never rewritten within a run; the
 // key is written by the claimer in the same kernel, the payload in the group's next one
 struct __attribute__((aligned(16))) EcHdr { u64 tag, p1, m1; long long player; };
@@ -829,13 +849,54 @@ AZ_D int propagate_proofs_grp(Node *pool, int plen, int my_node, int leaf, int r
     return marked;
 }
 
-AZ_D void reset_slot(const EngDev &E, int g, u32 game_id) {
+// Resignation in self-play (az_engine_set_resign; the contract is in include/az_amd.h and above its code in
+// k_move).  The two pieces of arithmetic the host can call (az_resign_value / az_resign_holdout are these on the host):
+//   the value of a ply, from the root's children in pool order i = 0 .. nc - 1 (N and Q each behind a byte stride: the kernels pass a
+//   Node's two fields, the host two plain arrays):  S_N = sum N_i;  S_Q = sum over N_i > 0 of (double)N_i * Q_i, in that order in
+//   float64;  v_mean = S_Q / (double)S_N;  v_best = Q of the child with the greatest N (the lowest index among equals);
+//   v = v_best > v_mean ? v_best : v_mean.  false (and *v untouched) when S_N == 0: the ply is untested.
+AZ_HD bool resign_value(int nc, const void *N, size_t n_stride, const void *Q, size_t q_stride, double *v) {
+    long long sn = 0;
+    double sq = 0.0, vbest = 0.0;
+    int best = -1;
+    for (int i = 0; i < nc; ++i) {
+        const int n = *reinterpret_cast<const int *>(static_cast<const char *>(N) + (size_t)i * n_stride);
+        const double q = *reinterpret_cast<const double *>(static_cast<const char *>(Q) + (size_t)i * q_stride);
+        if (n > 0) { sn += n; sq += (double)n * q; }
+        if (n > best) { best = n; vbest = q; }
+    }
+    if (sn == 0) return false;
+    const double vmean = sq / (double)sn;
+    *v = vbest > vmean ? vbest : vmean;
+    return true;
+}
+//   the holdout coin of a game: one draw per (seed, game id), never a function of the slot, the slot group or the batch
+#define AZ_P_RESIGN 11
+AZ_HD bool resign_holdout(u32 seed, u32 gid, double p_holdout) {
+    const Philox4 r = az_philox(seed, gid, 0u, 0xFFFFu, AZ_P_RESIGN, 0);
+    return az_u53(r.x, r.y) < p_holdout;
+}
+
+// first_id: the first game id of the run (the game log's row of game_id is game_id - first_id)
+AZ_D void reset_slot(const EngDev &E, int g, u32 game_id, u32 first_id) {
     BB b;
     start_position(E.gd, b);
     E.root_p1[g] = b.p1; E.root_m1[g] = b.m1; E.root_player[g] = (int8_t)b.player;
     E.root[g] = 0; E.n_nodes[g] = 1; E.ply[g] = 0; E.game_id[g] = game_id; E.active[g] = 1;
     E.leaf_status[g] = LS_NONE; E.evals[g] = 0; E.side[g] = 0; E.gmask[g] = 0;
     if (E.fpicks) E.fpicks[g] = 0;
+    if (E.rs) {  // az_engine_set_resign: both windows empty, the game's log row opened with its holdout coin
+        const ResignDev R = *E.rs;
+        R.rs_cnt[2 * g] = 0; R.rs_cnt[2 * g + 1] = 0;
+        const u32 at = game_id - first_id;
+        if (at < (u32)R.gl_n) {
+            int *row = R.gl_rows + (size_t)at * 8;
+            row[0] = (int)game_id; row[1] = 0; row[2] = 0; row[3] = 0;
+            row[4] = resign_holdout(E.seed, game_id, R.rs_phold) ? 1 : 0;
+            row[5] = -1; row[6] = 0; row[7] = 0;
+            R.gl_low[(size_t)at * 2] = 2.0; R.gl_low[(size_t)at * 2 + 1] = 2.0;
+        }
+    }
     store_node(pool_of(E, g), fresh_node(0, -1, 0.0, 0));
 }
 
@@ -856,7 +917,7 @@ __global__ void k_reset_all(EngDev E, u32 first_id, int n_games) {
     E.pool_sel[g] = 0;
     if (E.x_solved) { E.x_solved[g] = 0; E.x_nodes[g] = 0; }
     if (E.pf) { E.pf[g] = 0; E.pf[E.G + g] = 0; E.pf[2 * E.G + g] = 0; }
-    if (g < n_games) reset_slot(E, g, first_id + (u32)g);
+    if (g < n_games) reset_slot(E, g, first_id + (u32)g, first_id);
     else { E.active[g] = 0; E.leaf_status[g] = LS_NONE; }
 }
 
@@ -2121,6 +2182,7 @@ __global__ void k_move(EngDev E, int g0, int g1) {
         m[0] = (int)gid; m[1] = ply; m[2] = b.player; m[3] = action;
         E.o_z[si] = 0;
     }
+    const int mover = b.player;  // az_engine_set_resign: whose value the root's children hold
     az_play(gd, b, action);
     E.root_p1[g] = b.p1; E.root_m1[g] = b.m1; E.root_player[g] = (int8_t)b.player;
     E.root[g] = chosen;
@@ -2139,14 +2201,65 @@ __global__ void k_move(EngDev E, int g0, int g1) {
     }
     atomicMax(E.max_nodes, E.n_nodes[g]);
     int w = 0;
-    if (az_status(gd, b, &w)) {  // trainer.py:235, 262-265
+    bool over = az_status(gd, b, &w);
+    // Resignation (az_engine_set_resign; the contract is in include/az_amd.h).  The ply above is recorded, counted and played as ever;
+    // the test follows, and only if the rules have not ended the game.  A ply below rs_minply, a fast ply of the playout cap and a ply
+    // whose root children hold no visit (S_N == 0) are untested: they leave the window alone.  A tested ply pushes its value
+    // v = max(v_mean, v_best) (resign_value, from the raw N and Q of the children the search left under the old root: no pruning, no
+    // proofs, no completed Q) into the mover's window of its last rs_k tested values -- one window per side and slot, emptied by
+    // reset_slot.  m = the maximum of a full window; low[side] = the minimum of m over the game, 2.0 while the window was never full.
+    // The side triggers at the first ply where m < rs_v, so it triggers at a threshold t exactly when low < t.  On a trigger: in a
+    // holdout game (the coin of (seed, game id) in the log row, drawn by reset_slot) only the first one is noted -- ply and player --
+    // and the game goes on, low with it; otherwise the mover resigns: the game ends here with winner -mover, through the very z patch,
+    // CTR_GAMES_DONE and refill a finished game takes.  The log row is this slot's thread's alone: index game id - first id, no atomics.
+    // E.rs is null unless the mode is on and the launch is az_engine_run's: az_engine_advance and the arena never resign.
+    int *row = nullptr;
+    u32 at = 0;
+    ResignDev R = {};
+    if (E.rs) {
+        R = *E.rs;
+        at = gid - (u32)E.ctr[CTR_FIRST_ID];
+        if (at < (u32)R.gl_n) row = R.gl_rows + (size_t)at * 8;
+    }
+    if (row && !over && !fast && ply >= R.rs_minply) {
+        double v;
+        if (resign_value(nc, &pool[fc].N, sizeof(Node), &pool[fc].Q, sizeof(Node), &v)) {
+            const int s = mover == 1 ? 0 : 1;
+            double *win = R.rs_win + ((size_t)g * 2 + s) * AZ_RESIGN_MAX_K;
+            const int cnt = R.rs_cnt[2 * g + s];
+            win[cnt % R.rs_k] = v;
+            R.rs_cnt[2 * g + s] = cnt + 1;
+            if (cnt + 1 >= R.rs_k) {
+                double m = win[0];
+                for (int i = 1; i < R.rs_k; ++i) m = win[i] > m ? win[i] : m;
+                double *low = R.gl_low + (size_t)at * 2 + s;
+                if (m < *low) *low = m;
+                if (m < R.rs_v && row[5] < 0) {
+                    row[5] = ply; row[6] = mover;
+                    if (!row[4]) { over = true; w = -mover; row[3] = 1; }
+                }
+            }
+        }
+    }
+    if (over) {  // trainer.py:235, 262-265
         for (int p = 0; p <= ply; ++p) {
             int s2 = E.samp_idx[(size_t)g * E.max_plies + p];
             if (s2 >= 0) E.o_z[s2] = (int8_t)(w * E.o_meta[(size_t)s2 * 4 + 2]);
         }
+        if (row) {
+            row[1] = ply + 1; row[2] = w;
+            if (row[3]) atomicAdd(&E.ctr[CTR_RESIGNED], 1ULL);
+            if (row[4]) {
+                atomicAdd(&E.ctr[CTR_HOLDOUT_GAMES], 1ULL);
+                if (row[5] >= 0) {
+                    atomicAdd(&E.ctr[CTR_HOLDOUT_TRIG], 1ULL);
+                    if (w * row[6] >= 0) atomicAdd(&E.ctr[CTR_HOLDOUT_FP], 1ULL);  // the side that would have resigned did not lose
+                }
+            }
+        }
         atomicAdd(&E.ctr[CTR_GAMES_DONE], 1ULL);
         unsigned long long nx = atomicAdd(&E.ctr[CTR_NEXT_GAME], 1ULL);
-        if (nx < E.ctr[CTR_TOTAL_GAMES]) reset_slot(E, g, (u32)E.ctr[CTR_FIRST_ID] + (u32)nx);
+        if (nx < E.ctr[CTR_TOTAL_GAMES]) reset_slot(E, g, (u32)E.ctr[CTR_FIRST_ID] + (u32)nx, (u32)E.ctr[CTR_FIRST_ID]);
         else E.active[g] = 0;
     }
 }
@@ -2647,6 +2760,19 @@ struct az_engine {
     // only while it is on, else d.pf is null; proof_sums [3]: where k_proof_stats leaves the totals
     int *proof_ctr = nullptr;
     unsigned long long *proof_sums = nullptr;
+    // az_engine_set_resign: the settings live in rs (rs.rs_k == 0: off) and reach the device as *rs_dev, written at every run.  The
+    // per-slot windows and counts, [G][2][AZ_RESIGN_MAX_K] and [G][2], and rs_dev are allocated when the mode first goes on; the game
+    // log -- gl_rows [gl_cap][8], gl_low [gl_cap][2], memory of their own because a run with more games grows them -- at the run, for
+    // its n_games; gl_n = the rows of the last az_engine_run (0: it ran with the mode off).  d.rs == rs_dev only inside az_engine_run
+    // (rs_attach): every other entry
+    // point launches k_move with null pointers.  No captured search holds k_move, and no kernel of one reads these fields.
+    ResignDev rs = {};
+    ResignDev *rs_dev = nullptr;
+    double *rs_win = nullptr;
+    int *rs_cnt = nullptr;
+    int *gl_rows = nullptr;
+    double *gl_low = nullptr;
+    int gl_cap = 0, gl_n = 0;
     int groups_req = 0;
     bool groups_env = false;
     hipStream_t gstream[AZ_MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2752,6 +2878,7 @@ extern "C" int az_engine_create(const az_engine_cfg *cfg, az_net *net, void *str
     d.pf = nullptr;
     d.puct_cinit = 1.0; d.puct_cbase = 0.0; d.puct_fpu = -1.0;
     d.sh_h2 = nullptr; d.sh_wq = nullptr; d.sh_hb = nullptr; d.sh_nt = 0;
+    d.rs = nullptr;
     size_t G = d.G, NC = G * (size_t)d.C, S = (size_t)cfg->sample_capacity;
     int rc = AZ_OK;
 #define A_(p, n) if (rc == AZ_OK) rc = dev_alloc(e, &d.p, (n))
@@ -2822,6 +2949,8 @@ extern "C" void az_engine_destroy(az_engine *e) {
     for (auto &kv : e->graphs) (void)hipGraphExecDestroy(kv.second);
     for (void *p : e->allocs) (void)hipFree(p);
     for (int i = 0; i < AZ_MAX_GROUPS; ++i) { if (e->ec_hdr[i]) (void)hipFree(e->ec_hdr[i]); if (e->ec_pay[i]) (void)hipFree(e->ec_pay[i]); }
+    if (e->gl_rows) (void)hipFree(e->gl_rows);
+    if (e->gl_low) (void)hipFree(e->gl_low);
     if (e->ev_in) (void)hipEventDestroy(e->ev_in);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->h_ctr) (void)hipHostFree(e->h_ctr);
@@ -3278,6 +3407,37 @@ static void sh_detach(az_engine *e) {
     d.sh_h2 = nullptr; d.sh_wq = nullptr; d.sh_hb = nullptr; d.sh_nt = 0;
 }
 
+// ---- resignation in self-play (k_move) ------------------------------------------------------------------------------
+// A run with the mode on: the game log for its n_games (grown when this run has more games than any before; the engine's stream is
+// idle here, every entry point drains it before it returns), cleared on the engine's stream -- k_reset_all follows on it and every
+// group's stream is ordered behind that -- and the engine's device view pointing at the windows and the log until the run returns
+// (rs_detach).  With the mode off the log is empty.
+static int rs_attach(az_engine *e, int32_t n_games) {
+    EngDev &d = e->d;
+    e->gl_n = 0;
+    if (e->rs.rs_k == 0) return AZ_OK;
+    if (e->gl_cap < n_games) {
+        AZ_HIP(hipStreamSynchronize(e->stream));
+        if (e->gl_rows) { (void)hipFree(e->gl_rows); e->gl_rows = nullptr; }
+        if (e->gl_low) { (void)hipFree(e->gl_low); e->gl_low = nullptr; }
+        e->gl_cap = 0;
+        AZ_HIP(hipMalloc((void **)&e->gl_rows, (size_t)n_games * 8 * sizeof(int)));
+        AZ_HIP(hipMalloc((void **)&e->gl_low, (size_t)n_games * 2 * sizeof(double)));
+        e->gl_cap = n_games;
+    }
+    AZ_HIP(hipMemsetAsync(e->gl_rows, 0, (size_t)n_games * 8 * sizeof(int), e->stream));
+    AZ_HIP(hipMemsetAsync(e->gl_low, 0, (size_t)n_games * 2 * sizeof(double), e->stream));
+    e->gl_n = n_games;
+    e->rs.rs_win = e->rs_win; e->rs.rs_cnt = e->rs_cnt; e->rs.gl_rows = e->gl_rows; e->rs.gl_low = e->gl_low; e->rs.gl_n = n_games;
+    AZ_HIP(hipMemcpy(e->rs_dev, &e->rs, sizeof(ResignDev), hipMemcpyHostToDevice));  // blocking: k_reset_all is launched after it
+    d.rs = e->rs_dev;
+    return AZ_OK;
+}
+static void rs_detach(az_engine *e) {
+    EngDev &d = e->d;
+    d.rs = nullptr;
+}
+
 static int run_games(az_engine *e, uint32_t first_game_id, int32_t n_games);
 
 extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_games) {
@@ -3287,6 +3447,7 @@ extern "C" int az_engine_run(az_engine *e, uint32_t first_game_id, int32_t n_gam
     const int rc = run_games(e, first_game_id, n_games);
     ec_detach(e);
     sh_detach(e);
+    rs_detach(e);
     return rc;
 }
 
@@ -3307,6 +3468,7 @@ static int run_games(az_engine *e, uint32_t first_game_id, int32_t n_games) {
     if (eval_cache_on(e)) AZ_TRY(ec_attach(e, n_groups));
     e->sh_used = step_heads_on(e);
     if (e->sh_used) AZ_TRY(sh_attach(e));
+    AZ_TRY(rs_attach(e, n_games));
     hipLaunchKernelGGL(k_reset_all, grid_for(d.G, TB), dim3(TB), 0, e->stream, d, (u32)first_game_id, (int)n_games);
     long long max_iters = ((long long)n_games / d.G + 2) * (long long)d.max_plies + 8;
     e->active_bound = n_games < d.G ? n_games : d.G;
@@ -3985,6 +4147,97 @@ extern "C" int az_engine_playout_cap_stats(az_engine *e, int64_t *full_plies, in
 
 extern "C" int az_playout_cap_full(uint32_t seed, uint32_t game_id, int32_t ply, double p_full) {
     return playout_cap_full(seed, game_id, ply, p_full) ? 1 : 0;
+}
+
+// ---- resignation in self-play (k_move, k_resign_value) ---------------------------------------------------------------
+extern "C" int az_engine_set_resign(az_engine *e, double v_resign, int32_t consecutive, int32_t min_ply, double p_holdout) {
+    AZ_SETTER(e, "az_engine_set_resign");
+    EngDev &d = e->d;
+    const bool on = v_resign == v_resign;  // a NaN threshold is the mode off: the other three are then not looked at
+    if (!on) {
+        if (e->rs.rs_k == 0) return AZ_OK;
+    } else {
+        AZ_REQUIRE(v_resign >= -1.0 && v_resign < 0.0, AZ_EINVAL, "az_engine_set_resign: v_resign must be in [-1, 0) (NaN = off), got %g", v_resign);
+        AZ_REQUIRE(consecutive >= 1 && consecutive <= AZ_RESIGN_MAX_K, AZ_EINVAL, "az_engine_set_resign: consecutive must be in [1, %d], got %d", AZ_RESIGN_MAX_K, consecutive);
+        AZ_REQUIRE(min_ply >= 0, AZ_EINVAL, "az_engine_set_resign: min_ply must be >= 0, got %d", min_ply);
+        AZ_REQUIRE(p_holdout >= 0.0 && p_holdout <= 1.0, AZ_EINVAL, "az_engine_set_resign: p_holdout must be in [0, 1], got %g", p_holdout);
+        if (e->rs.rs_k == consecutive && e->rs.rs_v == v_resign && e->rs.rs_minply == min_ply && e->rs.rs_phold == p_holdout) return AZ_OK;
+    }
+    AZ_TRY(enter(e));
+    if (on && !e->rs_win) AZ_TRY(dev_alloc(e, &e->rs_win, (size_t)d.G * 2 * AZ_RESIGN_MAX_K));
+    if (on && !e->rs_cnt) AZ_TRY(dev_alloc(e, &e->rs_cnt, (size_t)d.G * 2));
+    if (on && !e->rs_dev) AZ_TRY(dev_alloc(e, &e->rs_dev, (size_t)1));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    e->rs.rs_k = on ? consecutive : 0; e->rs.rs_v = on ? v_resign : 0.0; e->rs.rs_minply = on ? min_ply : 0; e->rs.rs_phold = on ? p_holdout : 0.0;
+    // the settings are k_move's arguments alone, and k_move is launched, never captured: no cached search graph holds them
+    return AZ_OK;
+}
+
+extern "C" int az_engine_resign_stats(az_engine *e, int64_t *resigned, int64_t *holdout_games, int64_t *holdout_triggered, int64_t *holdout_false_positives) {
+    AZ_REQUIRE(e && resigned && holdout_games && holdout_triggered && holdout_false_positives, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_resign_stats");
+    AZ_USABLE(e, "az_engine_resign_stats");
+    AZ_TRY(enter(e));
+    AZ_TRY(fetch_counters(e));
+    *resigned = (int64_t)e->h_ctr[CTR_RESIGNED];
+    *holdout_games = (int64_t)e->h_ctr[CTR_HOLDOUT_GAMES];
+    *holdout_triggered = (int64_t)e->h_ctr[CTR_HOLDOUT_TRIG];
+    *holdout_false_positives = (int64_t)e->h_ctr[CTR_HOLDOUT_FP];
+    return AZ_OK;
+}
+
+// device views of the last az_engine_run's game log: n rows (0, and null pointers: that run had the mode off, or there was none)
+extern "C" int az_engine_game_log(az_engine *e, int64_t *n, const int32_t **d_rows, const double **d_low) {
+    AZ_REQUIRE(e && n, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_game_log");
+    AZ_USABLE(e, "az_engine_game_log");
+    AZ_TRY(enter(e));
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    *n = e->gl_n;
+    if (d_rows) *d_rows = e->gl_n > 0 ? e->gl_rows : nullptr;
+    if (d_low) *d_low = e->gl_n > 0 ? e->gl_low : nullptr;
+    return AZ_OK;
+}
+
+// the value of a ply (resign_value) for every slot's root as it stands: NaN where the slot holds no game, the root is not expanded
+// or its children hold no visit.  One thread per slot; reads only.
+__global__ void k_resign_value(EngDev E, double *out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= E.G) return;
+    double v = __builtin_nan("");
+    if (E.active[g]) {
+        const Node *pool = pool_of(E, g);
+        const int root = E.root[g];
+        if (pool[root].flags & F_EXPANDED) {
+            const int fc = pool[root].first, nc = pool[root].nch;
+            double r;
+            if (nc > 0 && resign_value(nc, &pool[fc].N, sizeof(Node), &pool[fc].Q, sizeof(Node), &r)) v = r;
+        }
+    }
+    out[g] = v;
+}
+
+extern "C" int az_engine_resign_values(az_engine *e, double *d_v) {
+    AZ_REQUIRE(e && d_v, AZ_EINVAL, "null argument");
+    AZ_NO_OPEN_SEARCH(e, "az_engine_resign_values");
+    AZ_USABLE(e, "az_engine_resign_values");
+    AZ_TRY(enter(e));
+    hipLaunchKernelGGL(k_resign_value, grid_for(e->d.G, TB), dim3(TB), 0, e->stream, e->d, d_v);
+    AZ_HIP(hipGetLastError());
+    AZ_HIP(hipStreamSynchronize(e->stream));
+    return AZ_OK;
+}
+
+extern "C" int az_resign_value(int32_t n_children, const int32_t *N, const double *Q, double *v) {
+    AZ_REQUIRE(n_children >= 0 && v && (n_children == 0 || (N && Q)), AZ_EINVAL, "az_resign_value: null argument or a negative count");
+    for (int i = 0; i < n_children; ++i) AZ_REQUIRE(N[i] >= 0, AZ_EINVAL, "az_resign_value: N[%d] = %d is negative", i, N[i]);
+    double r = 0.0;
+    *v = resign_value(n_children, N, sizeof(int32_t), Q, sizeof(double), &r) ? r : __builtin_nan("");
+    return AZ_OK;
+}
+
+extern "C" int az_resign_holdout(uint32_t seed, uint32_t game_id, double p_holdout) {
+    return resign_holdout(seed, game_id, p_holdout) ? 1 : 0;
 }
 
 // ---- forced playouts and policy target pruning (k_step_forced, move_policy) -------------------------------------

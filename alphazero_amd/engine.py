@@ -39,7 +39,7 @@ class _DevView:
 
 
 def _wrap(ptr, shape, dtype, owner):
-    typestr = {torch.int8: "|i1", torch.float32: "<f4", torch.int32: "<i4", torch.uint8: "|u1"}[dtype]
+    typestr = {torch.int8: "|i1", torch.float32: "<f4", torch.int32: "<i4", torch.uint8: "|u1", torch.float64: "<f8"}[dtype]
     if int(np.prod(shape)) == 0:
         return torch.empty(shape, dtype=dtype, device="cuda")
     return torch.as_tensor(_DevView(ptr, shape, typestr, owner), device="cuda")
@@ -433,6 +433,64 @@ class SelfPlayEngine:
     def playout_cap_full(seed, game_id, ply, p_full):
         """the playout cap's coin of (seed, game id, ply): True = a full ply (az_playout_cap_full: host code, the kernels' arithmetic)"""
         return bool(lib().az_playout_cap_full(int(seed) & 0xFFFFFFFF, int(game_id) & 0xFFFFFFFF, int(ply), float(p_full)))
+
+    def set_resign(self, resign):
+        """resignation in run() (az_engine_set_resign): None = off, or a dict of threshold, consecutive, min_ply,
+        holdout (alphazero_amd.resign) -- a side whose value max(v_mean, v_best) stayed below the threshold for `consecutive` tested
+        plies resigns, except in the holdout share of the games, which are played out and only note the trigger.  holdout = 1.0
+        records the game log and changes no sample.  Served by run() in every search mode; advance() never resigns."""
+        from .resign import parse
+        r = parse(resign)
+        if r is None:
+            check(lib().az_engine_set_resign(self.h, float("nan"), 0, 0, 0.0))
+        else:
+            check(lib().az_engine_set_resign(self.h, r["threshold"], r["consecutive"], r["min_ply"], r["holdout"]))
+
+    def resign_stats(self):
+        """{"resigned", "holdout_games", "holdout_triggered", "holdout_false_positives"} of the games ended since the last run() /
+        set_roots(); all 0 with the mode off"""
+        v = [C.c_int64() for _ in range(4)]
+        check(lib().az_engine_resign_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("resigned", "holdout_games", "holdout_triggered", "holdout_false_positives"), (x.value for x in v)))
+
+    GAME_LOG_COLUMNS = ("game_id", "plies", "winner", "ended", "holdout", "trigger_ply", "trigger_player")
+
+    def game_log(self):
+        """the game log of the last run() as a dict of CUDA tensors (copies): one entry per game at index game id - first_game_id --
+        the int32 [n] columns game_id, plies, winner, ended (0 the rules / 1 resignation), holdout, trigger_ply (-1: none),
+        trigger_player (0: none), the rows themselves as "rows" int32 [n, 8], and "low" float64 [n, 2] (column 0 player +1, column 1
+        player -1; 2.0: the window was never full).  n = 0 when that run had resignation off."""
+        n, rows, low = C.c_int64(), C.c_void_p(), C.c_void_p()
+        check(lib().az_engine_game_log(self.h, C.byref(n), C.byref(rows), C.byref(low)))
+        r = _wrap(rows.value, (n.value, 8), torch.int32, self).clone()
+        out = {k: r[:, i].contiguous() for i, k in enumerate(self.GAME_LOG_COLUMNS)}
+        out["rows"] = r
+        out["low"] = _wrap(low.value, (n.value, 2), torch.float64, self).clone()
+        return out
+
+    def resign_values(self):
+        """float64 [n_slots] on the device: the resignation rule's value max(v_mean, v_best) of every slot's root as it stands, NaN
+        where the root's children hold no visit or the slot holds no game (az_engine_resign_values; one launch, reads only)"""
+        out = torch.empty(self.cfg.n_slots, dtype=torch.float64, device="cuda")
+        check(lib().az_engine_resign_values(self.h, out.data_ptr()))
+        return out
+
+    @staticmethod
+    def resign_value(N, Q):
+        """the rule's value of a root whose children, in child order, have visit counts N and values Q; NaN when no child was visited
+        (az_resign_value: host code, the kernels' arithmetic)"""
+        N = np.ascontiguousarray(N, np.int32)
+        Q = np.ascontiguousarray(Q, np.float64)
+        if not (N.ndim == Q.ndim == 1 and len(N) == len(Q)):
+            raise ValueError("resign_value: N and Q are one-dimensional and of one length")
+        v = C.c_double()
+        check(lib().az_resign_value(len(N), N.ctypes.data, Q.ctypes.data, C.byref(v)))
+        return v.value
+
+    @staticmethod
+    def resign_holdout(seed, game_id, p):
+        """the holdout coin of (seed, game id): True = the game is played out whatever the rule says (az_resign_holdout: host code)"""
+        return bool(lib().az_resign_holdout(int(seed) & 0xFFFFFFFF, int(game_id) & 0xFFFFFFFF, float(p)))
 
     def set_forced_playouts(self, k):
         """forced playouts and policy target pruning (az_engine_set_forced_playouts): None = off, or k in (0, 64]

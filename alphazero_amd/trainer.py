@@ -63,7 +63,8 @@ class AlphaZeroTrainer:
 
     def __init__(self, verbose=False, engine_slots=4096, seed=0, materialize_memory=True, selfplay_symmetry=None,
                  selfplay_gumbel=None, selfplay_gumbel_batch=1, selfplay_gumbel_full=False, selfplay_playout_cap=None, selfplay_forced_playouts=None,
-                 selfplay_exact_endgame=None, selfplay_proof_backup=False, selfplay_puct=None, eval_search=None, eval_opening_plies=None):
+                 selfplay_exact_endgame=None, selfplay_proof_backup=False, selfplay_puct=None, selfplay_resign=None, eval_search=None,
+                 eval_opening_plies=None):
         self.game = self.config = self.board = self.nn = self.nn_twin = None
         self.az_player = self.temp_scheduler = self.data_augment_strategy = None
         self.memory = self.loss_values = self.eval_results = None
@@ -131,6 +132,15 @@ class AlphaZeroTrainer:
         # opponent too.  eval_opening_plies: BatchedArena's `opening_plies`, the seeded opening that makes the rounds different games.
         self.eval_search, self.eval_opening_plies = eval_search, eval_opening_plies
         self._eval_search_spec()
+        # resignation in that wave: None (off) or a dict of threshold, consecutive, min_ply, holdout and calibrate
+        # (alphazero_amd.resign) -- a game whose search value stayed below the threshold is given up, except in the holdout share, which
+        # measures the rule's false positives.  calibrate = a target false-positive rate: after each wave the next threshold is
+        # resign.calibrate of the wave's game log.  The self-play engine alone, in every search mode.  resign_threshold is the
+        # threshold of the next wave, resign_stats[iteration] what each wave did.
+        self.selfplay_resign = selfplay_resign
+        r = self._check_selfplay_resign()
+        self.resign_threshold = None if r is None else r["threshold"]
+        self.resign_stats = {}
 
     def _eval_search_spec(self, nn=None):
         """BatchedArena's `search` dict for the evaluation (None: today's arena), checked -- against `nn` too when it is given"""
@@ -157,6 +167,14 @@ class AlphaZeroTrainer:
             raise ValueError(f"selfplay_playout_cap={self.selfplay_playout_cap!r} does not combine with selfplay_symmetry={self.selfplay_symmetry!r}: "
                              f"the playout cap is served in the plain PUCT search only")
         return cap
+
+    def _check_selfplay_resign(self):
+        from .resign import parse
+        r = parse(self.selfplay_resign, "selfplay_resign", calibrate=True)
+        if r is not None and r["calibrate"] is not None and self._dist()[1] > 1:
+            raise ValueError(f"selfplay_resign={self.selfplay_resign!r}: calibrate is not served with more than one rank (the game logs "
+                             f"would have to be gathered across the ranks); a fixed threshold is")
+        return r
 
     def _check_selfplay_forced_playouts(self):
         from .forced_playouts import parse
@@ -347,6 +365,17 @@ class AlphaZeroTrainer:
             self._engine._proof_backup = proof
         if self._engine.puct != puct:  # ValueError for a network routed to the external evaluator
             self._engine.set_puct({"c_init": puct[0], "c_base": puct[1], "fpu": puct[2]})
+        resign = self._check_selfplay_resign()  # ValueError for calibrate with more than one rank
+        if resign is None:
+            self.resign_threshold = None
+        else:
+            if self.resign_threshold is None:  # the option was assigned after construction: its own threshold starts the series
+                self.resign_threshold = resign["threshold"]
+            resign = {k: resign[k] for k in ("consecutive", "min_ply", "holdout")}
+            resign["threshold"] = self.resign_threshold  # the calibrated one from the second wave on
+        if resign != getattr(self._engine, "_resign", None):
+            self._engine.set_resign(resign)
+            self._engine._resign = resign
         return self._engine
 
     def _run_engine(self, eng, n_games, first_game_id):
@@ -391,6 +420,7 @@ class AlphaZeroTrainer:
                        "z": torch.zeros(0, dtype=torch.int8, device="cuda"), "meta": torch.zeros((0, 4), dtype=torch.int32, device="cuda"),
                        "visits": torch.zeros((0, A), dtype=torch.int32, device="cuda")}
             smp = {k: v.cuda() for k, v in all_gather_samples(smp).items()}
+        self._after_wave_resign(eng, iter_idx)
         meta = smp["meta"]
         order = torch.argsort(meta[:, 0].long() * 4096 + meta[:, 1].long())  # (episode, move) order of the reference's loop
         smp = {k: v[order].contiguous() for k, v in smp.items()}
@@ -410,6 +440,26 @@ class AlphaZeroTrainer:
             self.memory = [Sample(state=st[i], pi=pi[i], player=1, outcome=int(z[i]), episode_idx=int(mt[i, 0]), move_idx=int(mt[i, 1]),
                                   transformation=None if i < S else TRANSFORM_NAMES[mt[i, 3]]) for i in range(len(z))]
         self.print(f"Total number of samples: {self.device_memory['z'].shape[0]}")
+
+    def _after_wave_resign(self, eng, iter_idx):
+        """selfplay_resign: this rank's counters of the wave into resign_stats[iter_idx] and the log line; with calibrate, the next
+        wave's threshold from the wave's game log (resign.calibrate over its holdout games)"""
+        r = self._check_selfplay_resign()
+        if r is None:
+            return
+        st = eng.resign_stats()
+        st.update(threshold=self.resign_threshold, games=eng.stats()["games_done"])
+        if r["calibrate"] is not None:
+            from .resign import calibrate
+            log = eng.game_log()
+            self.resign_threshold = calibrate(log["low"].cpu().numpy(), log["winner"].cpu().numpy(), r["calibrate"], self.resign_threshold,
+                                              holdout=log["holdout"].cpu().numpy())
+            st["next_threshold"] = self.resign_threshold
+        self.resign_stats[iter_idx] = st
+        self.print(f"Resignation: threshold {st['threshold']:.4f}, {st['resigned']} of {st['games']} games resigned, "
+                   f"{st['holdout_games']} held out, {st['holdout_triggered']} of them triggered, "
+                   f"{st['holdout_false_positives']} false positives"
+                   + (f", next threshold {st['next_threshold']:.4f}" if "next_threshold" in st else ""))
 
     # ------------------------------------------------------------------ optimisation (trainer.py:288-387)
     def _n_samples(self):
@@ -661,6 +711,9 @@ class AlphaZeroTrainer:
         path = self._model_dir(model_name, path)
         with open(os.path.join(path, "loss.json"), "w") as f:
             json.dump(self.loss_values, f, indent=4)
+        if self.selfplay_resign is not None:
+            with open(os.path.join(path, "resign.json"), "w") as f:
+                json.dump(self.resign_stats, f, indent=4)
         if self.config.do_eval:
             with open(os.path.join(path, "eval.json"), "w") as f:
                 json.dump(self.eval_results, f, indent=4)

@@ -560,6 +560,59 @@ int az_engine_forced_playouts_stats(az_engine *e, int64_t *forced_picks, int64_t
 int az_forced_playout(int32_t n, double p, int32_t root_n, double k);
 int az_forced_prune(int32_t n_children, const int32_t *N, const double *Q, const double *P, int32_t root_n, double k, int32_t *out_N);
 
+/* ---- resignation in self-play: a value threshold, a holdout and a game log ---------------------------------------
+ * AlphaGo Zero / AlphaZero (Silver et al. 2017, "Mastering the game of Go without human knowledge", Methods: self-play): a game whose
+ * search value has fallen below v_resign is given up; a share of the games is played out anyway so that the threshold's
+ * false-positive rate is known, and v_resign is set from that share.  The reference has no counterpart: it plays every game to the
+ * end (trainer.py:215-273).  Opt-in, default off: with the mode off no launch, kernel, allocation or output bit differs from an
+ * engine that never had it on, and the four counters read 0.  Every operation below is one IEEE double operation in the order written.
+ *   settings      v_resign in [-1, 0); consecutive = k in [1, 4]; min_ply >= 0; p_holdout in [0, 1].  OFF is spelled v_resign = NaN
+ *                 (the other three are then not looked at).  AZ_EINVAL outside the ranges, AZ_ESTATE while a search is open.  The
+ *                 settings are arguments of k_move alone, which is launched and never captured: no cached search graph holds them,
+ *                 so a change drops none.
+ *   value of a ply  from the root's children after the ply's search, in pool order i = 0 .. nc - 1:  S_N = sum N_i;
+ *                 S_Q = sum over N_i > 0 of (double)N_i * Q_i, accumulated in that order in float64;  v_mean = S_Q / (double)S_N;
+ *                 v_best = Q of the child with the greatest N (the lowest child index among equals);
+ *                 v = v_best > v_mean ? v_best : v_mean.  A child's Q is the value for the root's mover.  The rule reads the raw N
+ *                 and Q only: forced playouts are not pruned, proofs and the Gumbel search's completed Q are not consulted.
+ *                 S_N == 0: the ply is untested.  az_resign_value is this arithmetic as pure host code, the function the kernels
+ *                 call: *v = the value, NaN when S_N == 0; AZ_EINVAL for a null argument or a negative count.
+ *   tested plies  the test runs when the ply's move is played (k_move), after the ply was recorded, counted and played exactly as
+ *                 with the mode off, and only if the rules have not ended the game.  A ply p < min_ply is untested, and so is a fast
+ *                 ply of the playout cap.  A tested ply pushes v into the mover's window of its last k tested values (one window per
+ *                 side and game).  m = the maximum of a full window; low[side] = the minimum of m over the game, 2.0 while the
+ *                 window has never been full.  The side TRIGGERS at the first ply where m < v_resign -- so it triggers at a
+ *                 threshold t exactly when low < t, the statistic calibration needs.
+ *   holdout       per game: r = Philox4x32-10 keyed (seed, game_id) at counter (0, 0xFFFF, AZ_P_RESIGN = 11, 0), u = az_u53 of (r.x, r.y);
+ *                 the game is a holdout iff u < p_holdout.  Never a function of the slot, the slot group or the batch.
+ *                 az_resign_holdout: the coin as pure host code, 1 = holdout.
+ *   on a trigger  in a game that is not a holdout the mover resigns: the game ends at that ply with winner -mover, z is written with
+ *                 that winner, games_done moves and the slot is refilled, on the path a finished game takes.  The ply just played
+ *                 stays recorded and counted (under the playout cap samples == full_plies and plies == full + fast still hold).
+ *                 In a holdout game only the first trigger is noted (ply, player); the game goes on and low keeps updating.
+ *   counters      az_engine_resign_stats, since the last az_engine_run / az_engine_set_roots, counted as games end: resigned;
+ *                 holdout_games; holdout_triggered = holdout games with a trigger; holdout_false_positives = those of them with
+ *                 winner * trigger_player >= 0 (the side that would have resigned did not lose).
+ *   game log      kept while the mode is on: one row per game of the last az_engine_run at index game_id - first_game_id, whatever
+ *                 order the games finish in.  Row = int32[8]: game_id, plies, winner, ended (0 the rules / 1 resignation), holdout,
+ *                 trigger_ply (-1 none), trigger_player (0 none), 0.  Beside it low = double[2] per game: [0] player +1, [1] player
+ *                 -1.  az_engine_game_log returns n and DEVICE views valid until the next az_engine_run or az_engine_destroy; n = 0
+ *                 and null views when the last run had the mode off.  p_holdout = 1.0 is the record-only form: every game is logged,
+ *                 none is resigned, and the samples are bit-equal to the mode off.
+ *   served        az_engine_run with 1, 2 or 4 slot groups, in every search mode and with every evaluator the run serves: the rule
+ *                 reads the root's children and nothing else.  az_engine_advance and the arena never resign, whatever the setting.
+ *                 A game still depends on (seed, game id, the settings) only.
+ *   readout       az_engine_resign_values: d_v[slot] (device, double [n_slots]) = v of the slot's root as it stands, NaN where
+ *                 S_N == 0, the root is not expanded or the slot holds no game.  One launch (k_resign_value), with the mode on or
+ *                 off: a caller of the batched players or the arena applies its own rule with it. */
+int az_engine_set_resign(az_engine *e, double v_resign, int32_t consecutive, int32_t min_ply, double p_holdout);
+int az_engine_resign_stats(az_engine *e, int64_t *resigned, int64_t *holdout_games, int64_t *holdout_triggered,
+                           int64_t *holdout_false_positives);
+int az_engine_game_log(az_engine *e, int64_t *n, const int32_t **d_rows, const double **d_low);
+int az_engine_resign_values(az_engine *e, double *d_v);
+int az_resign_value(int32_t n_children, const int32_t *N, const double *Q, double *v);
+int az_resign_holdout(uint32_t seed, uint32_t game_id, double p_holdout);
+
 /* ---- leaf evaluation cache -------------------------------------------------------------------------------
  * Every game of an az_engine_run wave starts from the same position under one set of weights, and the network is a pure function
  * of (board, side to move): each slot group keeps a table of the network's outputs by exact position, filled and read on the device
