@@ -186,7 +186,9 @@ class MCT:
         else:
             # one lock-step per chunk: a simulation, or leaf_batch of them
             chunk = check_leaf_batch(self.leaf_batch, None) if self.eval_method == TreeEval.NEURAL else 8
-            while time() - start < compute_time:
+            # at least one chunk: the clock started before _sync_device_root, which may have built the engine (longer than a short budget),
+            # and a root without a visit has no move to return
+            while self.n_rollouts == 0 or time() - start < compute_time:
                 self._ensure_room(chunk)
                 self._device_search(chunk)
                 self.n_rollouts += chunk

@@ -397,6 +397,12 @@ def test_players_play_with_leaf_batch():
     assert n_rollouts >= 4 and n_rollouts % 4 == 0 and timed.mct._engine.root_children(0)[4] == n_rollouts
     timed.mct._engine.close()
 
+    # a budget shorter than the engine's own construction still searches one chunk: the root has visits and get_move a move to return
+    brief = AlphaZeroPlayer(compute_time=1e-9, nn=net, leaf_batch=4)
+    move, probs, counts, _ = brief.get_move(OthelloBoard(n=6))
+    assert brief.mct.get_stats()[0] == 4 and brief.mct._engine.root_children(0)[4] == 4 and len(counts) > 0 and probs == {move: 1}
+    brief.mct._engine.close()
+
     # 20 boards at once == 20 single-board searches under the same seeds and game ids (random ties: the draws depend on both)
     rng = np.random.default_rng(17)
     boards = []

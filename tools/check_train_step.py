@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The hand-written training step (csrc/az_train.hip) against torch autograd in float64 on the CPU: every activation, every
 gradient the step keeps in its workspace, the losses, and the parameters / BatchNorm statistics after k steps.
-    python tools/check_train_step.py [tag] [batch] [steps] [dropout]      tag: othello8 | othello6 | connect4
+    python tools/check_train_step.py [tag] [batch] [steps] [dropout]      tag: othello8 | othello6 | connect4 | connect4_<W>x<H> | tictactoe
 Prints one line per buffer (max abs error, scale); tests/test_gpu_train_step.py asserts on the same report.
     python tools/check_train_step.py --update-profile
 The parameter update at its own scale (gradients from one step at momentum 0 / weight decay 0, the hyper-parameters as identities of
@@ -10,6 +10,7 @@ The step as a function of nothing but its inputs (StateProblem, state_run, poiso
 tests/test_gpu_train_state.py."""
 import copy
 import os
+import re
 import sys
 
 import numpy as np
@@ -24,8 +25,11 @@ def make_net(tag, seed=0):
     from alphazero_amd.games.othello import OthelloNet
     torch.manual_seed(seed)
     from alphazero_amd.games.tictactoe import TicTacToeNet
-    net = {"othello8": lambda: OthelloNet(n=8), "othello6": lambda: OthelloNet(n=6), "connect4": lambda: Connect4Net(7, 6), "connect4_8x5": lambda: Connect4Net(8, 5),
-           "connect4_5x8": lambda: Connect4Net(5, 8), "tictactoe": lambda: TicTacToeNet()}[tag]()
+    plane = re.fullmatch(r"connect4_(\d+)x(\d+)", tag)  # connect4_<W>x<H>: Connect4Net(W, H) on any plane; "connect4" is the standard 7x6
+    if plane:
+        net = Connect4Net(int(plane.group(1)), int(plane.group(2)))
+    else:
+        net = {"othello8": lambda: OthelloNet(n=8), "othello6": lambda: OthelloNet(n=6), "connect4": lambda: Connect4Net(7, 6), "tictactoe": lambda: TicTacToeNet()}[tag]()
     with torch.no_grad():  # BatchNorm affine / running statistics away from their defaults, so that a mix-up shows
         for m in net.modules():
             if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
@@ -43,8 +47,17 @@ def make_samples(net, S, seed=1):
     return state, pi, z
 
 
-def torch_step(net, x, pi, z, bs, masks=None, p=0.0):
-    """forward + backward of the reference's loss with every intermediate kept (float64 module)"""
+def _relu(x, name, flip):
+    """F.relu, or with flip = (layer, flat index) and that layer's name: the same with that ONE unit on the other branch"""
+    if flip is None or flip[0] != name:
+        return F.relu(x)
+    m = (x > 0).to(x.dtype)
+    m.view(-1)[flip[1]] = 1.0 - m.view(-1)[flip[1]]
+    return x * m
+
+
+def torch_step(net, x, pi, z, bs, masks=None, p=0.0, flip=None):
+    """forward + backward of the reference's loss with every intermediate kept (float64 module); flip: see relu_flip_effect"""
     keep = {}
     if not hasattr(net, "conv1"):  # TicTacToeNet: the module's own forward (no workspace to compare: the step is one launch)
         logp, v = net(x)
@@ -61,19 +74,19 @@ def torch_step(net, x, pi, z, bs, masks=None, p=0.0):
     for i, (conv, bn) in enumerate(((net.conv1, net.bn1), (net.conv2, net.bn2), (net.conv3, net.bn3), (net.conv4, net.bn4))):
         c = k(f"c{i + 1}", conv(h))
         b = k(f"b{i + 1}", bn(c))
-        h = F.relu(b)
+        h = _relu(b, f"b{i + 1}", flip)
     h = h.reshape(-1, net.fc1_input_size)
     y1 = k("y1", net.fc1(h))
     a1 = net.fc_bn1(y1)
     keep["a1"] = a1
-    h1 = F.relu(a1)
+    h1 = _relu(a1, "a1", flip)
     if masks is not None:
         h1 = h1 * masks[0] / (1.0 - p)
     h1 = k("h1", h1)
     y2 = k("y2", net.fc2(h1))
     a2 = net.fc_bn2(y2)
     keep["a2"] = a2
-    h2 = F.relu(a2)
+    h2 = _relu(a2, "a2", flip)
     if masks is not None:
         h2 = h2 * masks[1] / (1.0 - p)
     h2 = k("h2", h2)
@@ -102,6 +115,32 @@ def relu_ties(keep, rel=2e-6):
             n = int((x < rel * m).sum())
             if n:
                 out.append((name, n, float(x.min()) / m))
+    return out
+
+
+def relu_flip_effect(tag, B, seed=0, rel=2e-6, closest_only=False):
+    """What ONE ReLU unit on the other branch does to the gradients of problem(tag, B, 1, seed), in float64 on the CPU: for every unit
+    relu_ties() counts (closest_only: the one with the smallest |x| / max|x| of its layer, over all layers), the float64 step again
+    with that unit's branch forced the other way -> [(layer, flat index, |x| / max|x|, err / max|g_ref|)], the last figure being
+    gradient_check's "rel" of the forced run against the plain one.  A float32 step that resolved that tie the other way shows exactly
+    this error and nothing else: it tells a flipped unit (the data's property; the seed is replaced) from a wrong kernel."""
+    net, state, pi, z, perm = problem(tag, B, 1, seed)
+    m = copy.deepcopy(net).double().train()
+    args = (state[perm].double(), pi[perm].double(), z[perm].double().unsqueeze(1), B)
+
+    def grads(flip):
+        m.zero_grad()
+        _, _, keep = torch_step(m, *args, flip=flip)  # (train mode moves the running statistics; the batch statistics do not read them)
+        return {k: p.grad.clone() for k, p in m.named_parameters() if not zero_gradient(k)}, keep
+    g0, keep = grads(None)
+    units = []
+    for name in ("b1", "b2", "b3", "b4", "a1", "a2"):
+        x = keep[name].detach().abs().reshape(-1)
+        units += [(float(x[i]) / float(x.max()), name, i) for i in (x < rel * float(x.max())).nonzero().flatten().tolist()]
+    out = []
+    for r, name, i in (sorted(units)[:1] if closest_only else units):
+        g1, _ = grads((name, i))
+        out.append((name, i, r, max(float((g1[k] - g0[k]).abs().max()) / float(g0[k].abs().max()) for k in g0)))
     return out
 
 
@@ -208,6 +247,43 @@ def report(tag="othello8", B=64, steps=3, dropout=0.0, verbose=True, seed=0, lr=
 # p1 = p0 - L g, so (p0 - p1) / L is the gradient; the other hyper-parameters are checked as identities of the step with itself.
 UPDATE_CASES = ([("othello8", b) for b in (16, 64, 128, 144, 320, 512)] + [("othello6", b) for b in (48, 80, 400)] + [("connect4", b) for b in (32, 144, 512)]
                 + [("connect4_5x8", 64)] + [("tictactoe", b) for b in (2, 64, 250)])
+# Every Connect4 plane the trainer accepts (width and height 5..8: CH = W, CW = H, P4 = (W - 4)(H - 4), FIN = 32 P4, A = W outputs), for
+# tests/test_gpu_train_planes.py: (tag, batch, seeds) of gradient_check; seeds 0-2 or 0, except where the float32 step resolves a ReLU tie of
+# the float64 run the other way (the rule: PLANE_FLIPS below; the replaced seed is named beside its replacement).  UPDATE_CASES above holds 7x6 and 5x8; these rows hold the
+# other fourteen.  Dense dispatches of plan_train_step: <= 64 rows <4,16,1,0> | 65..128 <8,8,1,0> | 144..368 row-split, 64-row blocks |
+# >= 384 row-split, 128-row blocks (fc2 on 64-row blocks, the late fc1 weight gradient in k_conv1_bwd); 144 and 400 end in a 16-row block.
+PLANE_CASES = [
+    # the extreme planes at every dense dispatch, seeds 0-2
+    ("connect4_5x5", 16, (0, 1, 2)),    # FIN 32, P4 1 (conv4 output 1x1, conv3 3x3): 2 K steps, 2 of 16 waves work one step each; <4,16,1,0> with one row tile
+    ("connect4_5x5", 128, (0, 1, 2)),   # FIN 32, P4 1: 2 of 8 waves work; <8,8,1,0>; 2 live fc1 weight-gradient tiles in a 4-wave block
+    ("connect4_5x5", 144, (0, 1, 2)),   # FIN 32, P4 1: row-split, 64-row blocks, last block 16 rows
+    ("connect4_5x5", 400, (0, 1, 2)),   # FIN 32, P4 1: row-split, 128-row blocks, last block 16 rows; late fc1 weight gradient: 2 tiles
+    ("connect4_7x7", 16, (0, 1, 2)),    # FIN 288, P4 9 (3x3): 18 K steps over 16 waves, 9 waves of 2 steps work; <4,16,1,0>; bn4 sums 9 = 8 + 1 positions
+    ("connect4_7x7", 128, (0, 1, 2)),   # FIN 288, P4 9: 18 K steps over 8 waves, 6 waves of 3 steps work (an odd count in the two-deep prefetch loop); <8,8,1,0>
+    ("connect4_7x7", 144, (0, 1, 2)),   # FIN 288, P4 9: row-split, 64-row blocks, last block 16 rows; 18 fc1 weight-gradient tiles, no multiple of 4
+    ("connect4_7x7", 400, (0, 1, 2)),   # FIN 288, P4 9: row-split, 128-row blocks, last block 16 rows; late fc1 weight gradient: 18 tiles
+    ("connect4_8x8", 16, (0, 1, 2)),    # FIN 512, P4 16, P1 64 with F1 64 / F2 32 (Othello8's plane, Connect4's dense widths); <4,16,1,0>
+    ("connect4_8x8", 128, (3, 1, 2)),   # (seed 0 flips b4[9907]) FIN 512, P4 16, P1 64; <8,8,1,0>
+    ("connect4_8x8", 144, (0, 1, 2)),   # FIN 512, P4 16, P1 64; row-split, 64-row blocks, last block 16 rows
+    ("connect4_8x8", 400, (0, 1, 3)),   # (seed 2 flips b4[84663]) FIN 512, P4 16, P1 64; row-split, 128-row blocks, last block 16 rows
+    # every other plane never held to float64 at the update's scale, once, with the dispatch rotated
+    ("connect4_5x6", 32, (0,)),         # FIN 64, P4 2 (1x2); <4,16,1,0>: 4 K steps for 16 waves
+    ("connect4_6x5", 128, (0,)),        # FIN 64, P4 2 (2x1), 6 outputs; <8,8,1,0>
+    ("connect4_5x7", 144, (0,)),        # FIN 96, P4 3 (1x3): 6 K steps, 6 fc1 weight-gradient tiles; row-split 64, last block 16 rows
+    ("connect4_7x5", 400, (0,)),        # FIN 96, P4 3 (3x1); row-split 128, last block 16 rows; late fc1 weight gradient: 6 tiles
+    ("connect4_6x6", 64, (0,)),         # FIN 128, P4 4 (2x2), 6 outputs; <4,16,1,0> at its largest batch
+    ("connect4_6x7", 48, (0,)),         # FIN 192, P4 6 (2x3: the relayout's H4 / W4 order shows), 6 outputs; <4,16,1,0>, three row tiles
+    ("connect4_6x8", 272, (1,)),        # (seed 0 flips b2[227885], in the stock float32 torch step too) FIN 256, P4 8 (2x4), 6 outputs; row-split 64: four full blocks and one of 16 rows
+    ("connect4_8x6", 16, (0,)),         # FIN 256, P4 8 (4x2); <4,16,1,0>, one row tile
+    ("connect4_7x8", 384, (0,)),        # FIN 384, P4 12 (3x4); row-split 128: three full blocks
+    ("connect4_8x7", 96, (0,)),         # FIN 384, P4 12 (4x3); <8,8,1,0>, six row tiles
+    ("connect4_8x5", 144, (0,)),        # FIN 128, P4 4 (4x1); row-split 64, last block 16 rows
+]
+# The (case, seed) pairs PLANE_CASES replaced, with the HIP step's err / max|g_ref| on an MI355X (profiles/r32_train_planes.txt): each is
+# relu_flip_effect's figure for the float64 run's closest tie, to the four digits recorded -- one unit on the other branch and nothing else
+# (tests/test_train_plane_seeds.py asserts that on the CPU).  A replacement needs a non-empty relu_ties AND the flip's signature (error /
+# allowance >= 4 where a clean run is <= 0.03); at most one seed per case; a case that fails on two of its first four seeds is a finding.
+PLANE_FLIPS = {("connect4_8x8", 128, 0): ("b4", 0.03017), ("connect4_8x8", 400, 2): ("b4", 0.01265), ("connect4_6x8", 272, 0): ("b2", 0.004108)}
 EPS = 2.0 ** -24  # half an ulp of a float32 relative to its magnitude: one rounding
 # One step at L = 16: the stored p1 is rounded to EPS |p1|, EPS |p| / L = 6e-9 in gradient units for the largest parameters (BatchNorm
 # weights, 1.5) -- under the float32 noise of their gradients (1e-6 of 1e-2) -- and one step at L = 16 is still a finite network.
@@ -394,7 +470,8 @@ def update_profile():
 # so parameters, momenta, running statistics, Hyper and the batch decide every bit of a step -- whatever the workspace held before,
 # whatever ran earlier in the process, wherever the caller's arrays lie.  No tolerance, no float64 model, hence no ReLU ties.
 STATE_CASES = [("connect4", 32), ("connect4", 144), ("connect4", 512), ("connect4_5x8", 64), ("othello6", 48), ("othello6", 80), ("othello8", 144),
-               ("tictactoe", 2), ("tictactoe", 64)]  # the smallest batch that reaches each dispatch of enqueue_step
+               ("tictactoe", 2), ("tictactoe", 64),  # the smallest batch that reaches each dispatch of enqueue_step
+               ("connect4_5x5", 16), ("connect4_7x7", 144)]  # fc1's K = 32: most waves have an empty range; K = 288: the last working wave a short one
 STATE_HYPER = (0.1, 0.9, 1e-4)  # lr, momentum, weight decay: the reference's
 
 
